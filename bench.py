@@ -13,9 +13,11 @@ the ranks (BASELINE.json configs[2]: rows of x / Dz / the barrier kernels / the 
 factorisation split by nested-dissection subtrees with a replicated top, RCCL allreduce for the exchanges; strong
 scaling).  `--replicas`: every rank solves its own copy (throughput mode, weak scaling).
 
-One JSON line on rank 0.  Extra objects: `roofline` (dominant HIP kernel, HIP-event timed inside the solve on the
-library's own stream), `cpu_baseline` (the same Newton path on the host cores), `parity` (z against the committed oracle
-vector of this workload, when there is one)."""
+One JSON line on rank 0.  A plain run sets up, warms up, times `--steps` solves and prints the line.  `--full` adds the
+extra objects: `roofline` (dominant HIP kernel, HIP-event timed inside the solve on the library's own stream),
+`cpu_baseline` (the same Newton path on the host cores), `parity` (z against the committed oracle vector of this workload,
+when there is one; the run fails if z does not match) and `kernel_bandwidth_probe` (the barrier / SpMV kernels on a larger
+mesh).  `--dump-outputs DIR` writes what the last timed solve returned as DIR/<name>.npy (see `dump_outputs`)."""
 import argparse
 import json
 import os
@@ -84,22 +86,102 @@ def spawn_ranks(ngpus, argv):
     return subprocess.call(cmd)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, z, n, sol):
+    """What the last timed solve handed back to its caller, as float64 .npy files: `z` (n x S, column-major as the solution
+    of fem2d_mpi_solve), and the SOL_main fields `its` (levels x t-steps Newton counts), `ts` and `c_dot_Dz` (per t-step).
+    Above DUMP_LIMIT_BYTES, `z` keeps a fixed sample of rows (seed 0, sorted) and `z_rows` names them."""
+    os.makedirs(out_dir, exist_ok=True)
+    import numpy as np
+    z = np.asarray(z, dtype=np.float64).reshape((n, -1), order="F")
+    arrays = {"its": np.asarray(sol["its"], dtype=np.float64), "ts": np.asarray(sol["ts"], dtype=np.float64),
+              "c_dot_Dz": np.asarray(sol["c_dot_Dz"], dtype=np.float64)}
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values())
+    if z.nbytes > room:
+        k = room // (8 * (z.shape[1] + 1))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        z = z[rows]
+        arrays["z_rows"] = rows.astype(np.float64)
+    arrays["z"] = z
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def roofline(kern, est, args):
+    """`--full`: the dominant kernel class of the timed solves (event-timed inside the solve) against the HBM peak."""
+    dom = max(est, key=lambda k: est[k])
+    kd = kern[dom]
+    achieved = kd["bytes"] / max(kd["ms"], 1e-12) / 1e6      # GB/s = bytes / ms / 1e6
+    # HBM traffic per launch from the committed PMC passes (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE
+    # runs of this same command, gfx950 FETCH_SIZE x2 correction applied); null for other workloads
+    # (not measured in this run: `traffic_source` names the committed file; null when no committed pass covers the kernel)
+    traffic, traffic_source = None, None
+    for name in ("r3_pmc_traffic.json", "r2_pmc_traffic.json"):
+        try:
+            pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
+            if pmc.get("workload") == "fem2d L=%d p=%g" % (args.L, args.p) and dom in pmc["kernels"]:
+                traffic = pmc["kernels"][dom]["hbm_bytes_per_launch"]
+                traffic_source = "profiles/" + name + " (committed rocprofv3 --pmc passes of this command, not this run)"
+                break
+        except Exception:
+            continue
+    return dict(bound="hbm", kernel=dom, achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s",
+                frac=achieved / HBM_PEAK_GBS, traffic=traffic, traffic_source=traffic_source,
+                avg_launch_us=1e3 * kd["ms"] / max(kd["launches"], 1), launches_timed=kd["launches"],
+                algorithmic_bytes_per_launch=kd["bytes"] / max(kd["launches"], 1),
+                note="latency-bound at this size: every working set is L2/Infinity-Cache resident and the "
+                     "factorisation + solve is a dependent chain of short launches (DESIGN.md sections 4b, 5)",
+                all_kernels={k: dict(gbs=v["bytes"] / max(v["ms"], 1e-12) / 1e6,
+                                     avg_us=1e3 * v["ms"] / max(v["launches"], 1), launches_timed=v["launches"],
+                                     est_total_s=est[k] / 1e3 / args.steps)
+                             for k, v in kern.items() if v["launches"]})
+
+
+def check_parity(out, z_final, args):
+    """`--full`: parity of the timed result, z against the CPU oracle's committed vector for this workload (tests/golden, data
+    only); exits non-zero when it does not match."""
+    import numpy as np
+    gold = os.path.join(ROOT, "tests", "golden", "large_fem2d_L%d_p%s.npz" % (args.L, str(args.p).replace(".", "_")))
+    if not os.path.exists(gold):
+        return
+    gz = np.load(gold)
+    zo = gz["z"].reshape(-1, order="F")
+    relz = float(np.linalg.norm(z_final - zo) / np.linalg.norm(zo))
+    relc = float(abs(out["c_dot_Dz_final"] - gz["c_dot_Dz"][-1]) / abs(gz["c_dot_Dz"][-1]))
+    PARITY_TOL = 1e-10      # the gate below uses the tolerance it reports (ADVICE r2)
+    out["parity"] = {"z_rel_l2_vs_oracle": relz, "c_dot_Dz_rel_vs_oracle": relc, "tolerance": PARITY_TOL,
+                     "oracle_newton_steps": int(gz["its"].sum()), "fixture": os.path.basename(gold)}
+    if "z_centre" in gz.files:       # the oracle's end point polished to the exact centre (tests/golden/polish_centre.py)
+        zc = gz["z_centre"].reshape(-1, order="F")
+        out["parity"]["z_rel_l2_vs_oracle_centre"] = float(np.linalg.norm(z_final - zc) / np.linalg.norm(zc))
+    if not (relz < PARITY_TOL and relc < 1e-9):
+        print(json.dumps(out))
+        raise SystemExit("bench.py: the timed solve does not reproduce the oracle's z (rel l2 %.3e)" % relz)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1)
-    ap.add_argument("--warmup", type=int, default=0)
+    ap.add_argument("--steps", type=int, default=1, help="timed solves (>= 1)")
+    ap.add_argument("--warmup", type=int, default=0, help="untimed solves before the timed ones")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: roofline, parity against the "
+                         "committed oracle vector, kernel bandwidth probe, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed solves, write what the last one returned (z, its, ts, c_dot_Dz) as DIR/<name>.npy")
     ap.add_argument("--L", type=int, default=7)
     ap.add_argument("--p", type=float, default=1.0)
-    ap.add_argument("--cpu-budget", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="--full: seconds of host time for cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--verbose", type=int, default=0)
     ap.add_argument("--replicas", action="store_true",
                     help="N>1: one independent replica of the workload per rank (throughput mode, weak scaling) instead of "
                          "ONE row-block sharded solve over all ranks (the default, BASELINE.json configs[2])")
     ap.add_argument("--shard", action="store_true", help="(default for N>1; kept for compatibility)")
     ap.add_argument("--probe-L", type=int, default=9,
-                    help="after the timed region, HIP-event time the barrier / SpMV kernels on this larger mesh with rotating "
+                    help="--full: after the timed region, HIP-event time the barrier / SpMV kernels on this larger mesh with rotating "
                          "buffers (0 = skip): the size at which they leave the launch-latency regime")
     ap.add_argument("--solver", choices=("gpu", "pcg"), default="gpu",
                     help="Newton linear solver: device multifrontal Cholesky (default) or V-cycle-preconditioned CG with the "
@@ -110,7 +192,10 @@ def parse_args(argv=None):
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="N>1 on a single-GPU box: every rank uses cuda:0 and torch.distributed runs on gloo (RCCL refuses "
                          "two ranks on one device); exercises the multi-rank control flow, not a measurement")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def main():
@@ -224,32 +309,6 @@ def main():
                 d["ms"] += v["ms"]; d["bytes"] += v["bytes"]; d["launches"] += v["launches"]
         # kernels are event-timed on every 8th Newton step only (bracketing every launch costs ~14 % of the solve)
         est = {k: v["ms"] * 8.0 for k, v in kern.items()}
-        dom = max(est, key=lambda k: est[k])
-        kd = kern[dom]
-        achieved = kd["bytes"] / max(kd["ms"], 1e-12) / 1e6      # GB/s = bytes / ms / 1e6
-        # HBM traffic per launch from the committed PMC passes (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE
-        # runs of this same command, gfx950 FETCH_SIZE x2 correction applied); null for other workloads
-        # (not measured in this run: `traffic_source` names the committed file; null when no committed pass covers the kernel)
-        traffic, traffic_source = None, None
-        for name in ("r3_pmc_traffic.json", "r2_pmc_traffic.json"):
-            try:
-                pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
-                if pmc.get("workload") == "fem2d L=%d p=%g" % (args.L, args.p) and dom in pmc["kernels"]:
-                    traffic = pmc["kernels"][dom]["hbm_bytes_per_launch"]
-                    traffic_source = "profiles/" + name + " (committed rocprofv3 --pmc passes of this command, not this run)"
-                    break
-            except Exception:
-                continue
-        roofline = dict(bound="hbm", kernel=dom, achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s",
-                        frac=achieved / HBM_PEAK_GBS, traffic=traffic, traffic_source=traffic_source,
-                        avg_launch_us=1e3 * kd["ms"] / max(kd["launches"], 1), launches_timed=kd["launches"],
-                        algorithmic_bytes_per_launch=kd["bytes"] / max(kd["launches"], 1),
-                        note="latency-bound at this size: every working set is L2/Infinity-Cache resident and the "
-                             "factorisation + solve is a dependent chain of short launches (DESIGN.md sections 4b, 5)",
-                        all_kernels={k: dict(gbs=v["bytes"] / max(v["ms"], 1e-12) / 1e6,
-                                             avg_us=1e3 * v["ms"] / max(v["launches"], 1), launches_timed=v["launches"],
-                                             est_total_s=est[k] / 1e3 / args.steps)
-                                     for k, v in kern.items() if v["launches"]})
         out = {
             "metric": "fem2d p-Laplace DoF/s per Newton step", "value": value, "unit": "DoF/s per Newton step",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -270,24 +329,7 @@ def main():
             "linear_solve_s_per_solve": sum(s["time_factor"] for s in sols) / args.steps,
             "barrier_spmv_kernel_s_per_solve": sum(est[k] for k in kern if not k.startswith("chol_")) / 1e3 / args.steps,
             "t_final": float(last["ts"][-1]), "c_dot_Dz_final": float(last["c_dot_Dz"][-1]),
-            "roofline": roofline,
         }
-        # parity of the timed result: z against the CPU oracle's committed vector for this workload (tests/golden, data only)
-        gold = os.path.join(ROOT, "tests", "golden", "large_fem2d_L%d_p%s.npz" % (args.L, str(args.p).replace(".", "_")))
-        if os.path.exists(gold):
-            gz = np.load(gold)
-            zo = gz["z"].reshape(-1, order="F")
-            relz = float(np.linalg.norm(z_final - zo) / np.linalg.norm(zo))
-            relc = float(abs(out["c_dot_Dz_final"] - gz["c_dot_Dz"][-1]) / abs(gz["c_dot_Dz"][-1]))
-            PARITY_TOL = 1e-10      # the gate below uses the tolerance it reports
-            out["parity"] = {"z_rel_l2_vs_oracle": relz, "c_dot_Dz_rel_vs_oracle": relc, "tolerance": PARITY_TOL,
-                             "oracle_newton_steps": int(gz["its"].sum()), "fixture": os.path.basename(gold)}
-            if "z_centre" in gz.files:       # the oracle's end point polished to the exact centre (tests/golden/polish_centre.py)
-                zc = gz["z_centre"].reshape(-1, order="F")
-                out["parity"]["z_rel_l2_vs_oracle_centre"] = float(np.linalg.norm(z_final - zc) / np.linalg.norm(zc))
-            if not (relz < PARITY_TOL and relc < 1e-9):
-                print(json.dumps(out))
-                raise SystemExit("bench.py: the timed solve does not reproduce the oracle's z (rel l2 %.3e)" % relz)
         if args.solver == "pcg":
             out["pcg"] = {k: sum(s["pcg"][k] for s in sols) for k in ("solves", "iterations", "fallbacks", "seconds")}
             out["pcg"]["gave_up_at_newton_system"] = last["pcg"]["gave_up_at"]
@@ -302,15 +344,20 @@ def main():
                                                          "bytes": st["bytes"] / max(newton_steps, 1)},
                                     hessian_values_stay_on_their_rank=info["values_local"],
                                     factorisation_split_over=info["split_world"])
-        if args.probe_L > 0 and world == 1:      # N=1 only, like the CPU baseline
-            # secondary evidence for the bandwidth-shaped kernels: the same kernels on the
-            # workload mesh (cache resident, launch bound) and on a mesh whose rotating working set exceeds the 256 MiB
-            # Infinity Cache
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            import spmv_roofline
-            out["kernel_bandwidth_probe"] = [spmv_roofline.probe(L, args.p) for L in sorted({args.L, args.probe_L})]
-        if not args.no_cpu_baseline and world == 1:      # the contract: rank 0 at N=1 only
-            out["cpu_baseline"] = cpu_baseline(args.L, args.p, args.cpu_budget)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, z_final, n, last)
+        if args.full:
+            out["roofline"] = roofline(kern, est, args)
+            check_parity(out, z_final, args)
+            if args.probe_L > 0 and world == 1:      # N=1 only, like the CPU baseline
+                # secondary evidence for the bandwidth-shaped kernels: the same kernels on the
+                # workload mesh (cache resident, launch bound) and on a mesh whose rotating working set exceeds the 256 MiB
+                # Infinity Cache
+                sys.path.insert(0, os.path.join(ROOT, "tools"))
+                import spmv_roofline
+                out["kernel_bandwidth_probe"] = [spmv_roofline.probe(L, args.p) for L in sorted({args.L, args.probe_L})]
+            if not args.no_cpu_baseline and world == 1:      # the contract: rank 0 at N=1 only
+                out["cpu_baseline"] = cpu_baseline(args.L, args.p, args.cpu_budget)
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()

@@ -1,7 +1,6 @@
 import sys, numpy as np
-sys.path.insert(0, "/root/repo")
 import os
-ROOT=os.environ.get("GRAFT_REPO_ROOT","/root/repo"); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import mgb_amd as M
 for kind,L,p in (("fem2d",7,1.0),("fem2d",7,1.5),("fem3d",4,1.0),("fem2d",8,1.0)):
     res={}

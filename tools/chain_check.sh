@@ -18,7 +18,7 @@ python3 tools/chol_timeline.py report "$out/tl" > "$out/chol_timeline.txt"
 rm -rf "$out/tl"
 grep -v "^#" "$out/chol_timeline.txt" | awk '{printf "%s:%s ", substr($2,1,12), $4} END {print ""}'
 grep "^# span\|launches" "$out/chol_timeline.txt"
-timeout -k 10 200 python3 bench.py --no-cpu-baseline --probe-L 0 > "$out/bench.log" 2> "$out/bench.err"
+timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --probe-L 0 > "$out/bench.log" 2> "$out/bench.err"
 python3 - "$out/bench.log" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

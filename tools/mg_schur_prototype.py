@@ -1,5 +1,5 @@
-import sys, time
-sys.path.insert(0, "/root/repo/oracle")
+import os, sys, time
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
 import numpy as np, scipy.sparse as sp, scipy.sparse.linalg as spla
 import mgb_oracle as O
 

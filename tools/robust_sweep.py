@@ -7,6 +7,7 @@ import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -33,14 +34,15 @@ if __name__ == "__main__":
                 ("panel_update_pairs", {"MGB_CHOL_STEP2_TILES": "0"}), ("dense_single_tiles", {"MGB_CHOL_DENSE_TILES": "0"})]
     zs = {}
     print("# fem2d L=%d p=%g: one solve per variant (fresh process each)" % (L, p))
-    for name, env in variants:
-        out = "/tmp/robust_%s.npy" % name
-        r = subprocess.run([sys.executable, "-c", CHILD % (ROOT, L, p), out], env=dict(os.environ, **env), capture_output=True, text=True)
-        if r.returncode != 0:
-            print(name, "FAILED", r.stderr[-300:])
-            continue
-        info = json.loads(r.stdout.strip().splitlines()[-1])
-        zs[name] = np.load(out)
-        d = np.linalg.norm(zs[name] - zs["default"]) / np.linalg.norm(zs["default"]) if "default" in zs else 0.0
-        print("%-18s newton %4d  t-steps %3d  t_final %.6g  c.Dz %.15g  |z - z_default|/|z| = %.3e" % (
-            name, info["newton"], info["nt"], info["t_final"], info["cdot"], d), flush=True)
+    with tempfile.TemporaryDirectory(prefix="robust_sweep_") as tmp:
+        for name, env in variants:
+            out = os.path.join(tmp, name + ".npy")
+            r = subprocess.run([sys.executable, "-c", CHILD % (ROOT, L, p), out], env=dict(os.environ, **env), capture_output=True, text=True)
+            if r.returncode != 0:
+                print(name, "FAILED", r.stderr[-300:])
+                continue
+            info = json.loads(r.stdout.strip().splitlines()[-1])
+            zs[name] = np.load(out)
+            d = np.linalg.norm(zs[name] - zs["default"]) / np.linalg.norm(zs["default"]) if "default" in zs else 0.0
+            print("%-18s newton %4d  t-steps %3d  t_final %.6g  c.Dz %.15g  |z - z_default|/|z| = %.3e" % (
+                name, info["newton"], info["nt"], info["t_final"], info["cdot"], d), flush=True)

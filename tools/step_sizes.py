@@ -1,5 +1,5 @@
 import sys, os, re, subprocess
-ROOT=os.environ.get("GRAFT_REPO_ROOT","/root/repo"); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import mgb_amd as M, io, contextlib
 import collections
 # verbose=2 prints per Newton step to stderr: capture via fd redirect
