@@ -1065,10 +1065,7 @@ bool Amg::dev_f2_solve(Level& lv, const double* dz, double t, SolveStats& st, do
     //   sampled steps (every 8th, when timing is on): plain launches bracketed by HIP events (KernelTimer);
     //   single GPU otherwise: ONE hipGraph launch for chain + <g, n> + both speculative trials (launch_step_graph);
     //   sharded: chain (split by subtrees, two collectives inside), then dot and trials with their collectives.
-    static const bool use_graph = [] {
-      const char* e = std::getenv("MGB_CHOL_GRAPH");
-      return !(e && e[0] == '0');
-    }();
+    const bool use_graph = GpuChol::knobs().graph;
     KernelTimer* tm = (live_ && timer_.sampling()) ? &timer_ : nullptr;
     const bool flag_rides = ctx_.world == 1;      // the dot kernel behind the chain hands the pivot flag to the host and re-arms it
     hipEvent_t e0 = nullptr, e1 = nullptr;

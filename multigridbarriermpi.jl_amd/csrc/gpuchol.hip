@@ -1481,6 +1481,248 @@ GpuChol::~GpuChol() {
   for (void* p : allocs_) (void)hipFree(p);
 }
 
+// The chain's job arrays, uploaded once at the end of build(): every Launch indexes one of them
+struct GpuChol::Jobs {
+  std::vector<int> lists;      // node lists per height
+  std::vector<StartJob> starts;
+  std::vector<StepTile> tiles;
+  std::vector<SingleTile> singles;
+  std::vector<RectJob> rects;
+};
+
+const CholKnobs& GpuChol::knobs() {
+  static const CholKnobs k = [] {
+    auto on = [](const char* name) {      // default on; "0..." turns it off
+      const char* e = std::getenv(name);
+      return !(e && e[0] == '0');
+    };
+    auto num = [](const char* name, int dflt) {
+      const char* e = std::getenv(name);
+      return e ? std::atoi(e) : dflt;
+    };
+    CholKnobs c;
+    c.graph = on("MGB_CHOL_GRAPH");
+    c.prof = std::getenv("MGB_CHOL_PROF") != nullptr;
+    c.leaf = on("MGB_CHOL_LEAF");
+    c.single = on("MGB_CHOL_SINGLE");
+    c.step2 = on("MGB_CHOL_STEP2");
+    c.wide = on("MGB_CHOL_WIDE");
+    c.start_pivot = on("MGB_CHOL_START_PIVOT");
+    c.step2_tiles = num("MGB_CHOL_STEP2_TILES", 224);
+    c.dense_tiles = num("MGB_CHOL_DENSE_TILES", 512);      // what two tiles per CU hold at once
+    c.bwd_split_nf = num("MGB_BWD_SPLIT_NF", 192);
+    return c;
+  }();
+  return k;
+}
+
+namespace {
+
+// the workgroup of front g (node t) that factors the pivot block after panel p
+StepTile pivot_tile(const GNode& g, int t, int p) {
+  StepTile st{};
+  st.off = g.off;
+  st.loff = g.loff + (long long)p * 2 * PB * PB;
+  st.nf = g.nf;
+  st.ns = g.ns;
+  st.pad = t;      // node index (front_single_kernel)
+  return st;
+}
+
+// Appends the 64x64 tiles of front g's trailing matrix from row k on, after panel p: the lower triangle or (column) one
+// tile per 64-row block below the next pivot block -- the workgroups of a panel launch.  Returns how many.
+int append_tiles(std::vector<StepTile>& out, const GNode& g, int t, int p, int k, bool column) {
+  StepTile st = pivot_tile(g, t, p);
+  const size_t n0 = out.size();
+  if (column) {
+    const int Tr = std::max(0, (g.nf + 1 - k - PB + TS - 1) / TS);
+    for (int ti = 0; ti < Tr; ++ti) {
+      st.ti = st.tj = (short)ti;
+      out.push_back(st);
+    }
+  } else {
+    const int Tr = (g.nf + 1 - k + TS - 1) / TS, Tc = std::max(1, (g.nf - k + TS - 1) / TS);
+    if (Tr > 30000) throw ArgError("gpuchol: front too large for tile index");
+    for (int ti = 0; ti < Tr; ++ti)
+      for (int tj = 0; tj <= std::min(ti, Tc - 1); ++tj) {
+        st.ti = (short)ti;
+        st.tj = (short)tj;
+        out.push_back(st);
+      }
+  }
+  return (int)(out.size() - n0);
+}
+
+SingleTile single_tile(const std::vector<GNode>& nodes, const StepTile& s) {
+  const GNode& g = nodes[s.pad];
+  SingleTile u{};
+  u.off = g.off;
+  u.loff = g.loff;
+  u.nf = g.nf;
+  u.ns = g.ns;
+  u.iofs = g.iofs;
+  u.a0 = g.a0;
+  u.a1 = g.a1;
+  u.first = g.first;
+  u.ti = s.ti;
+  u.tj = s.tj;
+  for (int sI = 0; sI < 2; ++sI) {
+    u.boff[sI] = g.off;
+    u.cld[sI] = 0;
+    if (g.child[sI] >= 0) {
+      const GNode& c = nodes[g.child[sI]];
+      u.cld[sI] = c.nf + 1;
+      u.boff[sI] = c.off + (long long)u.cld[sI] * c.ns + c.ns;
+    }
+  }
+  return u;
+}
+
+}  // namespace
+
+// Appends the launches of one node set to chain_ -- the forward ones height by height from the leaves, then the backward
+// ones from the root -- and their jobs to `jobs`; returns where the backward ones begin.  heights[h]: the set's nodes of
+// tree height h.
+int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::vector<GNode>& nodes,
+                      const std::vector<std::vector<StartJob>>& sjobs, const MfChol& sym, Jobs& jobs) {
+  const CholKnobs& kn = knobs();
+  std::vector<Launch> bwd;
+  std::vector<StepTile> scratch;
+  for (const std::vector<int>& mine : heights) {
+    if (mine.empty()) continue;
+    const int nofs = (int)jobs.lists.size(), ncnt = (int)mine.size();
+    jobs.lists.insert(jobs.lists.end(), mine.begin(), mine.end());
+    int max_ns = 0, max_nf = 0;
+    bool childless = true, all_pivots = true;      // a pass-through front (ns = 0) needs front_start to copy it
+    double start_bytes = 0;
+    for (int t : mine) {
+      const GNode& g = nodes[t];
+      max_ns = std::max(max_ns, g.ns);
+      max_nf = std::max(max_nf, g.nf);
+      childless = childless && g.child[0] < 0 && g.child[1] < 0;
+      all_pivots = all_pivots && g.ns >= 1;
+      start_bytes += 0.5 * g.nf * g.nf * 8.0 + (double)sym.a_idx_[t].size() * 20.0;
+      for (int c : g.child) {
+        if (c < 0) continue;
+        const double cnb = nodes[c].nf - nodes[c].ns;
+        start_bytes += 0.5 * cnb * cnb * 8.0;     // child entry read (the parent entry write is counted above)
+      }
+    }
+    // leaf heights with small fronts: the whole front in one workgroup (front_leaf_kernel)
+    const bool leaf = kn.leaf && max_nf <= 95 && max_ns <= 2 * PB && childless && all_pivots;
+    // single-panel heights with children: one dependency-free launch (front_single_kernel)
+    const bool single = kn.single && max_ns <= PB && !childless && all_pivots;
+    if (leaf) {
+      const size_t lds = ((size_t)(max_nf + 1) * max_nf - (size_t)max_nf * (max_nf - 1) / 2) * sizeof(double);
+      chain_.push_back({Kind::Leaf, nofs, ncnt, TB, lds, 0, 0, false, KC_CHOL_SINGLE, start_bytes});
+    } else if (!single) {
+      const int ofs = (int)jobs.starts.size();
+      if (kn.start_pivot)      // dedicated pivot jobs first: they are what the first panel launch waits for
+        for (int t : mine)
+          if (nodes[t].ns > 0 && !sjobs[t].empty()) {
+            StartJob pj = sjobs[t].front();      // chunk 0, row block 0: its assembly range covers the pivot block
+            pj.rb = -1;
+            jobs.starts.push_back(pj);
+          }
+      for (int t : mine) jobs.starts.insert(jobs.starts.end(), sjobs[t].begin(), sjobs[t].end());
+      chain_.push_back({Kind::Start, ofs, (int)jobs.starts.size() - ofs, TB, 0, 0, 0, false, KC_CHOL_START, start_bytes});
+    }
+    // panel launches, pivot-owning workgroups first: they are the critical path of the next launch
+    const int npanel = leaf ? 0 : (max_ns + PB - 1) / PB;
+    for (int p = 0; p < npanel; ++p) {
+      // two panels per launch (front_step2) while the height has at least two left; the odd last one runs front_step
+      // ... and only where the launch is latency-bound (its tiles fit the chip in one round): front_step2 holds 115 KB of
+      // LDS, one workgroup per CU, and loses against two rank-32 launches at 2-3 workgroups per CU on the big 3-D heights
+      const bool two = kn.step2 && !single && p + 1 < npanel;
+      int ntile2 = 0;
+      if (two) {
+        scratch.clear();
+        for (int t : mine)
+          if (nodes[t].ns > p * PB) ntile2 += append_tiles(scratch, nodes[t], t, p, std::min(nodes[t].ns, (p + 2) * PB), false);
+      }
+      const bool pair = two && ntile2 <= kn.step2_tiles;
+      const int ofs = (int)jobs.tiles.size();
+      int npiv = 0;
+      double bytes = 0;
+      if (two && !pair && kn.wide) {
+        // beyond that tile count: the same two panels as a panel launch (one workgroup per 64-row block, row block 0 also
+        // factors the next pivot block) and an update launch (the tiles, rank-64, nothing else) -- see front_step2_body
+        for (int t : mine) {
+          const GNode& g = nodes[t];
+          if (g.ns <= p * PB) continue;
+          jobs.tiles.push_back(pivot_tile(g, t, p));      // the front's pivot workgroup: trailing rows k2 .. k2 + 31
+          npiv++;
+          const int k2 = std::min(g.ns, (p + 2) * PB);
+          const double tr = g.nf + 1 - k2;
+          bytes += tr * (k2 - p * PB) * 32.0;      // panel read, mirrored + in-place write
+        }
+        for (int t : mine)
+          if (nodes[t].ns > p * PB) append_tiles(jobs.tiles, nodes[t], t, p, std::min(nodes[t].ns, (p + 2) * PB), true);
+        chain_.push_back({Kind::Panel2, ofs, (int)jobs.tiles.size() - ofs, TB, kPanel2Lds, p, npiv, false, KC_CHOL_STEP, bytes});
+        const int uofs = (int)jobs.tiles.size();
+        double ubytes = 0;
+        for (int t : mine) {
+          const GNode& g = nodes[t];
+          if (g.ns <= p * PB) continue;
+          const int k2 = std::min(g.ns, (p + 2) * PB);
+          append_tiles(jobs.tiles, g, t, p, k2, false);
+          const double tr = g.nf + 1 - k2;
+          ubytes += tr * (k2 - p * PB) * 8.0 + 0.5 * tr * tr * 16.0;      // solved panel read, trailing read + write
+        }
+        chain_.push_back({Kind::Update2, uofs, (int)jobs.tiles.size() - uofs, TB, kUpdate2Lds, p, 0, false, KC_CHOL_STEP, ubytes});
+        ++p;
+        continue;
+      }
+      const int np = pair ? 2 : 1;
+      for (int t : mine) {
+        const GNode& g = nodes[t];
+        if (g.ns <= p * PB) continue;
+        const int k1 = std::min(g.ns, (p + np) * PB), kw = k1 - p * PB;      // first trailing row, pivots of this launch
+        if (k1 < g.ns) {
+          jobs.tiles.push_back(pivot_tile(g, t, p));
+          npiv++;
+        }
+        const double tr = g.nf + 1 - k1;
+        bytes += tr * kw * 16.0 + 0.5 * tr * tr * 16.0;      // panel read + mirrored write, trailing read + write
+      }
+      for (int t : mine)
+        if (nodes[t].ns > p * PB) append_tiles(jobs.tiles, nodes[t], t, p, std::min(nodes[t].ns, (p + np) * PB), false);
+      const int cnt = (int)jobs.tiles.size() - ofs;
+      if (single) {      // same tiles, self-contained descriptors
+        const int sofs = (int)jobs.singles.size();
+        for (int q = ofs; q < ofs + cnt; ++q) jobs.singles.push_back(single_tile(nodes, jobs.tiles[q]));
+        const bool narrow = max_ns <= 8, dense = cnt > kn.dense_tiles;
+        const Kind k = dense ? (narrow ? Kind::SingleDenseNarrow : Kind::SingleDense) : (narrow ? Kind::SingleNarrow : Kind::Single);
+        chain_.push_back({k, sofs, cnt, TB, 0, 0, 0, false, KC_CHOL_SINGLE, start_bytes + bytes});
+      } else {
+        chain_.push_back({pair ? Kind::Step2 : Kind::Step, ofs, cnt, TB, pair ? (size_t)kStep2Lds : 0, p, npiv, false, KC_CHOL_STEP, bytes});
+      }
+      if (pair) ++p;
+    }
+    // backward: above bwd_split_nf the rectangular part runs in its own multi-workgroup launch first
+    const bool split = max_nf > kn.bwd_split_nf;
+    const int rofs = (int)jobs.rects.size();
+    double rect_bytes = 0, tri_bytes = 0;
+    for (int t : mine) {
+      const GNode& g = nodes[t];
+      const double nb = g.nf - g.ns;
+      rect_bytes += nb * g.ns * 8.0 + nb * 12.0;
+      tri_bytes += 0.5 * g.ns * g.ns * 8.0 + g.ns * 28.0;
+      if (split && nb > 0)
+        for (int ch = 0; ch * 64 < g.ns; ++ch) jobs.rects.push_back({t, ch});
+    }
+    const int nrect = (int)jobs.rects.size() - rofs, nt = max_nf > 384 ? 1024 : 256;
+    std::vector<Launch> h;
+    if (nrect) h.push_back({Kind::BwdRect, rofs, nrect, RT, (size_t)(max_nf + RT) * sizeof(double), 0, 0, false, KC_CHOL_BWD_RECT, rect_bytes});
+    h.push_back({nt == 1024 ? Kind::Bwd1024 : Kind::Bwd256, nofs, ncnt, nt, (size_t)(max_nf + nt + PB) * sizeof(double), 0, 0, nrect > 0,
+                 KC_CHOL_BWD, tri_bytes + (nrect ? 0.0 : rect_bytes)});
+    bwd.insert(bwd.begin(), h.begin(), h.end());      // the backward sweep runs from the root
+  }
+  const int first_bwd = (int)chain_.size();
+  chain_.insert(chain_.end(), bwd.begin(), bwd.end());
+  return first_bwd;
+}
+
 void GpuChol::build(const MfChol& sym, Ctx* ctx) {
   ctx_ = ctx;
   part_ = (ctx && ctx->world > 1) ? sym.partition(ctx->world) : CholPartition();
@@ -1594,277 +1836,17 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
     nodes[t].a0 = sjobs[t].empty() ? 0 : sjobs[t].front().a0;
     nodes[t].a1 = sjobs[t].empty() ? 0 : sjobs[t].back().a1;
   }
-  // schedule
-  static const bool leaf_ok = [] {
-    const char* e = std::getenv("MGB_CHOL_LEAF");
-    return !(e && e[0] == '0');
-  }();
-  static const bool single_ok = [] {
-    const char* e = std::getenv("MGB_CHOL_SINGLE");
-    return !(e && e[0] == '0');
-  }();
-  static const bool step2_ok = [] {      // MGB_CHOL_STEP2=0: one panel per launch everywhere (the scheme before front_step2)
-    const char* e = std::getenv("MGB_CHOL_STEP2");
-    return !(e && e[0] == '0');
-  }();
-  static const bool start_pivot_ok = [] {      // MGB_CHOL_START_PIVOT=0: the first pivot block is factored by the assembling workgroup
-    const char* e = std::getenv("MGB_CHOL_START_PIVOT");
-    return !(e && e[0] == '0');
-  }();
-  start_pivot_ = start_pivot_ok;
-  static const bool wide_ok = [] {      // MGB_CHOL_WIDE=0: one panel per launch beyond the fused kernel's tile count (the scheme before)
-    const char* e = std::getenv("MGB_CHOL_WIDE");
-    return !(e && e[0] == '0');
-  }();
-  static const int step2_max_tiles = [] {
-    const char* e = std::getenv("MGB_CHOL_STEP2_TILES");
-    return e ? std::atoi(e) : 224;
-  }();
-  static const int split_nf = [] {
-    const char* e = std::getenv("MGB_BWD_SPLIT_NF");
-    return e ? std::atoi(e) : 192;
-  }();
-  std::vector<SingleTile> singles;
-  std::vector<int> lists;
-  std::vector<StartJob> starts;
-  std::vector<StepTile> tiles;
-  std::vector<RectJob> rects;
-  launches_ = 0;
-  // one schedule per node set: `which` = 0 own nodes (split: this rank's subtree; else everything), 1 = the replicated top
-  auto make_plans = [&](int which, std::vector<HeightPlan>& out) {
-  out.clear();
-  for (int h = 0; h < nheights_; ++h) {
-    HeightPlan hp_new;
-    HeightPlan& hp = hp_new;
-    hp.nodes.ofs = (int)lists.size();
-    int max_ns = 0;
-    hp.max_nf = 0;
-    std::vector<int> mine;
-    for (int t = 0; t < nnodes_; ++t)
-      if (height[t] == h && (part_.split() ? (which == 0 ? part_.owner[t] == my_rank : part_.owner[t] < 0) : which == 0)) {
-        mine.push_back(t);
-        max_ns = std::max(max_ns, nodes[t].ns);
-        hp.max_nf = std::max(hp.max_nf, nodes[t].nf);
-      }
-    if (mine.empty()) continue;
-    lists.insert(lists.end(), mine.begin(), mine.end());
-    hp.nodes.cnt = (int)mine.size();
-    // leaf heights with small fronts: the whole front in one workgroup (front_leaf_kernel)
-    {
-      bool leaf = leaf_ok && hp.max_nf <= 95 && max_ns <= 2 * PB;
-      for (int t : mine) leaf = leaf && nodes[t].child[0] < 0 && nodes[t].child[1] < 0 && nodes[t].ns >= 1;
-      hp.leaf = leaf && !mine.empty();
-    }
-    // single-panel heights with children: one dependency-free launch (front_single_kernel)
-    bool any_child = false, all_pivots = true;
-    for (int t : mine) {
-      any_child = any_child || nodes[t].child[0] >= 0 || nodes[t].child[1] >= 0;
-      all_pivots = all_pivots && nodes[t].ns >= 1;      // a pass-through front (ns = 0) needs front_start to copy it
-    }
-    hp.single = single_ok && max_ns <= PB && any_child && all_pivots;
-    hp.narrow = hp.single && max_ns <= 8;
-    // front_start jobs
-    hp.start.ofs = (int)starts.size();
-    hp.start_bytes = 0;
-    for (int t : mine) {
-      const GNode& g = nodes[t];
-      hp.start_bytes += 0.5 * g.nf * g.nf * 8.0 + (double)sym.a_idx_[t].size() * 20.0;
-      for (int s = 0; s < 2; ++s) {
-        const int c = g.child[s];
-        if (c < 0) continue;
-        const double cnb = nodes[c].nf - nodes[c].ns;
-        hp.start_bytes += 0.5 * cnb * cnb * 8.0;     // child entry read (the parent entry write is counted above)
-      }
-    }
-    if (!hp.single && !hp.leaf) {
-      if (start_pivot_ok)      // dedicated pivot jobs first: they are what the first panel launch waits for
-        for (int t : mine)
-          if (nodes[t].ns > 0 && !sjobs[t].empty()) {
-            StartJob pj = sjobs[t].front();      // chunk 0, row block 0: its assembly range covers the pivot block
-            pj.rb = -1;
-            starts.push_back(pj);
-          }
-      for (int t : mine) starts.insert(starts.end(), sjobs[t].begin(), sjobs[t].end());
-    }
-    hp.start.cnt = (int)starts.size() - hp.start.ofs;
-    launches_++;
-    // front_step tiles, pivot-owning (0,0) tiles first
-    const int npanel = hp.leaf ? 0 : (max_ns + PB - 1) / PB;
-    for (int p = 0; p < npanel; ++p) {
-      Range rt{(int)tiles.size(), 0};
-      double bytes = 0;
-      int npiv = 0;
-      // two panels per launch (front_step2) while the height has at least two left; the odd last one runs front_step
-      // ... and only where the launch is latency-bound (its tiles fit the chip in one round): front_step2 holds 115 KB of
-      // LDS, one workgroup per CU, and loses against two rank-32 launches at 2-3 workgroups per CU on the big 3-D heights
-      int ntile2 = 0;
-      for (int t : mine) {
-        const GNode& g = nodes[t];
-        if (g.ns <= p * PB) continue;
-        const int k2 = std::min(g.ns, (p + 2) * PB), Tr = (g.nf + 1 - k2 + TS - 1) / TS, Tc = std::max(1, (g.nf - k2 + TS - 1) / TS);
-        for (int ti = 0; ti < Tr; ++ti) ntile2 += std::min(ti, Tc - 1) + 1;
-      }
-      const bool pair = step2_ok && !hp.single && p + 1 < npanel && ntile2 <= step2_max_tiles;
-      // beyond that tile count: the same two panels as a panel launch (one workgroup per 64-row block, row block 0 also
-      // factors the next pivot block) and an update launch (the tiles, rank-64, nothing else) -- see front_step2_body
-      const bool wide = wide_ok && step2_ok && !hp.single && p + 1 < npanel && !pair;
-      if (wide) {
-        double pbytes = 0, ubytes = 0;
-        for (int t : mine) {
-          const GNode& g = nodes[t];
-          if (g.ns <= p * PB) continue;
-          const int k2 = std::min(g.ns, (p + 2) * PB), Tr = (g.nf + 1 - k2 + TS - 1) / TS;
-          StepTile st{};
-          st.off = g.off;
-          st.loff = g.loff + (long long)p * 2 * PB * PB;
-          st.nf = g.nf;
-          st.ns = g.ns;
-          st.pad = t;
-          (void)Tr;
-          tiles.push_back(st);      // the front's pivot workgroup: trailing rows k2 .. k2 + 31
-          npiv++;
-          const double tr = g.nf + 1 - k2;
-          pbytes += tr * (k2 - p * PB) * 32.0;      // panel read, mirrored + in-place write
-        }
-        for (int t : mine) {
-          const GNode& g = nodes[t];
-          if (g.ns <= p * PB) continue;
-          const int k2 = std::min(g.ns, (p + 2) * PB), Trw = std::max(0, (g.nf + 1 - k2 - PB + TS - 1) / TS);
-          StepTile st{};
-          st.off = g.off;
-          st.loff = g.loff + (long long)p * 2 * PB * PB;
-          st.nf = g.nf;
-          st.ns = g.ns;
-          st.pad = t;
-          for (int ti = 0; ti < Trw; ++ti) {
-            st.ti = st.tj = (short)ti;
-            tiles.push_back(st);
-          }
-        }
-        rt.cnt = (int)tiles.size() - rt.ofs;
-        hp.step_npiv.push_back(npiv);
-        hp.step.push_back(rt);
-        hp.step_bytes.push_back(pbytes);
-        hp.step_p.push_back(p);
-        hp.step_pair.push_back(2);
-        launches_++;
-        Range ru{(int)tiles.size(), 0};
-        for (int t : mine) {
-          const GNode& g = nodes[t];
-          if (g.ns <= p * PB) continue;
-          const int k2 = std::min(g.ns, (p + 2) * PB), Tr = (g.nf + 1 - k2 + TS - 1) / TS, Tc = std::max(1, (g.nf - k2 + TS - 1) / TS);
-          if (Tr > 30000) throw ArgError("gpuchol: front too large for tile index");
-          StepTile st{};
-          st.off = g.off;
-          st.loff = g.loff + (long long)p * 2 * PB * PB;
-          st.nf = g.nf;
-          st.ns = g.ns;
-          st.pad = t;
-          for (int ti = 0; ti < Tr; ++ti)
-            for (int tj = 0; tj <= std::min(ti, Tc - 1); ++tj) {
-              st.ti = (short)ti;
-              st.tj = (short)tj;
-              tiles.push_back(st);
-            }
-          const double tr = g.nf + 1 - k2;
-          ubytes += tr * (k2 - p * PB) * 8.0 + 0.5 * tr * tr * 16.0;      // solved panel read, trailing read + write
-        }
-        ru.cnt = (int)tiles.size() - ru.ofs;
-        hp.step_npiv.push_back(0);
-        hp.step.push_back(ru);
-        hp.step_bytes.push_back(ubytes);
-        hp.step_p.push_back(p);
-        hp.step_pair.push_back(3);
-        launches_++;
-        ++p;
-        continue;
-      }
-      const int np = pair ? 2 : 1;
-      for (int pass = 0; pass < 2; ++pass)
-        for (int t : mine) {
-          const GNode& g = nodes[t];
-          if (g.ns <= p * PB) continue;
-          const int k1 = std::min(g.ns, (p + np) * PB), kw = k1 - p * PB;      // first trailing row, pivots of this launch
-          StepTile st{};
-          st.off = g.off;
-          st.loff = g.loff + (long long)p * 2 * PB * PB;
-          st.nf = g.nf;
-          st.ns = g.ns;
-          st.pad = t;      // node index (front_single_kernel)
-          if (pass == 0) {      // pivot workgroups first: they are the critical path of the next launch
-            if (k1 < g.ns) {
-              tiles.push_back(st);
-              npiv++;
-            }
-            const double tr = g.nf + 1 - k1;
-            bytes += tr * kw * 16.0 + 0.5 * tr * tr * 16.0;      // panel read + mirrored write, trailing read + write
-            continue;
-          }
-          const int Tr = (g.nf + 1 - k1 + TS - 1) / TS, Tc = std::max(1, (g.nf - k1 + TS - 1) / TS);
-          if (Tr > 30000) throw ArgError("gpuchol: front too large for tile index");
-          for (int ti = 0; ti < Tr; ++ti)
-            for (int tj = 0; tj <= std::min(ti, Tc - 1); ++tj) {
-              st.ti = (short)ti;
-              st.tj = (short)tj;
-              tiles.push_back(st);
-            }
-        }
-      hp.step_npiv.push_back(npiv);
-      if (hp.single) {      // same tiles, self-contained descriptors
-        hp.single_tiles.ofs = (int)singles.size();
-        for (int q = rt.ofs; q < (int)tiles.size(); ++q) {
-          const GNode& g = nodes[tiles[q].pad];
-          SingleTile u{};
-          u.off = g.off;
-          u.loff = g.loff;
-          u.nf = g.nf;
-          u.ns = g.ns;
-          u.iofs = g.iofs;
-          u.a0 = g.a0;
-          u.a1 = g.a1;
-          u.first = g.first;
-          u.ti = tiles[q].ti;
-          u.tj = tiles[q].tj;
-          for (int sI = 0; sI < 2; ++sI) {
-            u.boff[sI] = g.off;
-            u.cld[sI] = 0;
-            if (g.child[sI] >= 0) {
-              const GNode& c = nodes[g.child[sI]];
-              u.cld[sI] = c.nf + 1;
-              u.boff[sI] = c.off + (long long)u.cld[sI] * c.ns + c.ns;
-            }
-          }
-          singles.push_back(u);
-        }
-        hp.single_tiles.cnt = (int)singles.size() - hp.single_tiles.ofs;
-      }
-      rt.cnt = (int)tiles.size() - rt.ofs;
-      hp.step.push_back(rt);
-      hp.step_bytes.push_back(bytes);
-      hp.step_p.push_back(p);
-      hp.step_pair.push_back(pair ? 1 : 0);
-      launches_++;
-      if (pair) ++p;
-    }
-    // backward
-    hp.split = hp.max_nf > split_nf;
-    hp.rect.ofs = (int)rects.size();
-    hp.rect_bytes = hp.tri_bytes = 0;
-    for (int t : mine) {
-      const GNode& g = nodes[t];
-      const double nb = g.nf - g.ns;
-      hp.rect_bytes += nb * g.ns * 8.0 + nb * 12.0;
-      hp.tri_bytes += 0.5 * g.ns * g.ns * 8.0 + g.ns * 28.0;
-      if (hp.split && nb > 0)
-        for (int ch = 0; ch * 64 < g.ns; ++ch) rects.push_back({t, ch});
-    }
-    hp.rect.cnt = (int)rects.size() - hp.rect.ofs;
-    launches_ += 1 + (hp.rect.cnt ? 1 : 0);
-    out.push_back(std::move(hp_new));
+  // schedule: the nodes of every height, own (split: this rank's subtree; else everything) and the replicated top
+  std::vector<std::vector<int>> own(nheights_), top(nheights_);
+  for (int t = 0; t < nnodes_; ++t) {
+    if (!part_.split() || part_.owner[t] == my_rank) own[height[t]].push_back(t);
+    else if (part_.owner[t] < 0) top[height[t]].push_back(t);
   }
-  };
-  make_plans(0, plan_);
-  if (part_.split()) make_plans(1, plan_top_);
+  Jobs jobs;
+  chain_.clear();
+  own_bwd_ = schedule(own, nodes, sjobs, sym, jobs);
+  top_fwd_ = (int)chain_.size();
+  if (part_.split()) schedule(top, nodes, sjobs, sym, jobs);
   if ((size_t)(max_nf_ + RT + PB) * 8 > 150 * 1024) throw ArgError("gpuchol: front exceeds the LDS budget of the sweeps");
   d_nodes_ = upload(nodes);
   d_perm_ = upload(sym.perm_);
@@ -1872,18 +1854,18 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
   d_pinv_ = upload(pinv);
   d_asm_src_ = upload(asrc);
   d_asm_pos_ = upload(apos);
-  d_lists_ = upload(lists);
+  d_lists_ = upload(jobs.lists);
   {      // node descriptors in launch order (front_leaf, backward) and per backward_rect job
-    std::vector<GNode> hn(lists.size()), rn(rects.size());
-    for (size_t k = 0; k < lists.size(); ++k) hn[k] = nodes[lists[k]];
-    for (size_t k = 0; k < rects.size(); ++k) rn[k] = nodes[rects[k].node];
+    std::vector<GNode> hn(jobs.lists.size()), rn(jobs.rects.size());
+    for (size_t k = 0; k < jobs.lists.size(); ++k) hn[k] = nodes[jobs.lists[k]];
+    for (size_t k = 0; k < jobs.rects.size(); ++k) rn[k] = nodes[jobs.rects[k].node];
     d_hnodes_ = upload(hn);
     d_rnodes_ = upload(rn);
   }
-  d_start_ = upload(starts);
-  d_tiles_ = upload(tiles);
-  d_singles_ = upload(singles);
-  d_rectjobs_ = upload(rects);
+  d_start_ = upload(jobs.starts);
+  d_tiles_ = upload(jobs.tiles);
+  d_singles_ = upload(jobs.singles);
+  d_rectjobs_ = upload(jobs.rects);
   if (part_.split()) {
     std::vector<RootXchg> roots;
     long long xoff = 0;
@@ -1943,25 +1925,22 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
   ck(hipMalloc((void**)&d_fail_, sizeof(int)), "hipMalloc flag");
   allocs_.push_back(d_fail_);
   ck(hipMemset(d_fail_, 0, sizeof(int)), "memset");
-  if (std::getenv("MGB_CHOL_PROF")) {
-    ck(hipMalloc((void**)&d_prof_, (size_t)kProfSlots * launches_ * sizeof(long long)), "hipMalloc prof");
+  if (knobs().prof) {
+    const size_t nl = chain_.size();
+    ck(hipMalloc((void**)&d_prof_, kProfSlots * nl * sizeof(long long)), "hipMalloc prof");
     allocs_.push_back(d_prof_);
+    reset_stamps();
 #ifdef MGB_PROF_PER_WG
     {
       long long* wg = nullptr;
-      ck(hipMalloc((void**)&wg, (size_t)launches_ * kProfMaxWg * 2 * sizeof(long long)), "hipMalloc wgprof");
+      ck(hipMalloc((void**)&wg, nl * kProfMaxWg * 2 * sizeof(long long)), "hipMalloc wgprof");
       allocs_.push_back(wg);
-      ck(hipMemset(wg, 0, (size_t)launches_ * kProfMaxWg * 2 * sizeof(long long)), "memset wgprof");
+      ck(hipMemset(wg, 0, nl * kProfMaxWg * 2 * sizeof(long long)), "memset wgprof");
       ck(hipMemcpyToSymbol(HIP_SYMBOL(g_wgprof), &wg, sizeof(wg)), "symbol wgprof");
       ck(hipMemcpyToSymbol(HIP_SYMBOL(g_prof_base), &d_prof_, sizeof(d_prof_)), "symbol prof base");
       d_wgprof_ = wg;
     }
 #endif
-    {
-      std::vector<long long> init((size_t)kProfSlots * launches_, 0LL);
-      for (int q = 0; q < launches_; ++q) init[(size_t)kProfSlots * q + 8] = -1LL;
-      ck(hipMemcpy(d_prof_, init.data(), init.size() * sizeof(long long), hipMemcpyHostToDevice), "init prof");
-    }
   }
   // per device (function attributes do not carry over to another GPU of the same process): set on every build
   ck(hipFuncSetAttribute((const void*)backward_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024), "attr");
@@ -1979,10 +1958,6 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
 void GpuChol::factor_solve(hipStream_t st, double* d_vals, const double* d_b, double* d_x, KernelTimer* tm, bool flag_armed,
                            bool values_summed, bool x_local) {
   if (n_ == 0) return;
-  static const bool use_graph = [] {
-    const char* e = std::getenv("MGB_CHOL_GRAPH");
-    return !(e && e[0] == '0');
-  }();
   // the pivot flag is re-armed here, outside the captured chain (a memset node replayed from the graph was seen
   // to leave garbage in the flag when another library used the device between replays)
   if (!flag_armed) ck(hipMemsetAsync(d_fail_, 0, sizeof(int), st), "memset flag");
@@ -1990,7 +1965,7 @@ void GpuChol::factor_solve(hipStream_t st, double* d_vals, const double* d_b, do
     factor_solve_split(st, d_vals, d_b, d_x, tm, values_summed, x_local && vals_local_ && !values_summed);
     return;
   }
-  if (!use_graph || tm || d_prof_) {
+  if (!knobs().graph || tm || d_prof_) {
     enqueue(st, d_vals, d_b, d_x, tm);
     return;
   }
@@ -2016,76 +1991,52 @@ void GpuChol::factor_solve(hipStream_t st, double* d_vals, const double* d_b, do
   ck(hipGraphLaunch(ge.exec, st), "hipGraphLaunch");
 }
 
-void GpuChol::enqueue_forward(hipStream_t st, const std::vector<HeightPlan>& plan, const double* d_vals, const double* d_b,
-                              KernelTimer* tm, int& nprof) {
-  for (const HeightPlan& hp : plan) {
-    if (hp.leaf) {
-      if (tm) tm->begin(st, KC_CHOL_SINGLE, hp.start_bytes);
-      const size_t lds = ((size_t)(hp.max_nf + 1) * hp.max_nf - (size_t)hp.max_nf * (hp.max_nf - 1) / 2) * sizeof(double);
-      hipLaunchKernelGGL(front_leaf_kernel, dim3(hp.nodes.cnt), dim3(TB), lds, st, d_hnodes_ + hp.nodes.ofs, d_lists_ + hp.nodes.ofs, d_asm_src_,
-                         d_asm_pos_, d_vals, d_perm_, d_b, d_fronts_, d_linv_, d_fail_,
-                         d_prof_ ? d_prof_ + kProfSlots * (nprof++) : nullptr);
-      if (tm) tm->end(st);
-      continue;
+// Issues chain_[begin, end) in order
+void GpuChol::run(hipStream_t st, int begin, int end, const double* d_vals, const double* d_b, double* d_x, KernelTimer* tm) {
+  for (int i = begin; i < end; ++i) {
+    const Launch& L = chain_[i];
+    long long* prof = d_prof_ ? d_prof_ + (size_t)kProfSlots * i : nullptr;
+    const dim3 grid(L.cnt), block(L.block);
+    const bool narrow = L.kind == Kind::SingleNarrow || L.kind == Kind::SingleDenseNarrow;
+    const bool dense = L.kind == Kind::SingleDense || L.kind == Kind::SingleDenseNarrow;
+    if (tm) tm->begin(st, L.timer, L.bytes);
+    switch (L.kind) {
+      case Kind::Leaf:
+        hipLaunchKernelGGL(front_leaf_kernel, grid, block, L.lds, st, d_hnodes_ + L.ofs, d_lists_ + L.ofs, d_asm_src_, d_asm_pos_,
+                           d_vals, d_perm_, d_b, d_fronts_, d_linv_, d_fail_, prof);
+        break;
+      case Kind::Single:
+      case Kind::SingleNarrow:
+      case Kind::SingleDense:
+      case Kind::SingleDenseNarrow:
+        hipLaunchKernelGGL(dense ? (narrow ? front_single_dense_kernel<true> : front_single_dense_kernel<false>)
+                                 : (narrow ? front_single_kernel<true> : front_single_kernel<false>),
+                           grid, block, L.lds, st, d_singles_ + L.ofs, d_pinv_, d_asm_src_, d_asm_pos_, d_vals, d_perm_, d_b, d_fronts_,
+                           d_fronts_, d_linv_, d_fail_, prof);
+        break;
+      case Kind::Start:
+        hipLaunchKernelGGL(front_start_kernel, grid, block, L.lds, st, d_nodes_, d_start_ + L.ofs, d_pinv_, d_asm_src_, d_asm_pos_,
+                           d_vals, d_perm_, d_b, d_fronts_, d_fronts_, d_linv_, d_fail_, prof, knobs().start_pivot ? 1 : 0);
+        break;
+      case Kind::Step:
+      case Kind::Step2:
+      case Kind::Panel2:
+      case Kind::Update2:
+        hipLaunchKernelGGL(L.kind == Kind::Step ? front_step_kernel : L.kind == Kind::Step2 ? front_step2_kernel
+                           : L.kind == Kind::Panel2 ? front_panel2_kernel : front_update2_kernel,
+                           grid, block, L.lds, st, d_tiles_ + L.ofs, L.p, L.npiv, d_fronts_, d_linv_, d_linv_, d_fail_, prof);
+        break;
+      case Kind::BwdRect:      // no phase stamps
+        hipLaunchKernelGGL(backward_rect_kernel, grid, block, L.lds, st, d_rnodes_ + L.ofs, d_rectjobs_ + L.ofs, d_bdry_, d_fronts_,
+                           d_y_, d_rect_);
+        break;
+      case Kind::Bwd256:
+      case Kind::Bwd1024:
+        hipLaunchKernelGGL(L.kind == Kind::Bwd1024 ? backward_kernel<1024> : backward_kernel<256>, grid, block, L.lds, st,
+                           d_hnodes_ + L.ofs, d_lists_ + L.ofs, d_bdry_, d_fronts_, d_linv_, d_perm_, d_rect_, L.rect ? 1 : 0, d_y_,
+                           d_x, prof);
+        break;
     }
-    if (hp.single) {
-      if (tm) tm->begin(st, KC_CHOL_SINGLE, hp.start_bytes + hp.step_bytes[0]);
-      static const int dense_tiles = [] {      // MGB_CHOL_DENSE_TILES: launches above this many tiles use the three-per-CU variant
-        const char* e = std::getenv("MGB_CHOL_DENSE_TILES");
-        return e ? std::atoi(e) : 512;      // what two tiles per CU hold at once
-      }();
-      const bool dense = hp.single_tiles.cnt > dense_tiles;
-      hipLaunchKernelGGL(dense ? (hp.narrow ? front_single_dense_kernel<true> : front_single_dense_kernel<false>)
-                               : (hp.narrow ? front_single_kernel<true> : front_single_kernel<false>),
-                         dim3(hp.single_tiles.cnt), dim3(TB), 0, st, d_singles_ + hp.single_tiles.ofs, d_pinv_,
-                         d_asm_src_, d_asm_pos_, d_vals, d_perm_, d_b, d_fronts_, d_fronts_, d_linv_, d_fail_,
-                         d_prof_ ? d_prof_ + kProfSlots * (nprof++) : nullptr);
-      if (tm) tm->end(st);
-      continue;
-    }
-    if (tm) tm->begin(st, KC_CHOL_START, hp.start_bytes);
-    hipLaunchKernelGGL(front_start_kernel, dim3(hp.start.cnt), dim3(TB), 0, st, d_nodes_, d_start_ + hp.start.ofs, d_pinv_,
-                       d_asm_src_, d_asm_pos_, d_vals, d_perm_, d_b, d_fronts_, d_fronts_, d_linv_, d_fail_,
-                       d_prof_ ? d_prof_ + kProfSlots * (nprof++) : nullptr, start_pivot_ ? 1 : 0);
-    if (tm) tm->end(st);
-    for (size_t q = 0; q < hp.step.size(); ++q) {
-      if (tm) tm->begin(st, KC_CHOL_STEP, hp.step_bytes[q]);
-      if (hp.step_pair[q] == 2)
-        hipLaunchKernelGGL(front_panel2_kernel, dim3(hp.step[q].cnt), dim3(TB), kPanel2Lds, st, d_tiles_ + hp.step[q].ofs, hp.step_p[q],
-                           hp.step_npiv[q], d_fronts_, d_linv_, d_linv_, d_fail_, d_prof_ ? d_prof_ + kProfSlots * (nprof++) : nullptr);
-      else if (hp.step_pair[q] == 3)
-        hipLaunchKernelGGL(front_update2_kernel, dim3(hp.step[q].cnt), dim3(TB), kUpdate2Lds, st, d_tiles_ + hp.step[q].ofs, hp.step_p[q],
-                           0, d_fronts_, d_linv_, d_linv_, d_fail_, d_prof_ ? d_prof_ + kProfSlots * (nprof++) : nullptr);
-      else if (hp.step_pair[q])
-        hipLaunchKernelGGL(front_step2_kernel, dim3(hp.step[q].cnt), dim3(TB), kStep2Lds, st, d_tiles_ + hp.step[q].ofs, hp.step_p[q],
-                           hp.step_npiv[q], d_fronts_, d_linv_, d_linv_, d_fail_, d_prof_ ? d_prof_ + kProfSlots * (nprof++) : nullptr);
-      else
-        hipLaunchKernelGGL(front_step_kernel, dim3(hp.step[q].cnt), dim3(TB), 0, st, d_tiles_ + hp.step[q].ofs, hp.step_p[q],
-                           hp.step_npiv[q], d_fronts_, d_linv_, d_linv_, d_fail_, d_prof_ ? d_prof_ + kProfSlots * (nprof++) : nullptr);
-      if (tm) tm->end(st);
-    }
-  }
-}
-
-void GpuChol::enqueue_backward(hipStream_t st, const std::vector<HeightPlan>& plan, double* d_x, KernelTimer* tm, int* nprof) {
-  for (int h = (int)plan.size() - 1; h >= 0; --h) {
-    const HeightPlan& hp = plan[h];
-    const int use_rect = hp.rect.cnt ? 1 : 0;
-    if (use_rect) {
-      if (tm) tm->begin(st, KC_CHOL_BWD_RECT, hp.rect_bytes);
-      hipLaunchKernelGGL(backward_rect_kernel, dim3(hp.rect.cnt), dim3(RT), (size_t)(hp.max_nf + RT) * sizeof(double), st,
-                         d_rnodes_ + hp.rect.ofs, d_rectjobs_ + hp.rect.ofs, d_bdry_, d_fronts_, d_y_, d_rect_);
-      if (tm) tm->end(st);
-    }
-    if (tm) tm->begin(st, KC_CHOL_BWD, hp.tri_bytes + (use_rect ? 0.0 : hp.rect_bytes));
-    if (hp.max_nf > 384)
-      hipLaunchKernelGGL(backward_kernel<1024>, dim3(hp.nodes.cnt), dim3(1024), (size_t)(hp.max_nf + 1024 + PB) * sizeof(double),
-                         st, d_hnodes_ + hp.nodes.ofs, d_lists_ + hp.nodes.ofs, d_bdry_, d_fronts_, d_linv_, d_perm_, d_rect_, use_rect, d_y_,
-                         d_x, (d_prof_ && nprof) ? d_prof_ + kProfSlots * ((*nprof)++) : nullptr);
-    else
-      hipLaunchKernelGGL(backward_kernel<256>, dim3(hp.nodes.cnt), dim3(256), (size_t)(hp.max_nf + 256 + PB) * sizeof(double),
-                         st, d_hnodes_ + hp.nodes.ofs, d_lists_ + hp.nodes.ofs, d_bdry_, d_fronts_, d_linv_, d_perm_, d_rect_, use_rect, d_y_,
-                         d_x, (d_prof_ && nprof) ? d_prof_ + kProfSlots * ((*nprof)++) : nullptr);
     if (tm) tm->end(st);
   }
 }
@@ -2093,18 +2044,15 @@ void GpuChol::enqueue_backward(hipStream_t st, const std::vector<HeightPlan>& pl
 void GpuChol::enqueue_chain(hipStream_t st, const double* d_vals, const double* d_b, double* d_x) {
   if (part_.split()) throw InternalError("gpuchol: a split factorisation cannot be captured");
   if (n_ == 0) return;
-  int nprof = 0;
-  enqueue_forward(st, plan_, d_vals, d_b, nullptr, nprof);
-  enqueue_backward(st, plan_, d_x, nullptr);
+  run(st, 0, top_fwd_, d_vals, d_b, d_x, nullptr);
   ck(hipGetLastError(), "chain launches");
 }
 
 void GpuChol::factor_solve_split(hipStream_t st, double* d_vals, const double* d_b, double* d_x, KernelTimer* tm, bool values_summed,
                                  bool x_local) {
-  int nprof = 0;
   const bool ride = vals_local_ && !values_summed;
   const int ntop = ride ? ntop_vals_ : 0;
-  enqueue_forward(st, plan_, d_vals, d_b, tm, nprof);                    // this rank's subtree
+  run(st, 0, own_bwd_, d_vals, d_b, d_x, tm);                            // this rank's subtree
   const dim3 xg(nroots_, std::max(1, std::min(64, max_root_nb_)));
   hipLaunchKernelGGL(schur_pack_kernel, xg, dim3(256), 0, st, d_roots_, d_fronts_, d_xchg_);
   const int vgrid = std::max(1, std::min(1024, (ntop_vals_ + 255) / 256));
@@ -2115,9 +2063,8 @@ void GpuChol::factor_solve_split(hipStream_t st, double* d_vals, const double* d
   hipLaunchKernelGGL(schur_unpack_kernel, xg, dim3(256), 0, st, d_roots_, d_xchg_, d_fronts_);
   if (ride)
     hipLaunchKernelGGL(vals_unpack_kernel, dim3(vgrid), dim3(256), 0, st, ntop_vals_, d_top_idx_, d_xchg_ + xchg_doubles_, d_vals);
-  enqueue_forward(st, plan_top_, d_vals, d_b, tm, nprof);                // replicated top: same arithmetic on every rank
-  enqueue_backward(st, plan_top_, d_x, tm);
-  enqueue_backward(st, plan_, d_x, tm);
+  run(st, top_fwd_, (int)chain_.size(), d_vals, d_b, d_x, tm);          // replicated top: same arithmetic on every rank
+  run(st, own_bwd_, top_fwd_, d_vals, d_b, d_x, tm);                     // back through this rank's subtree
   const int grid = std::min(2048, (n_ + 256) / 256);
   if (x_local) {      // every rank holds what its rows need: its subtree's unknowns and the replicated top
     hipLaunchKernelGGL(x_local_kernel, dim3(grid), dim3(256), 0, st, n_, d_kind_orig_, d_x);
@@ -2132,68 +2079,76 @@ void GpuChol::factor_solve_split(hipStream_t st, double* d_vals, const double* d
 }
 
 void GpuChol::enqueue(hipStream_t st, const double* d_vals, const double* d_b, double* d_x, KernelTimer* tm) {
-  int nprof = 0;
-  enqueue_forward(st, plan_, d_vals, d_b, tm, nprof);
-  enqueue_backward(st, plan_, d_x, tm, &nprof);
+  run(st, 0, top_fwd_, d_vals, d_b, d_x, tm);
   ck(hipGetLastError(), "factor_solve launches");
-  if (d_prof_) {      // debugging aid: phase stamps of workgroup 0 of every factorisation launch, in units of 10 ns
-    ck(hipStreamSynchronize(st), "prof sync");
-    std::vector<long long> hprof((size_t)kProfSlots * nprof);
-    ck(hipMemcpy(hprof.data(), d_prof_, hprof.size() * sizeof(long long), hipMemcpyDeviceToHost), "prof D2H");
-    std::fprintf(stderr, "[mgb chol prof] launch: load trsm update store sync Dwrite factor tail (us)\n");
-    for (int q = 0; q < nprof; ++q) {
-      const long long* v = hprof.data() + kProfSlots * q;
-      std::fprintf(stderr, "[mgb chol prof] %3d:", q);
-      for (int k = 1; k < 8; ++k) std::fprintf(stderr, " %6.2f", (v[k] && v[k - 1]) ? (v[k] - v[k - 1]) * 0.01 : 0.0);
-      // all workgroups: first start -> last end, and the time since the previous launch's last end (launch boundary)
-      const long long* pv = q ? hprof.data() + kProfSlots * (q - 1) : nullptr;
-      const long long end_q = (long long)((unsigned long long)v[9] >> 16), end_p = pv ? (long long)((unsigned long long)pv[9] >> 16) : 0;
-      std::fprintf(stderr, "  | all wgs %6.2f (last: wg %5d)  since prev end %6.2f\n", (end_q - v[8]) * 0.01,
-                   (int)((unsigned long long)v[9] & 65535ull), pv ? (v[8] - end_p) * 0.01 : 0.0);
-    }
-#ifdef MGB_PROF_PER_WG
-    if (d_wgprof_) {
-      std::vector<long long> wg((size_t)nprof * kProfMaxWg * 2);
-      ck(hipMemcpy(wg.data(), d_wgprof_, wg.size() * sizeof(long long), hipMemcpyDeviceToHost), "wgprof D2H");
-      std::fprintf(stderr, "[mgb chol wgs] launch: workgroups | start of the last one after the first | duration min / median / max | span | slowest: wg(start, duration) (us)\n");
-      for (int q = 0; q < nprof; ++q) {
-        std::vector<std::array<double, 3>> v;      // start, duration, id
-        long long t0 = -1;
-        for (int b = 0; b < kProfMaxWg; ++b) {
-          const long long st0 = wg[((size_t)q * kProfMaxWg + b) * 2], en = wg[((size_t)q * kProfMaxWg + b) * 2 + 1];
-          if (st0 == 0 || en == 0) continue;
-          if (t0 < 0 || st0 < t0) t0 = st0;
-        }
-        double last_start = 0, span = 0;
-        for (int b = 0; b < kProfMaxWg; ++b) {
-          const long long st0 = wg[((size_t)q * kProfMaxWg + b) * 2], en = wg[((size_t)q * kProfMaxWg + b) * 2 + 1];
-          if (st0 == 0 || en == 0) continue;
-          v.push_back({(st0 - t0) * 0.01, (en - st0) * 0.01, (double)b});
-          last_start = std::max(last_start, (st0 - t0) * 0.01);
-          span = std::max(span, (en - t0) * 0.01);
-        }
-        if (v.empty()) continue;
-        std::sort(v.begin(), v.end(), [](const auto& a, const auto& b2) { return a[1] < b2[1]; });
-        std::fprintf(stderr, "[mgb chol wgs] %3d: %5zu | %6.2f | %6.2f %6.2f %6.2f | %6.2f |", q, v.size(), last_start, v.front()[1],
-                     v[v.size() / 2][1], v.back()[1], span);
-        for (size_t k = v.size() > 4 ? v.size() - 4 : 0; k < v.size(); ++k)
-          std::fprintf(stderr, " %d(%.2f, %.2f)", (int)v[k][2], v[k][0], v[k][1]);
-        // the last finishers
-        std::sort(v.begin(), v.end(), [](const auto& a, const auto& b2) { return a[0] + a[1] < b2[0] + b2[1]; });
-        std::fprintf(stderr, " | last to end:");
-        for (size_t k = v.size() > 3 ? v.size() - 3 : 0; k < v.size(); ++k)
-          std::fprintf(stderr, " %d(%.2f, %.2f)", (int)v[k][2], v[k][0], v[k][1]);
-        std::fprintf(stderr, "\n");
-      }
-      ck(hipMemset(d_wgprof_, 0, wg.size() * sizeof(long long)), "wgprof reset");
-    }
-#endif
-    for (int q = 0; q < nprof; ++q) {
-      std::fill(hprof.begin() + (size_t)kProfSlots * q, hprof.begin() + (size_t)kProfSlots * (q + 1), 0LL);
-      hprof[(size_t)kProfSlots * q + 8] = -1LL;      // all ones: atomicMin target (unsigned)
-    }
-    ck(hipMemcpy(d_prof_, hprof.data(), hprof.size() * sizeof(long long), hipMemcpyHostToDevice), "prof reset");
+  if (d_prof_) print_stamps(st);
+}
+
+void GpuChol::reset_stamps() {
+  std::vector<long long> init((size_t)kProfSlots * chain_.size(), 0LL);
+  for (size_t q = 0; q < chain_.size(); ++q) init[kProfSlots * q + 8] = -1LL;      // all ones: atomicMin target (unsigned)
+  ck(hipMemcpy(d_prof_, init.data(), init.size() * sizeof(long long), hipMemcpyHostToDevice), "prof reset");
+}
+
+// debugging aid: the phase stamps of workgroup 0 of every stamped launch of the (unsplit) chain just issued, in units of 10 ns
+void GpuChol::print_stamps(hipStream_t st) {
+  ck(hipStreamSynchronize(st), "prof sync");
+  std::vector<long long> hprof((size_t)kProfSlots * chain_.size());
+  ck(hipMemcpy(hprof.data(), d_prof_, hprof.size() * sizeof(long long), hipMemcpyDeviceToHost), "prof D2H");
+  std::vector<int> slot;      // the stamped launches, in launch order
+  for (int i = 0; i < top_fwd_; ++i)
+    if (chain_[i].kind != Kind::BwdRect) slot.push_back(i);
+  const int nprof = (int)slot.size();
+  std::fprintf(stderr, "[mgb chol prof] launch: load trsm update store sync Dwrite factor tail (us)\n");
+  for (int q = 0; q < nprof; ++q) {
+    const long long* v = hprof.data() + kProfSlots * slot[q];
+    std::fprintf(stderr, "[mgb chol prof] %3d:", q);
+    for (int k = 1; k < 8; ++k) std::fprintf(stderr, " %6.2f", (v[k] && v[k - 1]) ? (v[k] - v[k - 1]) * 0.01 : 0.0);
+    // all workgroups: first start -> last end, and the time since the previous launch's last end (launch boundary)
+    const long long* pv = q ? hprof.data() + kProfSlots * slot[q - 1] : nullptr;
+    const long long end_q = (long long)((unsigned long long)v[9] >> 16), end_p = pv ? (long long)((unsigned long long)pv[9] >> 16) : 0;
+    std::fprintf(stderr, "  | all wgs %6.2f (last: wg %5d)  since prev end %6.2f\n", (end_q - v[8]) * 0.01,
+                 (int)((unsigned long long)v[9] & 65535ull), pv ? (v[8] - end_p) * 0.01 : 0.0);
   }
+#ifdef MGB_PROF_PER_WG
+  if (d_wgprof_) {
+    std::vector<long long> wg(chain_.size() * kProfMaxWg * 2);
+    ck(hipMemcpy(wg.data(), d_wgprof_, wg.size() * sizeof(long long), hipMemcpyDeviceToHost), "wgprof D2H");
+    std::fprintf(stderr, "[mgb chol wgs] launch: workgroups | start of the last one after the first | duration min / median / max | span | slowest: wg(start, duration) (us)\n");
+    for (int q = 0; q < nprof; ++q) {
+      const long long* w = wg.data() + (size_t)slot[q] * kProfMaxWg * 2;
+      std::vector<std::array<double, 3>> v;      // start, duration, id
+      long long t0 = -1;
+      for (int b = 0; b < kProfMaxWg; ++b) {
+        const long long st0 = w[b * 2], en = w[b * 2 + 1];
+        if (st0 == 0 || en == 0) continue;
+        if (t0 < 0 || st0 < t0) t0 = st0;
+      }
+      double last_start = 0, span = 0;
+      for (int b = 0; b < kProfMaxWg; ++b) {
+        const long long st0 = w[b * 2], en = w[b * 2 + 1];
+        if (st0 == 0 || en == 0) continue;
+        v.push_back({(st0 - t0) * 0.01, (en - st0) * 0.01, (double)b});
+        last_start = std::max(last_start, (st0 - t0) * 0.01);
+        span = std::max(span, (en - t0) * 0.01);
+      }
+      if (v.empty()) continue;
+      std::sort(v.begin(), v.end(), [](const auto& a, const auto& b2) { return a[1] < b2[1]; });
+      std::fprintf(stderr, "[mgb chol wgs] %3d: %5zu | %6.2f | %6.2f %6.2f %6.2f | %6.2f |", q, v.size(), last_start, v.front()[1],
+                   v[v.size() / 2][1], v.back()[1], span);
+      for (size_t k = v.size() > 4 ? v.size() - 4 : 0; k < v.size(); ++k)
+        std::fprintf(stderr, " %d(%.2f, %.2f)", (int)v[k][2], v[k][0], v[k][1]);
+      // the last finishers
+      std::sort(v.begin(), v.end(), [](const auto& a, const auto& b2) { return a[0] + a[1] < b2[0] + b2[1]; });
+      std::fprintf(stderr, " | last to end:");
+      for (size_t k = v.size() > 3 ? v.size() - 3 : 0; k < v.size(); ++k)
+        std::fprintf(stderr, " %d(%.2f, %.2f)", (int)v[k][2], v[k][0], v[k][1]);
+      std::fprintf(stderr, "\n");
+    }
+    ck(hipMemset(d_wgprof_, 0, wg.size() * sizeof(long long)), "wgprof reset");
+  }
+#endif
+  reset_stamps();
 }
 
 }  // namespace mgb

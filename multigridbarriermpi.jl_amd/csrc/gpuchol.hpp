@@ -80,12 +80,27 @@ struct RectJob {      // one workgroup of backward_rect: 64 own columns of one f
   int node, chunk;
 };
 
+// The chain's environment knobs (all optional), read once per process
+struct CholKnobs {
+  bool graph;          // MGB_CHOL_GRAPH=0: plain launches instead of hipGraph replay
+  bool prof;           // MGB_CHOL_PROF set: phase stamps of every launch, printed after each plain-launch unsplit chain
+  bool leaf;           // MGB_CHOL_LEAF=0: no front_leaf heights
+  bool single;         // MGB_CHOL_SINGLE=0: no front_single heights
+  bool step2;          // MGB_CHOL_STEP2=0: one panel per launch everywhere (the scheme before front_step2)
+  bool wide;           // MGB_CHOL_WIDE=0: one panel per launch beyond the fused kernel's tile count (no panel + update pairs)
+  bool start_pivot;    // MGB_CHOL_START_PIVOT=0: the first pivot block is factored by the assembling workgroup
+  int step2_tiles;     // MGB_CHOL_STEP2_TILES (224): largest launch, in tiles, that runs two panels fused
+  int dense_tiles;     // MGB_CHOL_DENSE_TILES (512): single-panel launches above this many tiles run three tiles per CU
+  int bwd_split_nf;    // MGB_BWD_SPLIT_NF (192): front size above which the backward sweep of a height has a backward_rect launch
+};
+
 class GpuChol {
  public:
   GpuChol() = default;
   GpuChol(const GpuChol&) = delete;
   GpuChol& operator=(const GpuChol&) = delete;
   ~GpuChol();
+  static const CholKnobs& knobs();
   // ctx (nullable): on a sharded context (ctx->world a power of two the tree can be split into) the factorisation is
   // split by subtrees -- this rank factors its subtree, the subtree roots' Schur complements (with their right-hand-side
   // rows) are summed over the ranks (one rank contributes each), every rank factors the replicated top and sweeps back
@@ -119,16 +134,18 @@ class GpuChol {
   int size() const { return n_; }
   double front_bytes() const { return (double)total_front_ * 8; }
   double factor_flops() const { return flops_; }
-  int launches_per_solve() const { return launches_; }
+  int launches_per_solve() const { return (int)chain_.size(); }
 
  private:
   template <class T>
   T* upload(const std::vector<T>& v);
-  void enqueue(hipStream_t st, const double* d_vals, const double* d_b, double* d_x, KernelTimer* timer);
-  struct HeightPlan;
-  void enqueue_forward(hipStream_t st, const std::vector<HeightPlan>& plan, const double* d_vals, const double* d_b, KernelTimer* tm,
-                       int& nprof);
-  void enqueue_backward(hipStream_t st, const std::vector<HeightPlan>& plan, double* d_x, KernelTimer* tm, int* nprof = nullptr);
+  struct Jobs;
+  int schedule(const std::vector<std::vector<int>>& heights, const std::vector<GNode>& nodes,
+               const std::vector<std::vector<StartJob>>& sjobs, const MfChol& sym, Jobs& jobs);
+  void run(hipStream_t st, int begin, int end, const double* d_vals, const double* d_b, double* d_x, KernelTimer* tm);
+  void enqueue(hipStream_t st, const double* d_vals, const double* d_b, double* d_x, KernelTimer* tm);
+  void print_stamps(hipStream_t st);
+  void reset_stamps();
   void factor_solve_split(hipStream_t st, double* d_vals, const double* d_b, double* d_x, KernelTimer* tm, bool values_summed,
                           bool x_local);
   int* d_kind_orig_ = nullptr;
@@ -141,7 +158,6 @@ class GpuChol {
   int nroots_ = 0, max_root_nb_ = 0;
   double* d_xchg_ = nullptr;      // Schur exchange buffer (+ ntop_vals_ matrix entries of the top nodes behind it)
   bool vals_local_ = false;
-  bool start_pivot_ = true;       // front_start launches carry a dedicated pivot job per front
   int ntop_vals_ = 0;
   int* d_top_idx_ = nullptr;      // indices into d_vals of the entries assembled into the top nodes
   double* d_xsol_ = nullptr;      // n + 1: masked solution + pivot flag
@@ -153,7 +169,7 @@ class GpuChol {
     hipGraphExec_t exec;
   };
   std::vector<GraphEntry> graphs_;
-  int n_ = 0, nnodes_ = 0, nheights_ = 0, launches_ = 0, max_nf_ = 0;
+  int n_ = 0, nnodes_ = 0, nheights_ = 0, max_nf_ = 0;
   long long total_front_ = 0;
   double flops_ = 0;
   // device
@@ -162,7 +178,7 @@ class GpuChol {
   double* d_linv_ = nullptr;      // 32x32 diagonal (pivot) blocks of L
   double* d_y_ = nullptr;         // solution in the new ordering
   int* d_fail_ = nullptr;
-  long long* d_prof_ = nullptr;   // MGB_CHOL_PROF=1: phase stamps of workgroup 0 of every factorisation launch
+  long long* d_prof_ = nullptr;   // MGB_CHOL_PROF=1: phase stamps of workgroup 0 of every launch but backward_rect
   [[maybe_unused]] long long* d_wgprof_ = nullptr; // (-DMGB_PROF_PER_WG builds) start / end of every workgroup of every stamped launch
   GNode* d_nodes_ = nullptr;
   int* d_perm_ = nullptr;
@@ -177,27 +193,25 @@ class GpuChol {
   StepTile* d_tiles_ = nullptr;
   SingleTile* d_singles_ = nullptr;
   RectJob* d_rectjobs_ = nullptr;
-  // host schedule
-  struct Range {
-    int ofs, cnt;
+  // host schedule: every dispatch of the chain, decided once by build()
+  enum class Kind : unsigned char {
+    Leaf, Single, SingleNarrow, SingleDense, SingleDenseNarrow, Start, Step, Step2, Panel2, Update2, BwdRect, Bwd256, Bwd1024
   };
-  struct HeightPlan {
-    Range nodes, start, rect;
-    std::vector<Range> step;
-    Range single_tiles{0, 0};
-    std::vector<int> step_npiv;   // leading pivot workgroups of every step launch
-    std::vector<int> step_p;      // first panel of the launch
-    std::vector<char> step_pair;  // 0: one panel (front_step), 1: two panels fused (front_step2), 2 / 3: two panels as a panel launch and an update launch
-    std::vector<double> step_bytes;
-    double start_bytes, rect_bytes, tri_bytes;
-    int max_nf;
-    bool split;      // backward: rectangular part in its own multi-workgroup launch
-    bool single;     // every front has one panel: front_single replaces front_start + front_step
-    bool narrow = false; // single && at most 8 pivots per front
-    bool leaf = false;   // small childless fronts: front_leaf does the whole front in one workgroup
+  struct Launch {
+    Kind kind;
+    int ofs, cnt;       // job range, one workgroup per job, in lists (Leaf, Bwd*), singles (Single*), starts (Start),
+                        // tiles (Step, Step2, Panel2, Update2) or rects (BwdRect)
+    int block;          // threads per workgroup
+    size_t lds;         // dynamic LDS bytes
+    int p, npiv;        // first panel, leading pivot workgroups (step kinds)
+    bool rect;          // Bwd*: the rectangular part ran in the BwdRect launch before
+    int timer;          // KernelTimer class
+    double bytes;       // algorithmic bytes
   };
-  std::vector<HeightPlan> plan_;       // own nodes (everything when the factorisation is not split)
-  std::vector<HeightPlan> plan_top_;   // split only: the replicated separators above the subtrees
+  // own forward | own backward | (split) top forward | top backward, in launch order; a launch's position is its profile slot.
+  // Own: this rank's subtree when split, else everything; top: the replicated separators above the subtrees.
+  std::vector<Launch> chain_;
+  int own_bwd_ = 0, top_fwd_ = 0;      // where own backward and the top begin
   std::vector<void*> allocs_;
 };
 
