@@ -341,6 +341,14 @@ int mgb_hostchol_factor_solve_dist_local(mgb_hostchol c, int rank, int world, mg
 /* host-only: the nested-dissection elimination tree of this level's pattern in postorder (children first):
  * own size, front size and parent (-1 = root) of the first min(cap, *nnodes) nodes */
 int mgb_plan_chol_tree(mgb_plan p, int dim, int cap, int* nnodes, int* ns, int* nf, int* parent);
+/* host-only: the tables of the fused backward sweep (csrc/bwd_fused.hpp) for this level's tree: cut = subtree height,
+ * top_nf = largest front of a height the fused launch takes (<= 0: no limit), threads = its workgroup size.
+ * info[12] = h_top, h_cut, workgroups, ints per workgroup record, levels per record, LDS solution entries, LDS reduction
+ * doubles, LDS slot ints, LDS bytes, boundary entries, nodes, heights (workgroups = 0: no fused launch).  wg: the workgroup
+ * records; bdry / slots: the concatenated boundary lists and the LDS slot of each entry; bofs / first: per node the offset
+ * of its boundary list and its first own unknown.  Each array is filled up to its capacity. */
+int mgb_plan_chol_bwd_fused(mgb_plan p, int dim, int cut, int top_nf, int threads, int* info, int cap_wg, int* wg, int cap_bdry,
+                            int* bdry, int* slots, int cap_nodes, int* bofs, int* first);
 int mgb_chol_selftest(int nx, int ny, double* max_residual, double* flops, double* seconds);
 
 #ifdef __cplusplus

@@ -146,6 +146,8 @@ PROTOTYPES = {
     "mgb_hostchol_rank_aligned": [H, C.c_int, c_int_p, c_int_p],
     "mgb_hostchol_factor_solve_dist_local": [H, C.c_int, C.c_int, ALLREDUCE_FN, C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_plan_chol_tree": [H, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p],
+    "mgb_plan_chol_bwd_fused": [H, C.c_int, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int,
+                                c_int_p, c_int_p],
     "mgb_chol_selftest": [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p],
 }
 _SPECIAL = {"mgb_last_error": ([], C.c_char_p), "mgb_version": ([], C.c_int), "mgb_device_count": ([], C.c_int)}

@@ -1311,6 +1311,34 @@ int mgb_plan_chol_tree(mgb_plan p, int dim, int cap, int* nnodes, int* ns, int* 
   });
 }
 
+int mgb_plan_chol_bwd_fused(mgb_plan p, int dim, int cut, int top_nf, int threads, int* info, int cap_wg, int* wg, int cap_bdry,
+                            int* bdry, int* slots, int cap_nodes, int* bofs, int* first) {
+  return guard([&] {
+    need(p && info, "chol_bwd_fused: bad arguments");
+    MfChol ch;
+    ch.analyze(p->plan.Apat, p->plan.coords.data(), dim);
+    std::vector<int> ns, fi, par, bd;
+    std::vector<const std::vector<int>*> lists;
+    ch.bwd_tables(ns, fi, par, lists);
+    FusedKnobs kn;
+    kn.cut = cut;
+    kn.top_nf = top_nf;
+    kn.threads = threads;
+    kn.split_nf = GpuChol::knobs().bwd_split_nf;
+    const FusedPlan P = plan_bwd_fused(ns, fi, par, lists, kn);
+    for (const std::vector<int>* l : lists) bd.insert(bd.end(), l->begin(), l->end());
+    const int v[12] = {P.h_top, P.h_cut, P.nwg, P.wstride, P.max_levels, P.xs_cap, P.red_cap, P.sl_cap, (int)P.lds_bytes,
+                       (int)bd.size(), (int)ns.size(), P.nheights};
+    std::copy(v, v + 12, info);
+    if (wg) std::copy(P.wg.begin(), P.wg.begin() + std::min<size_t>(cap_wg, P.wg.size()), wg);
+    const size_t mb = std::min<size_t>(cap_bdry, bd.size()), mn = std::min<size_t>(cap_nodes, ns.size());
+    if (bdry) std::copy(bd.begin(), bd.begin() + mb, bdry);
+    if (slots) std::copy(P.slots.begin(), P.slots.begin() + mb, slots);
+    if (bofs) std::copy(P.bofs.begin(), P.bofs.begin() + mn, bofs);
+    if (first) std::copy(fi.begin(), fi.begin() + mn, first);
+  });
+}
+
 int mgb_chol_selftest(int nx, int ny, double* max_residual, double* flops, double* seconds) {
   return guard([&] {
     need(nx > 0 && ny > 0, "selftest: bad size");

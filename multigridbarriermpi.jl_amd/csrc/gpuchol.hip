@@ -1408,6 +1408,239 @@ __global__ __launch_bounds__(NT) void backward_kernel(const GNode* __restrict__ 
   STAMP(7);
 }
 
+// ---- fused backward sweep: every height up to h_top in ONE launch without any cross-workgroup synchronisation (tables and
+// the scheme: bwd_fused.hpp).  The order of additions of every front is the one backward_rect_kernel / backward_kernel use
+// at that front's height (FJ_NSL, FJ_NT), whatever this kernel's own thread count, so the result is the same bit for bit.
+
+// lc: column c = lane & 31 of the pivot block, lc[m] = L[m][c] (1/L[c][c] on the diagonal, 0 above)
+__device__ __forceinline__ void load_pivot_block(double (&lc)[PB], const double* __restrict__ lpp, int lane) {
+#pragma unroll
+  for (int m = 0; m < PB; ++m) lc[m] = lpp[PB * m + (lane & 31)];
+}
+
+// f[r] = L[k0 + r][jc] of the panel at k0 (kw rows) for this thread's column jc of the earlier columns; threads beyond
+// them and rows beyond the panel load a copy of a valid entry (clamped, not predicated: 32 loads behind no branch)
+__device__ __forceinline__ void load_panel_rows(double (&f)[PB], const double* __restrict__ F, int ld, int k0, int kw, int jc) {
+  const double* Fj = F + (long long)ld * k0 + max(min(jc, k0 - 1), 0);
+#pragma unroll
+  for (int r = 0; r < PB; ++r) f[r] = Fj[(long long)ld * min(r, kw - 1)];
+}
+
+// x_p = L_pp^-T u_p of one 32-wide panel by one wave (the substitution of backward_kernel): up = the panel's entries in LDS
+__device__ __forceinline__ void panel_substitute(const double (&lc)[PB], double* up, int kw, int lane) {
+  const int c = lane & 31;
+  double uc = (c < kw) ? up[c] : 0.0;
+#pragma unroll
+  for (int m = PB - 1; m >= 0; --m) {
+    const double xm = readlane_f64(uc * lc[m], m);            // lane m: u_m / L[m][m]
+    uc = (c == m) ? xm : fma(-lc[m], xm, uc);                 // lanes c > m: lc[m] == 0
+  }
+  if (lane < kw) up[c] = uc;
+}
+
+// sum_i L[k0 + i][j] x_(k0 + i) over the kw rows of a solved panel, as backward_kernel adds it up with NSL row slices:
+// slice q takes the rows i = q (mod NSL) ascending by fma, then s_0 + s_1 + ... in order.  f: the 32 entries of L.
+template <int NSL>
+__device__ __forceinline__ double panel_dot(const double (&f)[PB], const double* up, int kw) {
+  double s[NSL];
+#pragma unroll
+  for (int q = 0; q < NSL; ++q) s[q] = 0.0;
+#pragma unroll
+  for (int r = 0; r < PB; ++r) {
+    const double v = fma(f[r], up[min(r, kw - 1)], s[r % NSL]);      // (clamped, not predicated: no branch around a load)
+    s[r % NSL] = (r < kw) ? v : s[r % NSL];
+  }
+  double t = s[0];
+#pragma unroll
+  for (int q = 1; q < NSL; ++q) t += s[q];
+  return t;
+}
+
+// the same for any slice count (the 1 024-thread heights, which the default threshold keeps out of the fused launch)
+__device__ inline double panel_dot_any(const double* __restrict__ Fj, long long ld, const double* up, int kw, int nsl) {
+  double t = 0.0;
+  for (int q = 0; q < nsl; ++q) {
+    double s = 0.0;
+    for (int r = q; r < kw; r += nsl) s = fma(Fj[ld * r], up[r], s);
+    t = q ? t + s : s;
+  }
+  return t;
+}
+
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// One workgroup per subtree of the cut.  LDS: the workgroup's record | xs: solution entries (ancestors, then the subtree) |
+// red: partial sums of the rectangular parts | the slot lists of its fronts.  A level's fronts run side by side on a
+// power-of-two share of the waves each; every barrier is executed by the whole workgroup the same number of times
+// (the panel loop runs to the level's largest panel count).
+// At most 512 threads: the pipelined panel loop keeps two 32-entry register arrays, which fit the 256 VGPRs a wave has
+// up to that size and not the 128 beyond it.
+__global__ __launch_bounds__(512) void backward_fused_kernel(const int* __restrict__ wgs, int wstride, int max_levels, int xs_cap,
+                                                              int red_cap, const int* __restrict__ slots,
+                                                              const double* __restrict__ fronts, const double* __restrict__ linv,
+                                                              const int* __restrict__ perm, double* y, double* x, long long* prof) {
+  extern __shared__ double sh[];
+  STAMP(0);      // stamps: 1 staged, 2 path done, 3 .. 6 the subtree's levels (6: the fourth and every later one), 7 end
+  int* rec = (int*)sh;
+  double* xs = sh + wstride / 2;
+  double* red = xs + xs_cap;
+  int* sl = (int*)(red + red_cap);
+  const int tid = threadIdx.x, T = blockDim.x, W = T >> 6, wave = uni(tid >> 6), lane = tid & 63;
+  {
+    const int* src = wgs + (size_t)blockIdx.x * wstride;
+    for (int i = tid; i < wstride; i += T) rec[i] = src[i];
+  }
+  __syncthreads();
+  const int nlevels = rec[0], njobs = rec[1], first_lv = rec[2], sub_lv = rec[5];
+  const int* jobs = rec + kFusedHdr + kFusedLevelInts * max_levels;
+  // every right-hand side (row nf of the front) into its place in xs, every slot list into LDS, ancestors above h_top
+  // from y: all of a workgroup's index and operand loads but the rows of L are issued here, side by side
+  for (int jb = wave; jb < njobs; jb += W) {
+    const int* j = jobs + kFusedJobInts * jb;
+    const int nf = uni(j[FJ_NF]), ns = uni(j[FJ_NS]), flags = uni(j[FJ_FLAGS]), base = uni(j[FJ_BASE]);
+    const long long off = ((long long)uni(j[FJ_OFF + 1]) << 32) | (unsigned)uni(j[FJ_OFF]);
+    const double* srcv = (flags & 2) ? y + uni(j[FJ_FIRST]) : fronts + off + (long long)(nf + 1) * nf;
+    for (int i0 = 0; i0 < ns; i0 += 256) {
+      double v[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + 64 * k + lane;
+        v[k] = srcv[min(i, ns - 1)];      // clamped, not predicated: the four loads go out together
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + 64 * k + lane;
+        if (i < ns) xs[base + i] = v[k];
+      }
+    }
+    if (flags & 2) continue;
+    const int nb = nf - ns;
+    const int* ssrc = slots + uni(j[FJ_SOFS]);
+    int* sdst = sl + uni(j[FJ_LSOFS]);
+    for (int i0 = 0; i0 < nb; i0 += 256) {
+      int v[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + 64 * k + lane;
+        v[k] = ssrc[min(i, nb - 1)];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int i = i0 + 64 * k + lane;
+        if (i < nb) sdst[i] = v[k];
+      }
+    }
+  }
+  __syncthreads();
+  STAMP(1);
+  if (first_lv == sub_lv) STAMP(2);
+  for (int lv = first_lv; lv < nlevels; ++lv) {
+    const int* li = rec + kFusedHdr + kFusedLevelInts * lv;
+    const int lofs = li[0], cnt = li[1], maxp = li[2], items = li[3];
+    int G = W;      // waves per front
+    while (G > 1 && W / G < cnt) G >>= 1;
+    const int ngrp = W / G, GT = G << 6, grp = wave / G, gtid = tid - grp * GT, gw = wave - grp * G;
+    double* redg = red + grp * items;
+    for (int r0 = 0; r0 < cnt; r0 += ngrp) {
+      const bool act = r0 + grp < cnt;
+      const int* j = jobs + kFusedJobInts * (lofs + (act ? r0 + grp : 0));
+      const int nf = uni(j[FJ_NF]), ns = uni(j[FJ_NS]), nsl = uni(j[FJ_NSL]), nt = uni(j[FJ_NT]), nb = nf - ns, ld = nf + 1;
+      const long long off = ((long long)uni(j[FJ_OFF + 1]) << 32) | (unsigned)uni(j[FJ_OFF]);
+      const long long loff = ((long long)uni(j[FJ_LOFF + 1]) << 32) | (unsigned)uni(j[FJ_LOFF]);
+      const double* F = fronts + off;
+      double* u = xs + uni(j[FJ_BASE]);
+      const int npanel = (ns + PB - 1) / PB;
+      const bool sub = act && gw == 0 && npanel > 0;      // this wave does the front's substitutions
+      // Software pipeline: the pivot block of the next panel is loaded as soon as a substitution is done (the first one
+      // before the rectangular part), the rows of L of the next update as soon as an update is done (they arrive during
+      // the substitution in between) -- each batch of 32 loads under ONE wave-uniform branch, a phase before its use.
+      // (Issuing both batches from every wave under no branch makes every wait a counted one, and was measured slower:
+      // 168 us against 132 for the launch at fem2d L=7 -- the idle waves' loads queue in front of the needed ones.)
+      double lc[PB], f[PB];
+      if (sub) load_pivot_block(lc, linv + loff + (long long)(npanel - 1) * 2 * PB * PB, lane);
+      if (items > 0) {      // u -= L21' x_bdry
+        if (act && nsl > 0) {
+          const int* sj = sl + uni(j[FJ_LSOFS]);
+          const int nit = ns * nsl, R = (nb + nsl - 1) / nsl;      // R: rows of the longest slice
+          // two (column, slice) items per thread at a time, eight rows each: 16 independent loads in flight; a slice's
+          // rows are still added in ascending order by fma
+          for (int it0 = gtid; it0 < nit; it0 += 2 * GT) {
+            const int it1 = it0 + GT;
+            const bool has1 = it1 < nit;
+            const int q0 = it0 / ns, q1 = has1 ? it1 / ns : q0;
+            const double* c0 = F + (long long)ld * ns + (it0 - q0 * ns);
+            const double* c1 = F + (long long)ld * ns + (has1 ? it1 - q1 * ns : it0 - q0 * ns);
+            double s0 = 0.0, s1 = 0.0;
+            for (int r0 = 0; r0 < R; r0 += 8) {
+              double a0[8], a1[8];
+#pragma unroll
+              for (int k = 0; k < 8; ++k) {      // clamped, not predicated
+                a0[k] = c0[(long long)ld * min(q0 + (r0 + k) * nsl, nb - 1)];
+                a1[k] = c1[(long long)ld * min(q1 + (r0 + k) * nsl, nb - 1)];
+              }
+#pragma unroll
+              for (int k = 0; k < 8; ++k) {
+                const int i0 = q0 + (r0 + k) * nsl, i1 = q1 + (r0 + k) * nsl;
+                const double v0 = fma(a0[k], xs[sj[min(i0, nb - 1)]], s0), v1 = fma(a1[k], xs[sj[min(i1, nb - 1)]], s1);
+                s0 = (i0 < nb) ? v0 : s0;
+                s1 = (i1 < nb) ? v1 : s1;
+              }
+            }
+            redg[it0] = s0;
+            if (has1) redg[it1] = s1;
+          }
+        }
+        __syncthreads();
+        if (act && nsl > 0)
+          for (int jc = gtid; jc < ns; jc += GT) {
+            double s = redg[jc];
+            for (int q = 1; q < nsl; ++q) s += redg[q * ns + jc];
+            u[jc] = u[jc] - s;
+          }
+        __syncthreads();
+      }
+      if (act && npanel > 1) load_panel_rows(f, F, ld, (npanel - 1) * PB, ns - (npanel - 1) * PB, gtid);
+      for (int it = 0; it < maxp; ++it) {
+        const int pp = npanel - 1 - it, k0 = pp * PB, kw = min(PB, ns - k0);
+        if (sub && pp >= 0) {
+          panel_substitute(lc, u + k0, kw, lane);
+          if (pp > 0) load_pivot_block(lc, linv + loff + (long long)(pp - 1) * 2 * PB * PB, lane);
+        }
+        __syncthreads();
+        if (it == maxp - 1) break;
+        if (act && pp > 0) {      // u_j -= sum_{i in p} L[i][j] x_i for the earlier columns j
+          const int jw = min(nt, (k0 + 63) & ~63), nslp = nt / jw;
+          for (int jc = gtid; jc < k0; jc += GT) {
+            double s;
+            if (jc >= GT) {      // fronts wider than their share of the workgroup: the columns beyond it, unpipelined
+              s = panel_dot_any(F + (long long)ld * k0 + jc, ld, u + k0, kw, nslp);
+            } else if (nslp == 1 || nslp == 2 || nslp == 4) {
+              s = nslp == 1 ? panel_dot<1>(f, u + k0, kw) : nslp == 2 ? panel_dot<2>(f, u + k0, kw) : panel_dot<4>(f, u + k0, kw);
+            } else {
+              s = panel_dot_any(F + (long long)ld * k0 + jc, ld, u + k0, kw, nslp);
+            }
+            u[jc] -= s;
+          }
+          if (pp > 1) load_panel_rows(f, F, ld, k0 - PB, PB, gtid);
+        }
+        __syncthreads();
+      }
+      if (act && (uni(j[FJ_FLAGS]) & 1)) {
+        const int first = uni(j[FJ_FIRST]);
+        for (int i = gtid; i < ns; i += GT) {
+          const double v = u[i];
+          y[first + i] = v;
+          x[perm[first + i]] = v;
+        }
+      }
+    }
+    if (lv + 1 == sub_lv) STAMP(2);
+    if (lv >= sub_lv) STAMP(min(3 + lv - sub_lv, 6));
+  }
+  for (int k = 3 + nlevels - sub_lv; k < 7; ++k) STAMP(k);      // fewer than four subtree levels: the rest read as empty phases
+  STAMP(7);
+}
+
 // Split factorisation: the Schur complement of a subtree root -- lower triangle of the boundary block of its front plus
 // the right-hand-side row, column j packed at j (nb + 1) - j (j - 1) / 2 -- into / out of the exchange buffer.  A rank
 // that does not own the subtree contributes zeros, so the sum over the ranks is the owner's block, exactly.
@@ -1511,6 +1744,10 @@ const CholKnobs& GpuChol::knobs() {
     c.step2_tiles = num("MGB_CHOL_STEP2_TILES", 224);
     c.dense_tiles = num("MGB_CHOL_DENSE_TILES", 512);      // what two tiles per CU hold at once
     c.bwd_split_nf = num("MGB_BWD_SPLIT_NF", 192);
+    c.bwd_fused = on("MGB_CHOL_BWD_FUSED");
+    c.bwd_cut = num("MGB_CHOL_BWD_CUT", 2);
+    c.bwd_fused_nf = num("MGB_CHOL_BWD_FUSED_NF", 384);
+    c.bwd_fused_threads = num("MGB_CHOL_BWD_FUSED_THREADS", 512);
     return c;
   }();
   return k;
@@ -1588,7 +1825,11 @@ int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::v
   const CholKnobs& kn = knobs();
   std::vector<Launch> bwd;
   std::vector<StepTile> scratch;
-  for (const std::vector<int>& mine : heights) {
+  // the fused backward launch (unsplit factorisations) takes every height up to h_top
+  const bool fused = fused_.enabled() && &heights == fused_heights_;
+  double fused_bytes = 0;
+  for (size_t hh = 0; hh < heights.size(); ++hh) {
+    const std::vector<int>& mine = heights[hh];
     if (mine.empty()) continue;
     const int nofs = (int)jobs.lists.size(), ncnt = (int)mine.size();
     jobs.lists.insert(jobs.lists.end(), mine.begin(), mine.end());
@@ -1712,6 +1953,11 @@ int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::v
         for (int ch = 0; ch * 64 < g.ns; ++ch) jobs.rects.push_back({t, ch});
     }
     const int nrect = (int)jobs.rects.size() - rofs, nt = max_nf > 384 ? 1024 : 256;
+    if (fused && (int)hh <= fused_.h_top) {
+      jobs.rects.resize(rofs);
+      fused_bytes += rect_bytes + tri_bytes;
+      continue;
+    }
     std::vector<Launch> h;
     if (nrect) h.push_back({Kind::BwdRect, rofs, nrect, RT, (size_t)(max_nf + RT) * sizeof(double), 0, 0, false, KC_CHOL_BWD_RECT, rect_bytes});
     h.push_back({nt == 1024 ? Kind::Bwd1024 : Kind::Bwd256, nofs, ncnt, nt, (size_t)(max_nf + nt + PB) * sizeof(double), 0, 0, nrect > 0,
@@ -1720,6 +1966,8 @@ int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::v
   }
   const int first_bwd = (int)chain_.size();
   chain_.insert(chain_.end(), bwd.begin(), bwd.end());
+  if (fused)
+    chain_.push_back({Kind::BwdFused, 0, fused_.nwg, fused_.threads, fused_.lds_bytes, 0, 0, false, KC_CHOL_BWD, fused_bytes});
   return first_bwd;
 }
 
@@ -1844,7 +2092,33 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
   }
   Jobs jobs;
   chain_.clear();
+  fused_ = FusedPlan();
+  fused_heights_ = nullptr;
+  if (!part_.split() && knobs().bwd_fused) {
+    std::vector<int> ns(nnodes_), first(nnodes_), parent(nnodes_);
+    std::vector<const std::vector<int>*> bd(nnodes_);
+    for (int t = 0; t < nnodes_; ++t) {
+      ns[t] = nodes[t].ns;
+      first[t] = nodes[t].first;
+      parent[t] = nodes[t].parent;
+      bd[t] = &sym.nodes_[t].bdry;
+    }
+    const CholKnobs& kn = knobs();
+    FusedKnobs fk;
+    fk.cut = kn.bwd_cut;
+    fk.top_nf = kn.bwd_fused_nf;
+    fk.threads = kn.bwd_fused_threads;
+    fk.split_nf = kn.bwd_split_nf;
+    fused_ = plan_bwd_fused(ns, first, parent, bd, fk);
+    if (fused_.lds_bytes > 150 * 1024) fused_ = FusedPlan();      // does not fit: the per-height launches
+    if (fused_.enabled()) {
+      fused_heights_ = &own;
+      for (int t = 0; t < nnodes_; ++t)
+        if (fused_.bofs[t] != nodes[t].bofs || fused_.height[t] != height[t]) throw InternalError("gpuchol: fused plan disagrees with the front layout");
+    }
+  }
   own_bwd_ = schedule(own, nodes, sjobs, sym, jobs);
+  fused_heights_ = nullptr;
   top_fwd_ = (int)chain_.size();
   if (part_.split()) schedule(top, nodes, sjobs, sym, jobs);
   if ((size_t)(max_nf_ + RT + PB) * 8 > 150 * 1024) throw ArgError("gpuchol: front exceeds the LDS budget of the sweeps");
@@ -1866,6 +2140,8 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
   d_tiles_ = upload(jobs.tiles);
   d_singles_ = upload(jobs.singles);
   d_rectjobs_ = upload(jobs.rects);
+  d_fused_wg_ = upload(fused_.wg);
+  d_fused_slots_ = upload(fused_.slots);
   if (part_.split()) {
     std::vector<RootXchg> roots;
     long long xoff = 0;
@@ -1946,13 +2222,14 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
   ck(hipFuncSetAttribute((const void*)backward_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024), "attr");
   ck(hipFuncSetAttribute((const void*)backward_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024), "attr");
   ck(hipFuncSetAttribute((const void*)backward_rect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024), "attr");
+  ck(hipFuncSetAttribute((const void*)backward_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024), "attr");
   ck(hipFuncSetAttribute((const void*)front_leaf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024), "attr");
   ck(hipFuncSetAttribute((const void*)front_step2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kStep2Lds), "attr");
   ck(hipFuncSetAttribute((const void*)front_panel2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kPanel2Lds), "attr");
   ck(hipFuncSetAttribute((const void*)front_update2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kUpdate2Lds), "attr");
 }
 
-// The whole chain is launch-bound (37 dependent launches at fem2d L=7), so it is captured once per
+// The whole chain is launch-bound (22 dependent launches at fem2d L=7; 37 with MGB_CHOL_BWD_FUSED=0), so it is captured once per
 // (values, rhs, solution) pointer triple into a hipGraph and replayed with ONE host call per Newton step; the
 // event-timed and phase-stamped variants (KernelTimer, MGB_CHOL_PROF) and MGB_CHOL_GRAPH=0 use plain launches.
 void GpuChol::factor_solve(hipStream_t st, double* d_vals, const double* d_b, double* d_x, KernelTimer* tm, bool flag_armed,
@@ -2035,6 +2312,10 @@ void GpuChol::run(hipStream_t st, int begin, int end, const double* d_vals, cons
         hipLaunchKernelGGL(L.kind == Kind::Bwd1024 ? backward_kernel<1024> : backward_kernel<256>, grid, block, L.lds, st,
                            d_hnodes_ + L.ofs, d_lists_ + L.ofs, d_bdry_, d_fronts_, d_linv_, d_perm_, d_rect_, L.rect ? 1 : 0, d_y_,
                            d_x, prof);
+        break;
+      case Kind::BwdFused:
+        hipLaunchKernelGGL(backward_fused_kernel, grid, block, L.lds, st, d_fused_wg_, fused_.wstride, fused_.max_levels,
+                           fused_.xs_cap, fused_.red_cap, d_fused_slots_, d_fronts_, d_linv_, d_perm_, d_y_, d_x, prof);
         break;
     }
     if (tm) tm->end(st);

@@ -12,7 +12,9 @@
 //     front_step p: (one launch per 32-wide panel) every 64x64 tile of the trailing matrix re-derives the
 //                   panel rows it needs (L = A * L11^-T), applies the rank-32 update, and the tile that
 //                   owns the next pivot block factors it, so a panel costs one launch
-//   for each height (root first): backward sweep  L' x = u
+//   backward sweep  L' x = u: ONE launch (backward_fused_kernel: one workgroup per subtree of a cut of the tree solves its
+//     own path from the top and then its subtree, no synchronisation between workgroups; bwd_fused.hpp); heights whose fronts
+//     are too large to repeat, and split factorisations, run one or two launches per height (root first) instead
 //
 // The right-hand side rides along as an extra row of every front (Cholesky of [A b; b' *]), so the
 // forward sweep L u = b happens inside the factorisation at no extra launch.  Fronts are stored as
@@ -26,6 +28,7 @@
 
 #include <vector>
 
+#include "bwd_fused.hpp"
 #include "mfchol.hpp"
 
 namespace mgb {
@@ -92,6 +95,11 @@ struct CholKnobs {
   int step2_tiles;     // MGB_CHOL_STEP2_TILES (224): largest launch, in tiles, that runs two panels fused
   int dense_tiles;     // MGB_CHOL_DENSE_TILES (512): single-panel launches above this many tiles run three tiles per CU
   int bwd_split_nf;    // MGB_BWD_SPLIT_NF (192): front size above which the backward sweep of a height has a backward_rect launch
+  bool bwd_fused;      // MGB_CHOL_BWD_FUSED=0: the backward sweep as one or two launches per height (no backward_fused launch)
+  int bwd_cut;         // MGB_CHOL_BWD_CUT (2): height of the subtrees the fused backward launch gives one workgroup each (raised by
+                       // up to two heights until they are at most 256, one per CU; trees that need more keep the per-height launches)
+  int bwd_fused_nf;    // MGB_CHOL_BWD_FUSED_NF (384): heights with a larger front keep their own backward launches; 0: no limit
+  int bwd_fused_threads;  // MGB_CHOL_BWD_FUSED_THREADS (512): workgroup size of the fused backward launch (a power of two, 64 .. 512)
 };
 
 class GpuChol {
@@ -193,14 +201,18 @@ class GpuChol {
   StepTile* d_tiles_ = nullptr;
   SingleTile* d_singles_ = nullptr;
   RectJob* d_rectjobs_ = nullptr;
+  const std::vector<std::vector<int>>* fused_heights_ = nullptr;      // (during build) the height lists the plan covers
+  FusedPlan fused_;               // fused backward sweep (unsplit factorisations): host tables, empty where it is off
+  int* d_fused_wg_ = nullptr;     // ... its workgroup records
+  int* d_fused_slots_ = nullptr;  // ... and the LDS slot of every boundary entry (parallel to d_bdry_)
   // host schedule: every dispatch of the chain, decided once by build()
   enum class Kind : unsigned char {
-    Leaf, Single, SingleNarrow, SingleDense, SingleDenseNarrow, Start, Step, Step2, Panel2, Update2, BwdRect, Bwd256, Bwd1024
+    Leaf, Single, SingleNarrow, SingleDense, SingleDenseNarrow, Start, Step, Step2, Panel2, Update2, BwdRect, Bwd256, Bwd1024, BwdFused
   };
   struct Launch {
     Kind kind;
     int ofs, cnt;       // job range, one workgroup per job, in lists (Leaf, Bwd*), singles (Single*), starts (Start),
-                        // tiles (Step, Step2, Panel2, Update2) or rects (BwdRect)
+                        // tiles (Step, Step2, Panel2, Update2), rects (BwdRect) or the fused sweep's workgroup records (BwdFused)
     int block;          // threads per workgroup
     size_t lds;         // dynamic LDS bytes
     int p, npiv;        // first panel, leading pivot workgroups (step kinds)

@@ -72,6 +72,12 @@ class MfChol {
     ns.clear(); nf.clear(); parent.clear();
     for (const Node& nd : nodes_) { ns.push_back(nd.ns); nf.push_back(nd.nf()); parent.push_back(nd.parent); }
   }
+  // what the backward sweep's schedule needs per node: own size, first own unknown (new ordering), parent and the
+  // boundary list (new indices, ascending; the pointers stay valid as long as this object)
+  void bwd_tables(std::vector<int>& ns, std::vector<int>& first, std::vector<int>& parent, std::vector<const std::vector<int>*>& bdry) const {
+    ns.clear(); first.clear(); parent.clear(); bdry.clear();
+    for (const Node& nd : nodes_) { ns.push_back(nd.ns); first.push_back(nd.first); parent.push_back(nd.parent); bdry.push_back(&nd.bdry); }
+  }
 
  private:
   friend class GpuChol;   // the device factorisation reuses this symbolic structure verbatim
