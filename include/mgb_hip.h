@@ -179,6 +179,17 @@ int mgb_amg_f2_f32(mgb_amg a, int level, const float* s, float t, float* lower_v
 int mgb_amg_f1_template_f64(mgb_amg a, int level, const double* s, double t, double* g);
 int mgb_amg_f2_template_f64(mgb_amg a, int level, const double* s, double t, double* lower_vals);
 int mgb_amg_chol_info(mgb_amg a, int level, int* split_world, double* exchange_doubles, int* launches);
+/* the launch chain of that factorisation (built now if needed; read-only: no numerics or launches change), in launch order:
+ * *nlaunch launches, the kind code and the workgroup count of the first min(cap, *nlaunch).  Kind codes (GpuChol::Kind):
+ *   0 Leaf  1 Single  2 SingleNarrow  3 SingleDense  4 SingleDenseNarrow  5 Start  6 Step  7 Step2  8 Panel2  9 Update2
+ *   10 BwdRect  11 Bwd256  12 Bwd1024  13 BwdFused
+ * unknown_node / unknown_col (nullable, N entries each): per unknown of the original ordering its tree node (postorder, as
+ * mgb_amg_chol_tree) and its column among that node's own columns (0 .. ns - 1).  kind / workgroups may be null. */
+int mgb_amg_chol_schedule(mgb_amg a, int level, int cap, int* nlaunch, int* kind, int* workgroups, int* unknown_node,
+                          int* unknown_col);
+/* the elimination tree of that factorisation in postorder (children first): own size, front size and parent (-1 = root)
+ * of the first min(cap, *nnodes) nodes -- mgb_plan_chol_tree for the level as the device factors it */
+int mgb_amg_chol_tree(mgb_amg a, int level, int cap, int* nnodes, int* ns, int* nf, int* parent);
 /* *yes = 1 if the subtrees of the split follow the row partition: a rank's Hessian values are then used where they were
  * computed, only the entries among separator unknowns are summed (inside the Schur-complement collective, counted in
  * exchange_doubles), and the allreduce of all nnz values per Newton step is gone (MGB_RANK_ALIGNED=0 restores it) */

@@ -879,6 +879,31 @@ class AMG:
         call("mgb_amg_chol_values_local", self.handle, self.L - 1 if l is None else int(l), C.byref(vl))
         return dict(split_world=sw.value, exchange_doubles=ex.value, launches=la.value, values_local=bool(vl.value))
 
+    CHOL_KINDS = ("Leaf", "Single", "SingleNarrow", "SingleDense", "SingleDenseNarrow", "Start", "Step", "Step2", "Panel2",
+                  "Update2", "BwdRect", "Bwd256", "Bwd1024", "BwdFused")      # kind codes of mgb_amg_chol_schedule
+
+    def chol_schedule(self, l=None):
+        """Launch chain of the device factorisation of level l (default finest) in launch order: kind names and workgroup
+        counts; per unknown its tree node (postorder) and own column; and per tree node its own size, front size, parent
+        and height (leaves 0).  Read-only."""
+        l = self.L - 1 if l is None else int(l)
+        N = self.level_size(l)[0]
+        nl = C.c_int()
+        call("mgb_amg_chol_schedule", self.handle, l, 0, C.byref(nl), None, None, None, None)
+        kind, wg = np.empty(nl.value, dtype=np.int32), np.empty(nl.value, dtype=np.int32)
+        node, col = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32)
+        call("mgb_amg_chol_schedule", self.handle, l, nl.value, C.byref(nl), iptr(kind), iptr(wg), iptr(node), iptr(col))
+        nn = C.c_int()
+        call("mgb_amg_chol_tree", self.handle, l, 0, C.byref(nn), None, None, None)
+        ns, nf, par = (np.empty(nn.value, dtype=np.int32) for _ in range(3))
+        call("mgb_amg_chol_tree", self.handle, l, nn.value, C.byref(nn), iptr(ns), iptr(nf), iptr(par))
+        height = np.zeros(nn.value, dtype=np.int32)
+        for t in range(nn.value):                     # postorder: children first
+            if par[t] >= 0:
+                height[par[t]] = max(height[par[t]], height[t] + 1)
+        return dict(kinds=[self.CHOL_KINDS[k] for k in kind], workgroups=wg, unknown_node=node, unknown_col=col, ns=ns, nf=nf,
+                    parent=par, height=height)
+
     def hessian_pattern(self, l):
         N, nz = self.level_size(l)
         rp = np.empty(N + 1, dtype=np.int32)

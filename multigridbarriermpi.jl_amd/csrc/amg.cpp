@@ -644,6 +644,25 @@ void Amg::chol_info(int l, int* split_world, double* exchange_doubles, int* laun
   if (launches) *launches = lv.gchol.launches_per_solve();
 }
 
+void Amg::chol_schedule(int l, int cap, int* nlaunch, int* kind, int* workgroups, int* unknown_node, int* unknown_col) {
+  Level& lv = level(l);
+  ensure_chol(lv);
+  lv.gchol.schedule_info(cap, nlaunch, kind, workgroups);
+  GpuChol::unknown_columns(lv.chol, unknown_node, unknown_col);
+}
+
+void Amg::chol_tree(int l, int cap, int* nnodes, int* ns, int* nf, int* parent) {
+  Level& lv = level(l);
+  ensure_chol(lv);
+  std::vector<int> a, b, c;
+  lv.chol.tree(a, b, c);
+  if (nnodes) *nnodes = (int)a.size();
+  const size_t m = std::min<size_t>(std::max(cap, 0), a.size());
+  if (ns) std::copy(a.begin(), a.begin() + m, ns);
+  if (nf) std::copy(b.begin(), b.begin() + m, nf);
+  if (parent) std::copy(c.begin(), c.begin() + m, parent);
+}
+
 void Amg::prepare(int l) {
   const int L = (int)levels_.size();
   for (int J = (l >= 0 ? l : (schedule_all_ ? 0 : L - 1)); J <= (l >= 0 ? l : L - 1); ++J) {

@@ -302,6 +302,10 @@ class Amg {
   const BarrierParams& params() const { return P_; }
   // device factorisation of level l: ranks it is split over (1 = replicated), doubles exchanged per solve, launches
   void chol_info(int l, int* split_world, double* exchange_doubles, int* launches);
+  // ... its launch chain (kind code and workgroups per launch, launch order) and per unknown its tree node and own column
+  void chol_schedule(int l, int cap, int* nlaunch, int* kind, int* workgroups, int* unknown_node, int* unknown_col);
+  // ... its elimination tree in postorder: own size, front size and parent of the first min(cap, *nnodes) nodes
+  void chol_tree(int l, int cap, int* nnodes, int* ns, int* nf, int* parent);
   bool chol_values_local(int l) { return values_stay_local(level(l)); }
   // feasibility phases: stop the continuation after the first centering at which row `col` of Dz is negative at every node
   // (col < 0: off).  The solve then returns normally with fewer t-steps instead of running to t_stop.

@@ -788,6 +788,19 @@ int mgb_amg_chol_info(mgb_amg a, int level, int* split_world, double* exchange_d
     a->amg->chol_info(level, split_world, exchange_doubles, launches);
   });
 }
+int mgb_amg_chol_schedule(mgb_amg a, int level, int cap, int* nlaunch, int* kind, int* workgroups, int* unknown_node,
+                          int* unknown_col) {
+  return guard([&] {
+    need(a && level >= 0 && level < a->amg->L(), "level out of range");
+    a->amg->chol_schedule(level, cap, nlaunch, kind, workgroups, unknown_node, unknown_col);
+  });
+}
+int mgb_amg_chol_tree(mgb_amg a, int level, int cap, int* nnodes, int* ns, int* nf, int* parent) {
+  return guard([&] {
+    need(a && level >= 0 && level < a->amg->L(), "level out of range");
+    a->amg->chol_tree(level, cap, nnodes, ns, nf, parent);
+  });
+}
 int mgb_amg_chol_values_local(mgb_amg a, int level, int* yes) {
   return guard([&] {
     need(a && yes && level >= 0 && level < a->amg->L(), "level out of range");

@@ -1193,10 +1193,10 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 }
 
 // Leaf heights (no children) whose fronts fit LDS and whose trailing matrix after the first panel is one 64x64
-// tile (nf <= 95, ns <= 64; at fem2d L=7 the 1 024 leaves, nf ~ 64, ns ~ 35): ONE workgroup assembles the front in
-// LDS, runs its (at most two) panels -- pivot-block factor, panel rows by in-register substitution, rank-32
-// update on the 4x4 micro-tiles of the tile kernels -- and writes the Schur complement, the rows of L and the
-// pivot blocks back.  One launch replaces front_start + two front_step launches of the widest height of the tree.
+// tile (ns <= 64, nf + 1 - min(ns, 32) <= 64 -- so nf <= 95; at fem2d L=7 the 1 024 leaves, nf ~ 64, ns ~ 35): ONE
+// workgroup assembles the front in LDS, runs its (at most two) panels -- pivot-block factor, panel rows by in-register
+// substitution, rank-32 update on the 4x4 micro-tiles of the tile kernels -- and writes the Schur complement, the rows
+// of L and the pivot blocks back.  One launch replaces front_start + two front_step launches of the widest height of the tree.
 __global__ __launch_bounds__(TB, 4) void front_leaf_kernel(
     const GNode* __restrict__ nodes, const int* __restrict__ list, const int* __restrict__ asm_src,
     const int* __restrict__ asm_pos, const double* __restrict__ vals, const int* __restrict__ perm,
@@ -1835,6 +1835,7 @@ int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::v
     jobs.lists.insert(jobs.lists.end(), mine.begin(), mine.end());
     int max_ns = 0, max_nf = 0;
     bool childless = true, all_pivots = true;      // a pass-through front (ns = 0) needs front_start to copy it
+    bool one_tile = true;      // front_leaf: the trailing matrix after the first panel, rows min(ns, 32) .. nf, is one 64-row tile
     double start_bytes = 0;
     for (int t : mine) {
       const GNode& g = nodes[t];
@@ -1842,6 +1843,7 @@ int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::v
       max_nf = std::max(max_nf, g.nf);
       childless = childless && g.child[0] < 0 && g.child[1] < 0;
       all_pivots = all_pivots && g.ns >= 1;
+      one_tile = one_tile && g.nf + 1 - std::min(g.ns, PB) <= TS;
       start_bytes += 0.5 * g.nf * g.nf * 8.0 + (double)sym.a_idx_[t].size() * 20.0;
       for (int c : g.child) {
         if (c < 0) continue;
@@ -1849,8 +1851,10 @@ int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::v
         start_bytes += 0.5 * cnb * cnb * 8.0;     // child entry read (the parent entry write is counted above)
       }
     }
-    // leaf heights with small fronts: the whole front in one workgroup (front_leaf_kernel)
-    const bool leaf = kn.leaf && max_nf <= 95 && max_ns <= 2 * PB && childless && all_pivots;
+    // leaf heights with small fronts: the whole front in one workgroup (front_leaf_kernel).  nf <= 95 alone is not enough:
+    // a narrow leaf with a wide boundary (3-D trees under a small MGB_LEAF: ns = 16, nf = 88) has more trailing rows than
+    // the kernel's one tile, and the rows past it were never updated
+    const bool leaf = kn.leaf && max_nf <= 95 && max_ns <= 2 * PB && childless && all_pivots && one_tile;
     // single-panel heights with children: one dependency-free launch (front_single_kernel)
     const bool single = kn.single && max_ns <= PB && !childless && all_pivots;
     if (leaf) {
@@ -1969,6 +1973,24 @@ int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::v
   if (fused)
     chain_.push_back({Kind::BwdFused, 0, fused_.nwg, fused_.threads, fused_.lds_bytes, 0, 0, false, KC_CHOL_BWD, fused_bytes});
   return first_bwd;
+}
+
+void GpuChol::schedule_info(int cap, int* nlaunch, int* kind, int* workgroups) const {
+  if (nlaunch) *nlaunch = (int)chain_.size();
+  const int m = std::min(std::max(cap, 0), (int)chain_.size());
+  for (int i = 0; i < m; ++i) {
+    if (kind) kind[i] = (int)chain_[i].kind;
+    if (workgroups) workgroups[i] = chain_[i].cnt;
+  }
+}
+
+void GpuChol::unknown_columns(const MfChol& sym, int* node, int* col) {
+  for (int t = 0; t < (int)sym.nodes_.size(); ++t)
+    for (int k = 0; k < sym.nodes_[t].ns; ++k) {
+      const int i = sym.perm_[sym.nodes_[t].first + k];
+      if (node) node[i] = t;
+      if (col) col[i] = k;
+    }
 }
 
 void GpuChol::build(const MfChol& sym, Ctx* ctx) {

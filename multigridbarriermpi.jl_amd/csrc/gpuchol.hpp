@@ -143,6 +143,11 @@ class GpuChol {
   double front_bytes() const { return (double)total_front_ * 8; }
   double factor_flops() const { return flops_; }
   int launches_per_solve() const { return (int)chain_.size(); }
+  // the chain in launch order (nullable outputs): *nlaunch launches, the Kind code (enum order) and the workgroup count of
+  // the first min(cap, *nlaunch) of them.  Read-only.
+  void schedule_info(int cap, int* nlaunch, int* kind, int* workgroups) const;
+  // per unknown (original ordering, nullable outputs): its tree node (postorder) and its column among that node's own columns
+  static void unknown_columns(const MfChol& sym, int* node, int* col);
 
  private:
   template <class T>
