@@ -133,7 +133,9 @@ int mgb_amg_create(mgb_ctx ctx, mgb_geo g, int S, const char* const* state_vars,
                    int nq, const int* idx_q, int idx_s, double p, mgb_amg* out);
 /* Barrier of an intersection of 1 or 2 power cones (upstream `intersect` of convex_Euclidian_power sets, as
  * used by parabolic_solve: s1 >= u^2 and s2 >= |grad u|^p).  nq[c], idx_q[3*c + i], idx_s[c], p[c] per cone;
- * idx_s2 (nullable) names an extra D row added to the cone's slack (feasibility phase), -1 for none. */
+ * idx_s2 (nullable) names an extra D row added to the cone's slack (feasibility phase), -1 for none.
+ * The rows a cone names -- idx_q[3*c .. 3*c + nq[c]), idx_s[c] and idx_s2[c] -- must be distinct (MGB_E_ARG otherwise, here and
+ * in mgb_amg_create / mgb_amg_create_terms / mgb_map_rows_barrier): the Hessian keeps one off-diagonal slot per pair of them. */
 int mgb_amg_create_cones(mgb_ctx ctx, mgb_geo g, int S, const char* const* state_vars, int K, const char* const* D,
                          int ncones, const int* nq, const int* idx_q, const int* idx_s, const int* idx_s2,
                          const double* p, mgb_amg* out);

@@ -171,6 +171,10 @@ BarrierParams make_params_cones(int K, int ncones, const int* nq, const int* idx
     S.is2 = idx_s2 ? idx_s2[c] : -1;
     need(S.is2 < K, "barrier: idx_s2 out of range");
     if (S.is2 < 0) S.is2 = -1;
+    // the active columns q_1..q_nq, s [, s2] must be distinct: expand_hessian_rows_kernel and the assembly give every pair of
+    // active columns ONE off-diagonal slot, which is only right when the pair names two different rows of D
+    for (int a = 0; a < S.nact(); ++a)
+      for (int b = 0; b < a; ++b) need(S.col(a) != S.col(b), "barrier: repeated column in a power cone");
     S.a = 2.0 / p[c];
     S.mu = (p[c] == 2.0) ? 0.0 : (p[c] < 2.0 ? 1.0 : 2.0);
   }

@@ -1,0 +1,213 @@
+"""The reference machinery of the barrier-row check (barrier_reference.py) on the CPU, on every run:
+
+  * the long-double rows against a 60-digit evaluation (mpmath; the only place it is imported): ratio <= 2^-8 -- long
+    double's unit roundoff is 2^-11 u, the factor 8 is for the few operations behind an entry;
+  * the fp64 baseline: the oracle's F / F1 / F2 on every class of the sweep; its worst ratio per class is rho_base, the
+    yardstick the device kernels are held to in test_gpu_barrier_rows.py.  A correctly rounded fp64 evaluation has ratio
+    <= 1 to first order; numpy's pow / log are within an ulp, so rho_base <= 4 pins the bound model (measured: 0.0 .. 1.2);
+  * the case table covers what the issue of the check lists;
+  * the level propagation on the committed goldens: oracle f0 / f1 / f2 in fp64 at the golden z against the exact values."""
+import os
+
+import numpy as np
+import pytest
+
+import barrier_reference as BR
+import mgb_oracle as O
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+RHO_BASE_MAX = 4.0
+MP_ROWS = 24          # rows of every class that go through mpmath (more than 200 per case of the table)
+
+
+# ---------------------------------------------------------------------------------------------------------- 60 digits
+def _mp_rows(terms, Y, a_node=None, mu_node=None, mask=None):
+    """F, F1, F2 of every row at 60 digits, written separately from barrier_reference (scalar code, one row at a time)."""
+    import mpmath as mp
+    mp.mp.dps = 60
+    n, K = Y.shape
+    outF, outG, outH = [], [], []
+    for r in range(n):
+        y = [mp.mpf(float(v)) for v in Y[r]]
+        F, G, H = mp.mpf(0), [mp.mpf(0)] * K, [[mp.mpf(0)] * K for _ in range(K)]
+        G = list(G)
+        inside = True
+        for ti, term in enumerate(terms):
+            if mask is not None and not mask[r, ti]:
+                continue
+            if term[0] == "linear":
+                _, idx, coef, off = term
+                phi = mp.mpf(float(off)) + sum(mp.mpf(float(c)) * y[i] for i, c in zip(idx, coef))
+                if not phi > 0:
+                    inside = False
+                    continue
+                F -= mp.log(phi)
+                for i, ci in zip(idx, coef):
+                    G[i] -= mp.mpf(float(ci)) / phi
+                    for j, cj in zip(idx, coef):
+                        H[i][j] += mp.mpf(float(ci)) * mp.mpf(float(cj)) / phi ** 2
+                continue
+            idx, p = term[0], term[1]
+            a = mp.mpf(float(BR.a_of(p))) if a_node is None else mp.mpf(float(a_node[r, ti]))
+            mu = mp.mpf(float(BR.mu_of(p))) if mu_node is None else mp.mpf(float(mu_node[r, ti]))
+            qi, scols = list(idx[:-1]), [idx[-1]] + ([term[2]] if len(term) > 2 else [])
+            s = sum(y[c] for c in scols)
+            if not s > 0:
+                inside = False
+                continue
+            phi = s ** a - sum(y[c] ** 2 for c in qi)
+            if not phi > 0:
+                inside = False
+                continue
+            F -= mp.log(phi) + mu * mp.log(s)
+            ds, dds = a * s ** (a - 1), a * (a - 1) * s ** (a - 2)
+            gs = -ds / phi - mu / s
+            hss = -dds / phi + ds ** 2 / phi ** 2 + mu / s ** 2
+            for c in qi:
+                G[c] += 2 * y[c] / phi
+                for c2 in qi:
+                    H[c][c2] += 4 * y[c] * y[c2] / phi ** 2 + (2 / phi if c == c2 else 0)
+                for cs in scols:
+                    H[c][cs] -= 2 * y[c] * ds / phi ** 2
+                    H[cs][c] -= 2 * y[c] * ds / phi ** 2
+            for cs in scols:
+                G[cs] += gs
+                for cs2 in scols:
+                    H[cs][cs2] += hss
+        outF.append(F if inside else mp.inf)
+        outG.append(G)
+        outH.append(H)
+    return outF, outG, outH
+
+
+def _ld(x):
+    """An mpmath number as a long double (head + tail of two doubles)."""
+    import mpmath as mp
+    if mp.isinf(x):
+        return BR.LD(np.inf)
+    hi = float(x)
+    return BR.LD(hi) + BR.LD(float(x - mp.mpf(hi)))
+
+
+def _mp_ratio(terms, Y, R, **kw):
+    mF, mG, mH = _mp_rows(terms, Y, **kw)
+    n, K = Y.shape
+    F = np.array([_ld(v) for v in mF], dtype=BR.LD)
+    G = np.array([[_ld(v) for v in row] for row in mG], dtype=BR.LD).reshape(n, K)
+    H = np.array([[[_ld(v) for v in r2] for r2 in row] for row in mH], dtype=BR.LD).reshape(n, K, K)
+    assert np.array_equal(np.isinf(F), np.isinf(R.F))
+    fin = np.isfinite(F)
+    return max(BR.ratio(R.F, F, R.bF, fin), BR.ratio(R.F1, G, R.bF1, fin), BR.ratio(R.F2, H, R.bF2, fin))
+
+
+@pytest.fixture(scope="module")
+def sweep():
+    return list(BR.classes())
+
+
+def test_case_table_covers_the_menu():
+    terms = [BR.parse(t) for _, _, ts in BR.CASES for t in ts]
+    cones = [t for t in terms if t["kind"] == 0]
+    halves = [t for t in terms if t["kind"] == 1]
+    assert {len(t["q"]) for t in cones} == {1, 2, 3} and {len(t["q"]) for t in halves} == {1, 2, 3}
+    assert {len(t["q"]) for t in cones if t["s2"] >= 0} == {1, 2, 3}                   # is2 set, with every nq
+    assert {len(ts) for _, _, ts in BR.CASES} == {1, 2, 3}
+    assert {K for _, K, _ in BR.CASES} == {2, 4, 5, 8}
+    assert {t["p"] for t in cones} == {1.0, BR.P_NEAR_ONE, 1.5, 2.0, 3.0, 8.0}
+    assert any(t["cols"] != sorted(t["cols"]) for t in cones) and any(t["cols"] != sorted(t["cols"]) for t in halves)
+    assert any(np.any(np.diff(sorted(t["cols"])) > 1) for t in cones)                  # non-contiguous
+    assert any(min(t["coef"]) < 0 < max(t["coef"]) for t in halves)                    # mixed signs
+    shared = [ts for _, _, ts in BR.CASES if len(ts) > 1 and
+              sum(len(BR.parse(t)["cols"]) for t in ts) > len({c for t in ts for c in BR.parse(t)["cols"]})]
+    assert len(shared) >= 3
+    assert any(K != len(BR.parse(ts[0])["cols"]) + 1 for _, K, ts in BR.CASES)         # K other than dim + 2
+    assert [r[0] for r in BR.REGIMES[:4]] == ["1e0", "1e-4", "1e-8", "1e-11"]
+
+
+def test_generated_rows_are_inside_at_the_asked_distance(sweep):
+    for label, K, terms, Y in sweep:
+        assert len(Y) >= 40, label
+        R = BR.reference(terms, Y)
+        assert R.feasible.all() and R.in_range.all() and np.isfinite(R.F).all(), label
+        assert float(R.dist.min()) >= BR.MIN_DIST, label
+
+
+def test_long_double_rows_match_60_digits(sweep):
+    worst = 0.0
+    for label, K, terms, Y in sweep:
+        Y = Y[:MP_ROWS]
+        worst = max(worst, _mp_ratio(terms, Y, BR.reference(terms, Y)))
+        assert worst <= 2.0 ** -8, label
+    K, terms, Y, pn = BR.node_exponent_rows()
+    Y, pn = Y[::4], pn[::4]
+    an, mn = BR.a_of(pn), BR.mu_of(pn)
+    assert set(mn.ravel()) == {0.0, 1.0, 2.0}
+    worst = max(worst, _mp_ratio(terms, Y, BR.reference(terms, Y, a_node=an, mu_node=mn), a_node=an, mu_node=mn))
+    K, terms, Y, mask = BR.piecewise_rows()
+    worst = max(worst, _mp_ratio(terms, Y[::3], BR.reference(terms, Y[::3], mask=mask[::3]), mask=mask[::3]))
+    for K, terms, Y, what in BR.hand_made():
+        Y = np.array(Y, dtype=np.float64)
+        mF = _mp_rows(terms, Y)[0]
+        assert all(np.isinf(float(v)) for v in mF) and np.all(np.isposinf(BR.reference(terms, Y).F)), what
+    print("long double rows against 60 digits: worst ratio %.2e (allowed 2^-8 = %.2e)" % (worst, 2.0 ** -8))
+    assert worst <= 2.0 ** -8
+
+
+def test_fp64_baseline_rows(sweep):
+    """rho_base of every class: the oracle's fp64 rows against the reference."""
+    worst = [0.0, 0.0, 0.0]
+    for label, K, terms, Y in sweep:
+        r = BR.rho_base(terms, Y, BR.reference(terms, Y))
+        worst = [max(a, b) for a, b in zip(worst, r)]
+        assert max(r) <= RHO_BASE_MAX, (label, r)
+    K, terms, Y, pn = BR.node_exponent_rows()
+    r = BR.rho_base(terms, Y, BR.reference(terms, Y, a_node=BR.a_of(pn), mu_node=BR.mu_of(pn)), p_node=pn)
+    assert max(r) <= RHO_BASE_MAX, ("per-node p", r)
+    worst = [max(a, b) for a, b in zip(worst, r)]
+    K, terms, Y, mask = BR.piecewise_rows()
+    R = BR.reference(terms, Y, mask=mask)
+    assert np.isfinite(R.F).all()                                    # the violated half space is masked out on those rows
+    r = BR.rho_base(terms, Y, R, mask=mask)
+    assert max(r) <= RHO_BASE_MAX, ("piecewise", r)
+    worst = [max(a, b) for a, b in zip(worst, r)]
+    print("fp64 baseline (oracle rows): worst ratio F %.2f  F1 %.2f  F2 %.2f" % tuple(worst))
+
+
+def test_a_wrong_formula_is_far_outside_the_bound():
+    """The check has teeth on the CPU too: the q-s slot with the wrong sign is a ratio of 1e6 and more in every regime of a
+    p = 1.5 cone.  Dropping mu / s^2 from hss is one at order-one distances and still far outside at 1e-4; closer to the
+    boundary that term sinks below the rounding of ds^2 / phi^2 next to it (its share is about (phi / s^a)^3 / u bounds), so
+    only the order-one regime can see it -- which is why the sweep keeps that regime for every case."""
+    terms = [([1, 2, 3], 1.5)]
+    for target in (None, 1e-4, 1e-8):
+        Y = BR.generate(terms, 4, 0, target, 3, 100, 5)
+        R = BR.reference(terms, Y)
+        H = BR.oracle_set(terms).F2(None, Y)
+        bad = H.copy()
+        bad[:, 3, 3] -= 1.0 / Y[:, 3] ** 2
+        assert BR.ratio(H, R.F2, R.bF2) <= RHO_BASE_MAX
+        if target is None or target >= 1e-4:
+            assert BR.ratio(bad, R.F2, R.bF2) > (1e6 if target is None else 16 * RHO_BASE_MAX)
+        bad = H.copy()
+        bad[:, 1, 3] *= -1
+        assert BR.ratio(bad, R.F2, R.bF2) > 1e6
+
+
+@pytest.mark.parametrize("kind,L,p", BR.SMALL_GOLDENS)
+def test_level_baseline_on_the_goldens(kind, L, p):
+    """Oracle f0 / f1 / f2 in fp64 at the golden z, t = ts[-1] and ts[len // 2], every level, against the exact values: the
+    level baseline.  Measured 0.05 .. 1.1; the any-order summation bound is pessimistic by design, 4 pins it."""
+    gold = np.load(os.path.join(HERE, "golden", BR.golden_name(kind, L, p)))
+    go = getattr(O, kind)(L)
+    Mo = O.amg(go)
+    dim = go.discretization["dim"]
+    c = O.map_rows(lambda xi: O.DEFAULT_F[dim](xi), Mo.x)
+    terms = BR.default_terms(dim, p)
+    ts = gold["ts"]
+    for t in (float(ts[-1]), float(ts[len(ts) // 2])):
+        for l in range(L):
+            r0, r1, r2, Lv = BR.oracle_level_baseline(Mo, l, gold["z"], c, t, terms)
+            kap = float(Lv.rows.kappa.max())
+            print("%s L=%d p=%g t=%.0e level %d: kappa_max %.1e  baseline ratio f0 %.2f f1 %.2f f2 %.2f" % (kind, L, p, t, l, kap, r0, r1, r2))
+            assert Lv.rows.feasible.all()
+            assert max(r0, r1, r2) <= RHO_BASE_MAX
