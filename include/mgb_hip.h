@@ -33,6 +33,7 @@ typedef struct mgb_geo_s* mgb_geo;   /* native Geometry (host); fields of src:31
 typedef struct mgb_amg_s* mgb_amg;   /* AMG hierarchy + barrier problem resident in HBM */
 typedef struct mgb_vec_s* mgb_vec;   /* device fp64 vector  == HPCVector.v (src:175) */
 typedef struct mgb_csr_s* mgb_csr;   /* device CSR          == HPCSparseMatrix local block (src:216-221) */
+typedef struct mgb_locator_s* mgb_locator;   /* point locator of a geometry, device resident (interpolation) */
 
 const char* mgb_last_error(void);
 int mgb_version(void);
@@ -296,6 +297,27 @@ int mgb_amg_sol_pcg(mgb_amg a, long long* counts4, double* time_s);
 int mgb_amg_time_mg_kernels(mgb_amg a, int level, int reps, int nrot, double* ms6, double* bytes6, double* alg6);
 /* coarsest level of the V-cycle whose top is level `top` (the largest level with at most 128 unknowns; dense inverse there) */
 int mgb_amg_mg_info(mgb_amg a, int top, int* coarsest);
+
+/* ---- evaluation at arbitrary points (the step after mpi_to_native in the reference's workflow: README.md:42-50,
+ * docs/src/guide.md:21-52 plot the solution; [UPSTREAM-UNVERIFIED] `interpolate`, the contract is this project's) --------- *
+ * z: nodal values, n x S row-major.  Elements are the row blocks of the geometry: 1-D block 2 (P1), 2-D block 7 (P2 + cubic
+ * bubble, rows 3..6 = edge midpoints and centroid of rows 0..2), 3-D block (k+1)^3 (Q_k on the axis-aligned box of the first
+ * and last row), k = 1..3; any other element shape is MGB_E_ARG at creation.
+ * Containment, in reference coordinates with tau = 1e-12: inside when min(lambda) >= -tau (2-D), every xi_a in
+ * [-tau, 1 + tau] (1-D, 3-D); of all elements containing a point the lowest index wins; a point in no element or with a
+ * non-finite coordinate is outside: every output column NaN, element -1, no error.
+ * The locator uses x, dim, block and n of the geometry alone: a uniform bin grid over the bounding box (about one cell per
+ * element, CSR cell -> ascending elements), built on the host, resident on the device together with x. */
+int mgb_locator_create(mgb_ctx ctx, mgb_geo g, mgb_locator* out);
+int mgb_locator_destroy(mgb_locator loc);
+/* one launch on the context stream, one thread per point: pts m x dim, z n x S, vals m x S, grads (nullable) m x S x dim, all
+ * row-major device vectors of the locator's context; elem_host_or_null: m element indices copied to the host (the call then
+ * waits for the launch).  m = 0 returns at once. */
+int mgb_interpolate(mgb_locator loc, int m, mgb_vec pts, int S, mgb_vec z, mgb_vec vals, mgb_vec grads_or_null,
+                    int32_t* elem_host_or_null);
+/* host restatement (no context, no GPU): the same bins, containment rule and bases on host arrays */
+int mgb_geo_interpolate_host(mgb_geo g, int m, const double* pts, int S, const double* z, double* vals,
+                             double* grads_or_null, int32_t* elem_or_null);
 
 /* ---- host-only symbolic helpers (no GPU needed; used by the CPU test-suite) ----------------- */
 

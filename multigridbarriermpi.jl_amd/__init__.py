@@ -36,6 +36,7 @@ __all__ = [
     "mpi_to_native", "amgb", "Geometry", "AMGBSOL", "HPCVector", "HPCMatrix", "HPCSparseMatrix",
     "backend_hip", "amgb_zeros", "amgb_all_isfinite", "amgb_diag", "amgb_blockdiag", "map_rows", "map_rows_gpu",
     "_raw_array", "_to_cpu_array", "MGBError", "device_count", "AMG", "amg", "hcat", "BarrierFn", "barrier_functions",
+    "interpolate", "sample_grid",
 ]
 
 
@@ -557,8 +558,15 @@ class Geometry:
     coarsen: list
     _geo: object = field(default=None, repr=False)     # mgb_geo handle (MPI geometries only)
     _geo_ref: object = field(default=None, repr=False) # shared owner of that handle, when the library built the geometry
+    _locator: object = field(default=None, repr=False) # mgb_locator handle, made by the first interpolate() and freed here
 
     def __del__(self):
+        try:
+            if self._locator is not None:
+                _lib.load().mgb_locator_destroy(self._locator)
+                self._locator = None
+        except Exception:
+            pass
         try:
             if self._geo is not None and self._geo_ref is None:
                 _lib.load().mgb_geo_destroy(self._geo)
@@ -1444,6 +1452,101 @@ def parabolic_solve(geometry: Geometry, h=0.2, t0=0.0, t1=1.0, p=1.0, f1=None, g
         z = M.get_z()
         u.append(HPCMatrix(z.reshape(n, 3, order="F"), backend))
     return ParabolicSOL(geometry, ts, u)
+
+
+# --------------------------------------------------------------------------- evaluation at arbitrary points
+
+
+def _locator_of(geometry: Geometry):
+    if geometry._geo is None:
+        raise TypeError("interpolate: geometry must come from native_to_mpi / fem*d_mpi")
+    backend = geometry.x.backend
+    if backend.world > 1:
+        raise NotImplementedError("interpolate: sharded contexts (world > 1) are not supported")
+    if geometry._locator is None:
+        h = C.c_void_p()
+        call("mgb_locator_create", backend.handle, geometry._geo, C.byref(h))
+        geometry._locator = h
+    return geometry._locator, backend
+
+
+def interpolate(obj, points, z=None, grad=False, return_element=False):
+    """Evaluate nodal values at arbitrary points on the device (csrc/interp.hip; contract in include/mgb_hip.h and DESIGN.md
+    section 4d).  `obj`: an AMGBSOL (its z and geometry), a ParabolicSOL (all snapshots stacked column-wise, ONE launch,
+    result (T, m, S)) or a device Geometry with `z=` an (n,) / (n, S) array, HPCVector or HPCMatrix.  `points`: (m, dim), or
+    (m,) in 1-D.  Returns vals (m, S) [, grads (m, S, dim) if grad] [, elem (m,) int32 if return_element].  A point outside
+    the mesh (or with a non-finite coordinate) gives NaN in every column and element -1."""
+    T = None
+    if isinstance(obj, AMGBSOL):
+        geometry, z = obj.geometry, (obj.z if z is None else z)
+    elif isinstance(obj, ParabolicSOL):
+        geometry = obj.geometry
+        if z is None:
+            T = len(obj.u)
+            z = np.hstack([np.asarray(_to_cpu_array(uk)).reshape(len(geometry.w), -1) for uk in obj.u])
+    elif isinstance(obj, Geometry):
+        geometry = obj
+    else:
+        raise TypeError("interpolate: expected an AMGBSOL, a ParabolicSOL or a Geometry")
+    loc, backend = _locator_of(geometry)
+    if z is None:
+        raise ValueError("interpolate: z= is required with a Geometry")
+    n, dim = len(geometry.w), geometry.discretization["dim"]
+    if isinstance(z, HPCMatrix) and z.backend is backend:
+        zv, zshape = z._v, z.shape
+    elif isinstance(z, HPCVector) and z.backend is backend:
+        zv, zshape = z, (len(z), 1)
+    else:
+        za = f64(np.asarray(_to_cpu_array(z)))
+        za = za.reshape(za.shape[0], -1) if za.ndim else za.reshape(1, 1)
+        zv, zshape = HPCVector(za, backend), za.shape
+    if zshape[0] != n or zshape[1] < 1:
+        raise ValueError("interpolate: z must have one row per node of the geometry (%d), got shape %r" % (n, tuple(zshape)))
+    S = int(zshape[1])
+    pts = f64(np.asarray(points))
+    if pts.ndim == 1 and dim == 1:
+        pts = pts.reshape(-1, 1)
+    if pts.ndim != 2 or pts.shape[1] != dim:
+        raise ValueError("interpolate: points must have shape (m, %d)" % dim)
+    m = pts.shape[0]
+    pv = HPCVector(pts, backend)
+    vals = HPCVector(m * S, backend)
+    grads = HPCVector(m * S * dim, backend) if grad else None
+    elem = np.empty(m, dtype=np.int32) if return_element else None
+    call("mgb_interpolate", loc, m, pv.handle, S, zv.handle, vals.handle, grads.handle if grad else None, iptr(elem))
+    out = [vals.to_numpy().reshape(m, S)]
+    if grad:
+        out.append(grads.to_numpy().reshape(m, S, dim))
+    if T is not None:      # columns are (snapshot, state variable)
+        out[0] = out[0].reshape(m, T, S // T).transpose(1, 0, 2)
+        if grad:
+            out[1] = out[1].reshape(m, T, S // T, dim).transpose(1, 0, 2, 3)
+    if return_element:
+        out.append(elem)
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def sample_grid(obj, shape, bounds=None, z=None):
+    """Sample on a regular grid (what a plot needs): `shape` = points per axis, slowest axis first -- (ny, nx) in 2-D --,
+    `bounds` = (lower corner, upper corner), default the bounding box of the nodes.  Returns X (*shape, dim) and the values
+    (*shape, S) -- (T, *shape, S) for a ParabolicSOL --, NaN outside the mesh."""
+    geometry = obj if isinstance(obj, Geometry) else obj.geometry
+    dim = geometry.discretization["dim"]
+    shape = (int(shape),) if np.isscalar(shape) else tuple(int(v) for v in shape)
+    if len(shape) != dim or min(shape) < 1:
+        raise ValueError("sample_grid: shape must give one positive point count per axis (%d)" % dim)
+    if bounds is None:
+        x = np.asarray(_to_cpu_array(geometry.x)).reshape(-1, dim)
+        lo, hi = x.min(axis=0), x.max(axis=0)
+    else:
+        lo, hi = (f64(np.asarray(b)).reshape(dim) for b in bounds)
+    axes = [np.linspace(lo[a], hi[a], shape[dim - 1 - a]) for a in range(dim)]
+    mesh = np.meshgrid(*axes[::-1], indexing="ij")                      # slowest axis first
+    X = np.stack(mesh[::-1], axis=-1)
+    vals = interpolate(obj, X.reshape(-1, dim), z=z)
+    if vals.ndim == 3:
+        return X, vals.reshape((vals.shape[0],) + shape + (vals.shape[-1],))
+    return X, vals.reshape(shape + (vals.shape[-1],))
 
 
 def mpi_to_native(obj):

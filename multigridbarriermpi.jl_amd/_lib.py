@@ -121,6 +121,10 @@ PROTOTYPES = {
     "mgb_amg_pcg_solve_linear": [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, c_int_p],
     "mgb_amg_mg_info": [H, C.c_int, c_int_p],
     "mgb_amg_time_mg_kernels": [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p],
+    "mgb_locator_create": [H, H, C.POINTER(H)],
+    "mgb_locator_destroy": [H],
+    "mgb_interpolate": [H, C.c_int, H, C.c_int, H, H, H, c_i32_p],
+    "mgb_geo_interpolate_host": [H, C.c_int, c_dbl_p, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_i32_p],
     "mgb_plan_prolongation": [H, H, c_int_p, c_int_p, c_int_p, c_i32_p, c_i32_p, c_dbl_p],
     "mgb_amg_solve": [H, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int],
     "mgb_amg_sol_info": [H, c_int_p, c_dbl_p, c_dbl_p, c_ll_p],

@@ -8,6 +8,7 @@
 #include <thread>
 
 #include "amg.hpp"
+#include "interp.hpp"
 
 using namespace mgb;
 
@@ -37,6 +38,12 @@ struct mgb_amg_s {
   bool pcg = false;
   bool upstream_stop = false;
   bool exact_centering = true;
+};
+struct mgb_locator_s {
+  mgb_ctx_s* ctx;
+  interp::Locator loc;
+  DevBuf<int> cellptr, cellelem;
+  DevBuf<double> x;
 };
 struct mgb_plan_s {
   LevelPlan plan;
@@ -1069,6 +1076,62 @@ int mgb_amg_time_kernels(mgb_amg a, int level, int reps, int nrot, double* ms8, 
                           k.apply_el};      // last slot: 1 if apply_D (slot 0) ran through the element-local view
     std::copy(ms, ms + 8, ms8);
     std::copy(by, by + 8, bytes8);
+  });
+}
+
+// ---- evaluation at arbitrary points (interp.hpp / interp.hip)
+int mgb_locator_create(mgb_ctx ctx, mgb_geo g, mgb_locator* out) {
+  return guard([&] {
+    need(ctx && g && out, "locator_create: null argument");
+    interp::Locator loc = interp::build_locator(g->g);
+    hip_check(hipSetDevice(ctx->ctx.device), "hipSetDevice");
+    auto* l = new mgb_locator_s{ctx, std::move(loc), {}, {}, {}};
+    try {
+      l->cellptr.upload(l->loc.cellptr.data(), l->loc.cellptr.size());
+      l->cellelem.upload(l->loc.cellelem.data(), l->loc.cellelem.size());
+      l->x.upload(g->g.x.data(), g->g.x.size());
+    } catch (...) {
+      delete l;
+      throw;
+    }
+    *out = l;
+  });
+}
+int mgb_locator_destroy(mgb_locator loc) {
+  return guard([&] { delete loc; });
+}
+int mgb_interpolate(mgb_locator loc, int m, mgb_vec pts, int S, mgb_vec z, mgb_vec vals, mgb_vec grads, int32_t* elem_host) {
+  return guard([&] {
+    need(loc && pts && z && vals, "interpolate: null argument");
+    need(m >= 0 && S >= 1, "interpolate: m must be >= 0 and S >= 1");
+    const interp::Locator& L = loc->loc;
+    need(pts->n == (long long)m * L.dim, "interpolate: pts must hold m x dim values");
+    need(z->n == (long long)L.n * S, "interpolate: z must hold n x S values");
+    need(vals->n == (long long)m * S, "interpolate: vals must hold m x S values");
+    need(!grads || grads->n == (long long)m * S * L.dim, "interpolate: grads must hold m x S x dim values");
+    need(pts->ctx == loc->ctx && z->ctx == loc->ctx && vals->ctx == loc->ctx && (!grads || grads->ctx == loc->ctx),
+         "interpolate: vectors of another context");
+    if (m == 0) return;
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    DevBuf<int> elem;
+    if (elem_host) elem.alloc(m);
+    interp::launch_interpolate(st, L.view(loc->cellptr.p, loc->cellelem.p, loc->x.p), L.dim, L.k, m, pts->buf.p, S, z->buf.p,
+                               vals->buf.p, grads ? grads->buf.p : nullptr, elem.p);
+    hip_check(hipGetLastError(), "interpolate launch");
+    if (elem_host) {
+      hip_check(hipStreamSynchronize(st), "sync interpolate");
+      elem.download(elem_host, m);
+    }
+  });
+}
+int mgb_geo_interpolate_host(mgb_geo g, int m, const double* pts, int S, const double* z, double* vals, double* grads,
+                             int32_t* elem) {
+  return guard([&] {
+    need(g && m >= 0 && S >= 1, "geo_interpolate_host: null geometry, m < 0 or S < 1");
+    need(m == 0 || (pts && z && vals), "geo_interpolate_host: null array");
+    const interp::Locator loc = interp::build_locator(g->g);
+    interp::interpolate_host(loc, g->g.x.data(), m, pts, S, z, vals, grads, elem);
   });
 }
 
