@@ -307,7 +307,8 @@ int mgb_amg_mg_info(mgb_amg a, int top, int* coarsest);
  * [-tau, 1 + tau] (1-D, 3-D); of all elements containing a point the lowest index wins; a point in no element or with a
  * non-finite coordinate is outside: every output column NaN, element -1, no error.
  * The locator uses x, dim, block and n of the geometry alone: a uniform bin grid over the bounding box (about one cell per
- * element, CSR cell -> ascending elements), built on the host, resident on the device together with x. */
+ * element, CSR cell -> ascending elements), built on the host, resident on the device together with x and the quadrature
+ * weights w (mgb_field_norms). */
 int mgb_locator_create(mgb_ctx ctx, mgb_geo g, mgb_locator* out);
 int mgb_locator_destroy(mgb_locator loc);
 /* one launch on the context stream, one thread per point: pts m x dim, z n x S, vals m x S, grads (nullable) m x S x dim, all
@@ -318,6 +319,43 @@ int mgb_interpolate(mgb_locator loc, int m, mgb_vec pts, int S, mgb_vec z, mgb_v
 /* host restatement (no context, no GPU): the same bins, containment rule and bases on host arrays */
 int mgb_geo_interpolate_host(mgb_geo g, int m, const double* pts, int S, const double* z, double* vals,
                              double* grads_or_null, int32_t* elem_or_null);
+
+/* ---- norms and errors of nodal fields by the nodal quadrature rule (the convergence study after a solve) ---------------- *
+ * A field is an n x S row-major nodal matrix on a geometry whose elements are its row blocks, as for mgb_interpolate; node i
+ * belongs to element e = i / block; integrals are the nodal rule of that geometry, int phi ~ sum_i w_i phi(x_i).  At node i a
+ * field is evaluated in its OWN element e, never in a neighbour sharing the point: the value is z[i], the gradient is the
+ * physical gradient of e's nodal basis at x_i (what the dx / dy / dz operator rows give).
+ * The difference field d = a - r and its gradient are taken at every node of a's geometry; r is exactly one of
+ *   nothing:                      d = a, the norms of a itself;
+ *   ref_vals (n x S) [, ref_grads (n x S x dim)]:  d_i = a_i - ref_vals_i; with ref_grads grad d_i = grad a(x_i) - ref_grads_i
+ *                                 (the exact gradient of an exact solution), without it the element gradient of the nodal
+ *                                 field a - ref_vals;
+ *   other + z_other (n_other x S): a field on another geometry of the same dimension and element degree, evaluated at x_i by
+ *                                 the other mesh's polynomial.  Its element is the one that CONTAINS the nudged point
+ *                                 x_i + theta (c_e - x_i), theta = 2^-20, c_e = mean of the nodes of i's own element (the
+ *                                 containment rule above: tau, lowest index wins); that element's polynomial and gradient
+ *                                 are then evaluated at x_i itself.  The nudge decides on which side of a coarse edge a
+ *                                 fine node takes the (discontinuous) coarse gradient: the side its own element lies on.  A
+ *                                 node whose nudged point lies in no element of the other mesh contributes nothing to any
+ *                                 sum or maximum and is counted in `outside`.  other == loc is allowed.
+ * Output: for every column s one row of MGB_NORM_COLS doubles
+ *   [0] sum w_i d_i (signed)  [1] sum w_i |d_i|^q  [2] sum w_i |grad d_i|_2^q  [3] max_i |d_i|  [4] max_i |grad d_i|_2
+ * -- the raw power sums, not their roots.  q: any finite real >= 1 (q = 2 and q = 1 take no pow; |d| = 0 contributes 0).
+ * A non-finite d_i or grad d_i makes the affected entries of THAT column non-finite (a NaN term makes the sum and the
+ * maximum NaN, it is never dropped); other columns are unaffected, bit for bit.
+ * MGB_E_ARG: a null loc, z or out; S < 1; q not finite or < 1; a vector whose length is not exactly what the shapes above
+ * say; ref_grads without ref_vals; both ref_vals and other; other without z_other or z_other without other; other of another
+ * context, dimension or element degree. */
+#define MGB_NORM_COLS 5
+/* two launches on the context stream (partial rows per workgroup and column, then one workgroup that combines them in
+ * ascending workgroup order: no atomics, bitwise reproducible); the results are copied to the host and the call waits */
+int mgb_field_norms(mgb_locator loc, int S, mgb_vec z, double q, mgb_vec ref_vals_or_null, mgb_vec ref_grads_or_null,
+                    mgb_locator other_or_null, mgb_vec z_other_or_null, double* out_host /* S x MGB_NORM_COLS */,
+                    long long* outside_host_or_null);
+/* host restatement (no context, no GPU): the same per-node routine, summed serially in ascending node order */
+int mgb_geo_field_norms_host(mgb_geo g, int S, const double* z, double q, const double* ref_vals_or_null,
+                             const double* ref_grads_or_null, mgb_geo other_or_null, const double* z_other_or_null,
+                             double* out, long long* outside_or_null);
 
 /* ---- host-only symbolic helpers (no GPU needed; used by the CPU test-suite) ----------------- */
 

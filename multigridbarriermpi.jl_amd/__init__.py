@@ -36,7 +36,7 @@ __all__ = [
     "mpi_to_native", "amgb", "Geometry", "AMGBSOL", "HPCVector", "HPCMatrix", "HPCSparseMatrix",
     "backend_hip", "amgb_zeros", "amgb_all_isfinite", "amgb_diag", "amgb_blockdiag", "map_rows", "map_rows_gpu",
     "_raw_array", "_to_cpu_array", "MGBError", "device_count", "AMG", "amg", "hcat", "BarrierFn", "barrier_functions",
-    "interpolate", "sample_grid",
+    "interpolate", "sample_grid", "norms", "error", "convergence", "FieldNorms", "Convergence",
 ]
 
 
@@ -1470,6 +1470,24 @@ def _locator_of(geometry: Geometry):
     return geometry._locator, backend
 
 
+def _nodal_values(geometry: Geometry, z, backend, who):
+    """z as a device vector of n x S row-major nodal values of `geometry`, and S."""
+    if z is None:
+        raise ValueError("%s: z= is required with a Geometry" % who)
+    n = len(geometry.w)
+    if isinstance(z, HPCMatrix) and z.backend is backend:
+        zv, zshape = z._v, z.shape
+    elif isinstance(z, HPCVector) and z.backend is backend:
+        zv, zshape = z, (len(z), 1)
+    else:
+        za = f64(np.asarray(_to_cpu_array(z)))
+        za = za.reshape(za.shape[0], -1) if za.ndim else za.reshape(1, 1)
+        zv, zshape = HPCVector(za, backend), za.shape
+    if zshape[0] != n or zshape[1] < 1:
+        raise ValueError("%s: z must have one row per node of the geometry (%d), got shape %r" % (who, n, tuple(zshape)))
+    return zv, int(zshape[1])
+
+
 def interpolate(obj, points, z=None, grad=False, return_element=False):
     """Evaluate nodal values at arbitrary points on the device (csrc/interp.hip; contract in include/mgb_hip.h and DESIGN.md
     section 4d).  `obj`: an AMGBSOL (its z and geometry), a ParabolicSOL (all snapshots stacked column-wise, ONE launch,
@@ -1489,20 +1507,8 @@ def interpolate(obj, points, z=None, grad=False, return_element=False):
     else:
         raise TypeError("interpolate: expected an AMGBSOL, a ParabolicSOL or a Geometry")
     loc, backend = _locator_of(geometry)
-    if z is None:
-        raise ValueError("interpolate: z= is required with a Geometry")
-    n, dim = len(geometry.w), geometry.discretization["dim"]
-    if isinstance(z, HPCMatrix) and z.backend is backend:
-        zv, zshape = z._v, z.shape
-    elif isinstance(z, HPCVector) and z.backend is backend:
-        zv, zshape = z, (len(z), 1)
-    else:
-        za = f64(np.asarray(_to_cpu_array(z)))
-        za = za.reshape(za.shape[0], -1) if za.ndim else za.reshape(1, 1)
-        zv, zshape = HPCVector(za, backend), za.shape
-    if zshape[0] != n or zshape[1] < 1:
-        raise ValueError("interpolate: z must have one row per node of the geometry (%d), got shape %r" % (n, tuple(zshape)))
-    S = int(zshape[1])
+    dim = geometry.discretization["dim"]
+    zv, S = _nodal_values(geometry, z, backend, "interpolate")
     pts = f64(np.asarray(points))
     if pts.ndim == 1 and dim == 1:
         pts = pts.reshape(-1, 1)
@@ -1547,6 +1553,148 @@ def sample_grid(obj, shape, bounds=None, z=None):
     if vals.ndim == 3:
         return X, vals.reshape((vals.shape[0],) + shape + (vals.shape[-1],))
     return X, vals.reshape(shape + (vals.shape[-1],))
+
+
+# --------------------------------------------------------------------------- norms and errors of solutions
+
+
+@dataclass
+class FieldNorms:
+    """Result of norms() / error(): (S,) arrays by the nodal quadrature rule -- `integral` = sum w d (signed), `lq` =
+    (sum w |d|^q)^(1/q), `w1q` = (sum w |grad d|_2^q)^(1/q), `max` = max |d|, `gradmax` = max |grad d|_2 -- the raw `sums`
+    (S x 5, the columns of mgb_field_norms), `q`, and `outside`: nodes that lie in no element of the other mesh."""
+    integral: np.ndarray
+    lq: np.ndarray
+    w1q: np.ndarray
+    max: np.ndarray
+    gradmax: np.ndarray
+    sums: np.ndarray
+    q: float
+    outside: int = 0
+
+
+def _field_norms(geometry, zv, S, q, ref_vals=None, ref_grads=None, other=None, z_other=None, sign=1.0) -> FieldNorms:
+    loc, _ = _locator_of(geometry)
+    q = float(q)
+    if not (math.isfinite(q) and q >= 1.0):
+        raise ValueError("norms: q must be a finite real >= 1, got %r" % (q,))
+    sums = np.empty((S, 5))
+    outside = C.c_longlong(0)
+    call("mgb_field_norms", loc, S, zv.handle, q, ref_vals.handle if ref_vals is not None else None,
+         ref_grads.handle if ref_grads is not None else None, other, z_other.handle if z_other is not None else None,
+         dptr(sums), C.byref(outside))
+    sums[:, 0] *= sign
+    return FieldNorms(sums[:, 0].copy(), sums[:, 1] ** (1.0 / q), sums[:, 2] ** (1.0 / q), sums[:, 3].copy(), sums[:, 4].copy(),
+                      sums, q, int(outside.value))
+
+
+def _field_of(obj, who, z=None):
+    """(geometry, z) of an AMGBSOL, a (Geometry, z) pair or a Geometry with z=."""
+    if isinstance(obj, AMGBSOL):
+        return obj.geometry, (obj.z if z is None else z)
+    if isinstance(obj, Geometry):
+        return obj, z
+    if isinstance(obj, tuple) and len(obj) == 2 and isinstance(obj[0], Geometry):
+        return obj
+    raise TypeError("%s: expected an AMGBSOL or a (Geometry, z) pair" % who)
+
+
+def norms(obj, z=None, q=2.0) -> FieldNorms:
+    """L^q norm, W^{1,q} seminorm, integral and maxima of nodal values by the nodal quadrature rule, on the device
+    (csrc/norms.hip; contract in include/mgb_hip.h and DESIGN.md section 4e).  `obj`, `z`: as for interpolate -- an AMGBSOL,
+    or a device Geometry with `z=` an (n,) / (n, S) array, HPCVector or HPCMatrix.  One entry per column."""
+    geometry, z = _field_of(obj, "norms", z)
+    _, backend = _locator_of(geometry)
+    zv, S = _nodal_values(geometry, z, backend, "norms")
+    return _field_norms(geometry, zv, S, q)
+
+
+def error(a, b, q=2.0, grad=None, on=None, allow_outside=False) -> FieldNorms:
+    """Norms of the difference a - b (csrc/norms.hip).  `a`: an AMGBSOL or a (Geometry, z) pair.  `b`: a callable
+    x_row -> S values evaluated on the host at the nodes (like `f` and `g` of amgb), with `grad=` a callable x_row -> (S, dim)
+    for the exact gradient; or an (n, S) array of nodal values (`grad=` an (n, S, dim) array); or another AMGBSOL /
+    (Geometry, z) pair on a different mesh of the same dimension.  Without `grad=` the gradient of the reference is the element
+    gradient of its nodal values.  For two meshes the quadrature runs on the one with more nodes (`on="a"` / `on="b"`
+    overrides) and the other field is evaluated there by its own polynomials; the signed integral is always that of a - b;
+    nodes outside the other mesh are counted in `outside` and raise ValueError unless allow_outside."""
+    ga, za = _field_of(a, "error")
+    _, backend = _locator_of(ga)
+    zv, S = _nodal_values(ga, za, backend, "error")
+    n, dim = len(ga.w), ga.discretization["dim"]
+    if on not in (None, "a", "b"):
+        raise ValueError("error: on must be None, 'a' or 'b'")
+    if isinstance(b, AMGBSOL) or (isinstance(b, tuple) and len(b) == 2 and isinstance(b[0], Geometry)):
+        if grad is not None:
+            raise ValueError("error: grad= goes with a callable or an array, not with a second mesh")
+        gb, zb = _field_of(b, "error")
+        _, backend_b = _locator_of(gb)
+        if backend_b is not backend:
+            raise ValueError("error: the two fields live on different backends")
+        if gb.discretization["dim"] != dim:
+            raise ValueError("error: the two meshes have different dimensions (%d and %d)" % (dim, gb.discretization["dim"]))
+        if gb.discretization.get("k") != ga.discretization.get("k"):
+            raise ValueError("error: the two meshes have elements of different degrees")
+        zbv, Sb = _nodal_values(gb, zb, backend, "error")
+        if Sb != S:
+            raise ValueError("error: a has %d columns, b has %d" % (S, Sb))
+        on_a = len(gb.w) <= n if on is None else on == "a"
+        if on_a:
+            res = _field_norms(ga, zv, S, q, other=_locator_of(gb)[0], z_other=zbv)
+        else:
+            res = _field_norms(gb, zbv, S, q, other=_locator_of(ga)[0], z_other=zv, sign=-1.0)
+    else:
+        if on == "b":
+            raise ValueError("error: on='b' needs a second mesh")
+        x = np.asarray(_to_cpu_array(ga.x)).reshape(n, dim)
+        rows = lambda f, shape: np.array([np.asarray(f(xi), dtype=np.float64).reshape(shape) for xi in x])
+        rv = rows(b, (-1,)) if callable(b) else f64(np.asarray(_to_cpu_array(b)))
+        rv = rv.reshape(rv.shape[0], -1) if rv.ndim else rv.reshape(1, 1)
+        if rv.shape != (n, S):
+            raise ValueError("error: b must give %d values per node on %d nodes, got shape %r" % (S, n, rv.shape))
+        rg = None
+        if grad is not None:
+            rg = rows(grad, (-1, dim)) if callable(grad) else f64(np.asarray(_to_cpu_array(grad)))
+            if rg.size != n * S * dim or (rg.ndim == 3 and rg.shape != (n, S, dim)):
+                raise ValueError("error: grad must give (%d, %d) values per node on %d nodes" % (S, dim, n))
+            rg = HPCVector(f64(rg).reshape(-1), backend)
+        res = _field_norms(ga, zv, S, q, ref_vals=HPCVector(f64(rv).reshape(-1), backend), ref_grads=rg)
+    if res.outside > 0 and not allow_outside:
+        raise ValueError("error: %d quadrature nodes lie outside the other mesh (allow_outside=True skips them)" % res.outside)
+    return res
+
+
+@dataclass
+class Convergence:
+    """Result of convergence(): `errors` (one FieldNorms per level), the stacked `lq`, `w1q`, `max`, `gradmax` (levels x S) and
+    the observed orders log2(e_l / e_{l+1}) of each ((levels - 1) x S)."""
+    errors: list
+    lq: np.ndarray
+    w1q: np.ndarray
+    max: np.ndarray
+    gradmax: np.ndarray
+    order_lq: np.ndarray
+    order_w1q: np.ndarray
+    order_max: np.ndarray
+    order_gradmax: np.ndarray
+
+
+def convergence(sols, exact=None, grad=None, q=2.0) -> Convergence:
+    """Errors of the solutions `sols` (coarse to fine, each mesh the refinement of the one before) against `exact` (and its
+    gradient `grad`: callables as for error), or against the finest solution when `exact` is None, and the observed orders
+    log2(e_l / e_{l+1}).  Host glue around error()."""
+    sols = list(sols)
+    if exact is None:
+        if len(sols) < 2:
+            raise ValueError("convergence: at least two solutions are needed without an exact one")
+        errs = [error(s, sols[-1], q=q) for s in sols[:-1]]
+    else:
+        errs = [error(s, exact, q=q, grad=grad) for s in sols]
+    stack = lambda name: np.array([getattr(e, name) for e in errs]).reshape(len(errs), -1)
+    cols = {name: stack(name) for name in ("lq", "w1q", "max", "gradmax")}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        orders = {name: np.log2(v[:-1] / v[1:]) for name, v in cols.items()}
+    return Convergence(errs, cols["lq"], cols["w1q"], cols["max"], cols["gradmax"], orders["lq"], orders["w1q"], orders["max"],
+                       orders["gradmax"])
 
 
 def mpi_to_native(obj):

@@ -9,6 +9,7 @@
 
 #include "amg.hpp"
 #include "interp.hpp"
+#include "norms.hpp"
 
 using namespace mgb;
 
@@ -43,7 +44,9 @@ struct mgb_locator_s {
   mgb_ctx_s* ctx;
   interp::Locator loc;
   DevBuf<int> cellptr, cellelem;
-  DevBuf<double> x;
+  DevBuf<double> x, w;
+  DevBuf<double> norm_scratch;      // mgb_field_norms: partials and results, grown on demand
+  DevBuf<long long> norm_counts;
 };
 struct mgb_plan_s {
   LevelPlan plan;
@@ -1085,11 +1088,13 @@ int mgb_locator_create(mgb_ctx ctx, mgb_geo g, mgb_locator* out) {
     need(ctx && g && out, "locator_create: null argument");
     interp::Locator loc = interp::build_locator(g->g);
     hip_check(hipSetDevice(ctx->ctx.device), "hipSetDevice");
-    auto* l = new mgb_locator_s{ctx, std::move(loc), {}, {}, {}};
+    need(g->g.w.size() == (size_t)g->g.n, "locator_create: the geometry must carry one weight per node");
+    auto* l = new mgb_locator_s{ctx, std::move(loc), {}, {}, {}, {}, {}, {}};
     try {
       l->cellptr.upload(l->loc.cellptr.data(), l->loc.cellptr.size());
       l->cellelem.upload(l->loc.cellelem.data(), l->loc.cellelem.size());
       l->x.upload(g->g.x.data(), g->g.x.size());
+      l->w.upload(g->g.w.data(), g->g.w.size());
     } catch (...) {
       delete l;
       throw;
@@ -1132,6 +1137,93 @@ int mgb_geo_interpolate_host(mgb_geo g, int m, const double* pts, int S, const d
     need(m == 0 || (pts && z && vals), "geo_interpolate_host: null array");
     const interp::Locator loc = interp::build_locator(g->g);
     interp::interpolate_host(loc, g->g.x.data(), m, pts, S, z, vals, grads, elem);
+  });
+}
+
+// ---- norms and errors by the nodal quadrature rule (norms.hpp / norms.hip)
+namespace {
+bool good_q(double q) { return q >= 1.0 && (q - q) == 0.0; }
+}  // namespace
+int mgb_field_norms(mgb_locator loc, int S, mgb_vec z, double q, mgb_vec ref_vals, mgb_vec ref_grads, mgb_locator other,
+                    mgb_vec z_other, double* out_host, long long* outside_host) {
+  return guard([&] {
+    need(loc && z && out_host, "field_norms: null argument");
+    need(S >= 1, "field_norms: S must be >= 1");
+    need(good_q(q), "field_norms: q must be finite and >= 1");
+    const interp::Locator& L = loc->loc;
+    need(z->n == (long long)L.n * S, "field_norms: z must hold n x S values");
+    need(!ref_grads || ref_vals, "field_norms: ref_grads without ref_vals");
+    need(!(ref_vals && other), "field_norms: both ref_vals and another mesh");
+    need((other != nullptr) == (z_other != nullptr), "field_norms: other and z_other come together");
+    need(!ref_vals || ref_vals->n == (long long)L.n * S, "field_norms: ref_vals must hold n x S values");
+    need(!ref_grads || ref_grads->n == (long long)L.n * S * L.dim, "field_norms: ref_grads must hold n x S x dim values");
+    need(z->ctx == loc->ctx && (!ref_vals || ref_vals->ctx == loc->ctx) && (!ref_grads || ref_grads->ctx == loc->ctx),
+         "field_norms: vectors of another context");
+    if (other) {
+      need(other->ctx == loc->ctx && z_other->ctx == loc->ctx, "field_norms: the other mesh belongs to another context");
+      need(other->loc.dim == L.dim, "field_norms: the other mesh has another dimension");
+      need(other->loc.k == L.k, "field_norms: the other mesh has elements of another degree");
+      need(z_other->n == (long long)other->loc.n * S, "field_norms: z_other must hold n_other x S values");
+    }
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const size_t nd = norms::scratch_doubles(L.n, S), nc = norms::scratch_counts(L.n);
+    if (loc->norm_scratch.n < nd) loc->norm_scratch.alloc(nd);
+    if (loc->norm_counts.n < nc) loc->norm_counts.alloc(nc);
+    norms::Args A;
+    A.own = L.view(loc->cellptr.p, loc->cellelem.p, loc->x.p);
+    A.w = loc->w.p;
+    A.z = z->buf.p;
+    A.ref_vals = ref_vals ? ref_vals->buf.p : nullptr;
+    A.ref_grads = ref_grads ? ref_grads->buf.p : nullptr;
+    if (other) {
+      A.other = other->loc.view(other->cellptr.p, other->cellelem.p, other->x.p);
+      A.z_other = z_other->buf.p;
+      A.cross = true;
+    }
+    A.n = L.n;
+    A.S = S;
+    A.q = q;
+    norms::launch_field_norms(st, L.dim, L.k, A, loc->norm_scratch.p, loc->norm_counts.p);
+    hip_check(hipGetLastError(), "field_norms launch");
+    hip_check(hipStreamSynchronize(st), "sync field_norms");
+    const size_t nwg = (size_t)norms::workgroups(L.n);
+    hip_check(hipMemcpy(out_host, loc->norm_scratch.p + nwg * S * norms::kCols, (size_t)S * norms::kCols * sizeof(double),
+                        hipMemcpyDeviceToHost), "D2H");
+    if (outside_host) hip_check(hipMemcpy(outside_host, loc->norm_counts.p + nwg, sizeof(long long), hipMemcpyDeviceToHost), "D2H");
+  });
+}
+int mgb_geo_field_norms_host(mgb_geo g, int S, const double* z, double q, const double* ref_vals, const double* ref_grads,
+                             mgb_geo other, const double* z_other, double* out, long long* outside) {
+  return guard([&] {
+    need(g && z && out, "geo_field_norms_host: null argument");
+    need(S >= 1, "geo_field_norms_host: S must be >= 1");
+    need(good_q(q), "geo_field_norms_host: q must be finite and >= 1");
+    need(!ref_grads || ref_vals, "geo_field_norms_host: ref_grads without ref_vals");
+    need(!(ref_vals && other), "geo_field_norms_host: both ref_vals and another mesh");
+    need((other != nullptr) == (z_other != nullptr), "geo_field_norms_host: other and z_other come together");
+    need(g->g.w.size() == (size_t)g->g.n, "geo_field_norms_host: the geometry must carry one weight per node");
+    const interp::Locator L = interp::build_locator(g->g);
+    interp::Locator Lo;
+    if (other && other != g) Lo = interp::build_locator(other->g);
+    const interp::Locator& O = other && other != g ? Lo : L;
+    norms::Args A;
+    A.own = L.view(L.cellptr.data(), L.cellelem.data(), g->g.x.data());
+    A.w = g->g.w.data();
+    A.z = z;
+    A.ref_vals = ref_vals;
+    A.ref_grads = ref_grads;
+    if (other) {
+      need(O.dim == L.dim, "geo_field_norms_host: the other mesh has another dimension");
+      need(O.k == L.k, "geo_field_norms_host: the other mesh has elements of another degree");
+      A.other = O.view(O.cellptr.data(), O.cellelem.data(), other->g.x.data());
+      A.z_other = z_other;
+      A.cross = true;
+    }
+    A.n = L.n;
+    A.S = S;
+    A.q = q;
+    norms::field_norms_host(L.dim, L.k, A, out, outside);
   });
 }
 

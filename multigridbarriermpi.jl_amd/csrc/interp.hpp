@@ -1,6 +1,7 @@
 // Evaluation of a nodal field at arbitrary points: inverse element maps, nodal bases, the containment
 // rule and the bin grid that finds an element, written ONCE.  The gfx950 kernel (interp.hip) and the host restatement
-// (mgb_geo_interpolate_host) both run eval_point below, the way kernels_tpl.hpp is shared.
+// (mgb_geo_interpolate_host) both run eval_point below, the way kernels_tpl.hpp is shared; norms.hpp builds on the same
+// pieces (ElemBasis, find_element).
 //   1-D: block 2 (left, right), P1.          2-D: block 7 (v1 v2 v3 m12 m23 m31 centroid, geometry.cpp), P2 + cubic bubble.
 //   3-D: block (k+1)^3, k = 1..3, equispaced tensor nodes (x fastest) on the axis-aligned box of the first and last row.
 // Containment (public contract): reference coordinates, tau = 1e-12; inside when min(lambda) >= -tau (2-D) or every
@@ -124,13 +125,95 @@ MGB_HD void lagrange(double xi, double* v, double* d) {
   }
 }
 
-// One query point: find the cell, walk its ascending candidate list, take the first element that contains p, evaluate the
-// basis once and loop over the S columns of the row-major n x S matrix z (the block * S values of an element are one
-// contiguous run).  vals: S values; grads (nullable): S x DIM; elem (nullable): one int.  K = degree of the tensor elements
-// (unused in 2-D).
+// The basis of ONE element at ONE point, evaluated once and applied to any number of columns: init() takes the reference
+// coordinates r of the point in element e (ref_coords), eval() one column s of the element's block * S contiguous nodal
+// values ze (row-major n x S) and gives the value and the physical gradient g[DIM].  SUB: the nodal field is ze - sub, the
+// difference taken node by node before the sums (norms.hpp).  K = degree of the tensor elements (unused in 2-D).
 template <int DIM, int K>
-MGB_HD void eval_point(const BinsView& B, const double* p, int S, const double* z, double* vals, double* grads,
-                       int32_t* elem) {
+struct ElemBasis {
+  static constexpr int M1 = K + 1;
+  double bv[DIM][M1], bd[DIM][M1], ih[DIM];
+  MGB_HD void init(const double* x, int block, int e, const double* r) {
+    const double* a = x + (size_t)e * block * DIM;
+    const double* b = a + (size_t)(block - 1) * DIM;
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) {
+      lagrange<K>(r[d], bv[d], bd[d]);
+      ih[d] = 1.0 / (b[d] - a[d]);
+    }
+  }
+  template <bool SUB>
+  MGB_HD void eval(const double* ze, const double* sub, int S, int s, double& val, double* g) const {
+    if constexpr (DIM == 1) {
+      double acc = 0.0, g0 = 0.0;
+#pragma unroll
+      for (int i = 0; i < M1; ++i) {
+        double zz = ze[(size_t)i * S + s];
+        if constexpr (SUB) zz -= sub[(size_t)i * S + s];
+        acc += bv[0][i] * zz;
+        g0 += bd[0][i] * zz;
+      }
+      val = acc;
+      g[0] = g0 * ih[0];
+    } else {
+      double acc = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+#pragma unroll
+      for (int m = 0; m < M1; ++m)
+#pragma unroll
+        for (int j = 0; j < M1; ++j) {
+          double line = 0.0, dline = 0.0;      // the x-line of nodes (., j, m)
+#pragma unroll
+          for (int i = 0; i < M1; ++i) {
+            double zz = ze[(size_t)(i + M1 * (j + M1 * m)) * S + s];
+            if constexpr (SUB) zz -= sub[(size_t)(i + M1 * (j + M1 * m)) * S + s];
+            line += bv[0][i] * zz;
+            dline += bd[0][i] * zz;
+          }
+          acc += line * (bv[1][j] * bv[2][m]);
+          g0 += dline * (bv[1][j] * bv[2][m]);
+          g1 += line * (bd[1][j] * bv[2][m]);
+          g2 += line * (bv[1][j] * bd[2][m]);
+        }
+      val = acc;
+      g[0] = g0 * ih[0];
+      g[1] = g1 * ih[1];
+      g[2] = g2 * ih[2];
+    }
+  }
+};
+
+template <int K>
+struct ElemBasis<2, K> {
+  double N[7], Nx[7], Ny[7], xx, ex, xy, ey;
+  MGB_HD void init(const double* x, int, int e, const double* r) {
+    tri_basis(r[0], r[1], N, Nx, Ny);
+    const double* v = x + (size_t)e * 14;
+    const double ax = v[2] - v[0], ay = v[3] - v[1], bx = v[4] - v[0], by = v[5] - v[1];
+    const double idet = 1.0 / (ax * by - ay * bx);
+    // physical gradient = T^-T (reference gradient), T = [v2 - v1, v3 - v1]
+    xx = by * idet, ex = -ay * idet, xy = -bx * idet, ey = ax * idet;
+  }
+  template <bool SUB>
+  MGB_HD void eval(const double* ze, const double* sub, int S, int s, double& val, double* g) const {
+    double acc = 0.0, g0 = 0.0, g1 = 0.0;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      double zz = ze[(size_t)j * S + s];
+      if constexpr (SUB) zz -= sub[(size_t)j * S + s];
+      acc += N[j] * zz;
+      g0 += Nx[j] * zz;
+      g1 += Ny[j] * zz;
+    }
+    val = acc;
+    g[0] = g0 * xx + g1 * ex;
+    g[1] = g0 * xy + g1 * ey;
+  }
+};
+
+// Find the element of a point: the cell, then the ascending candidate list, the first element that contains p; -1 when no
+// element does or a coordinate is not finite.
+template <int DIM>
+MGB_HD int find_element(const BinsView& B, const double* p) {
   bool fin = true;
 #pragma unroll
   for (int d = 0; d < DIM; ++d) fin = fin & finite(p[d]);
@@ -149,6 +232,33 @@ MGB_HD void eval_point(const BinsView& B, const double* p, int S, const double* 
       found = ref_coords<DIM>(B.x, B.block, e, p, r) ? e : found;
     }
   }
+  return found;
+}
+
+// Evaluate the S columns of the row-major n x S matrix z and (grads non-null) their gradients in element e at point p: the
+// basis once, then the columns (the block * S values of an element are one contiguous run).  p need not lie inside e.
+template <int DIM, int K>
+MGB_HD void eval_in_element(const BinsView& B, int e, const double* p, int S, const double* z, double* vals, double* grads) {
+  double r[DIM];
+  ref_coords<DIM>(B.x, B.block, e, p, r);
+  ElemBasis<DIM, K> E;
+  E.init(B.x, B.block, e, r);
+  const double* ze = z + (size_t)e * B.block * S;
+  for (int s = 0; s < S; ++s) {
+    double g[DIM];
+    E.template eval<false>(ze, nullptr, S, s, vals[s], g);
+    if (grads) {
+#pragma unroll
+      for (int d = 0; d < DIM; ++d) grads[DIM * s + d] = g[d];
+    }
+  }
+}
+
+// One query point: find its element, evaluate there.  vals: S values; grads (nullable): S x DIM; elem (nullable): one int.
+template <int DIM, int K>
+MGB_HD void eval_point(const BinsView& B, const double* p, int S, const double* z, double* vals, double* grads,
+                       int32_t* elem) {
+  const int found = find_element<DIM>(B, p);
   if (elem) *elem = found;
   if (found < 0) {
     const double nan = std::numeric_limits<double>::quiet_NaN();
@@ -157,80 +267,7 @@ MGB_HD void eval_point(const BinsView& B, const double* p, int S, const double* 
       for (int s = 0; s < S * DIM; ++s) grads[s] = nan;
     return;
   }
-  double r[DIM];
-  ref_coords<DIM>(B.x, B.block, found, p, r);
-  const double* ze = z + (size_t)found * B.block * S;
-  if constexpr (DIM == 2) {
-    double N[7], Nx[7], Ny[7];
-    tri_basis(r[0], r[1], N, Nx, Ny);
-    const double* v = B.x + (size_t)found * 14;
-    const double ax = v[2] - v[0], ay = v[3] - v[1], bx = v[4] - v[0], by = v[5] - v[1];
-    const double idet = 1.0 / (ax * by - ay * bx);
-    // physical gradient = T^-T (reference gradient), T = [v2 - v1, v3 - v1]
-    const double xx = by * idet, ex = -ay * idet, xy = -bx * idet, ey = ax * idet;
-    for (int s = 0; s < S; ++s) {
-      double acc = 0.0, g0 = 0.0, g1 = 0.0;
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        const double zz = ze[(size_t)j * S + s];
-        acc += N[j] * zz;
-        g0 += Nx[j] * zz;
-        g1 += Ny[j] * zz;
-      }
-      vals[s] = acc;
-      if (grads) {
-        grads[2 * s] = g0 * xx + g1 * ex;
-        grads[2 * s + 1] = g0 * xy + g1 * ey;
-      }
-    }
-  } else {
-    constexpr int M1 = K + 1;
-    double bv[DIM][M1], bd[DIM][M1], ih[DIM];
-    const double* a = B.x + (size_t)found * B.block * DIM;
-    const double* b = a + (size_t)(B.block - 1) * DIM;
-#pragma unroll
-    for (int d = 0; d < DIM; ++d) {
-      lagrange<K>(r[d], bv[d], bd[d]);
-      ih[d] = 1.0 / (b[d] - a[d]);
-    }
-    for (int s = 0; s < S; ++s) {
-      if constexpr (DIM == 1) {
-        double acc = 0.0, g0 = 0.0;
-#pragma unroll
-        for (int i = 0; i < M1; ++i) {
-          const double zz = ze[(size_t)i * S + s];
-          acc += bv[0][i] * zz;
-          g0 += bd[0][i] * zz;
-        }
-        vals[s] = acc;
-        if (grads) grads[s] = g0 * ih[0];
-      } else {
-        double acc = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
-#pragma unroll
-        for (int m = 0; m < M1; ++m)
-#pragma unroll
-          for (int j = 0; j < M1; ++j) {
-            double line = 0.0, dline = 0.0;      // the x-line of nodes (., j, m)
-#pragma unroll
-            for (int i = 0; i < M1; ++i) {
-              const double zz = ze[(size_t)(i + M1 * (j + M1 * m)) * S + s];
-              line += bv[0][i] * zz;
-              dline += bd[0][i] * zz;
-            }
-            acc += line * (bv[1][j] * bv[2][m]);
-            g0 += dline * (bv[1][j] * bv[2][m]);
-            g1 += line * (bd[1][j] * bv[2][m]);
-            g2 += line * (bv[1][j] * bd[2][m]);
-          }
-        vals[s] = acc;
-        if (grads) {
-          grads[3 * s] = g0 * ih[0];
-          grads[3 * s + 1] = g1 * ih[1];
-          grads[3 * s + 2] = g2 * ih[2];
-        }
-      }
-    }
-  }
+  eval_in_element<DIM, K>(B, found, p, S, z, vals, grads);
 }
 
 // ---------------------------------------------------------------------------------------------------- host setup
