@@ -181,6 +181,14 @@ int mgb_amg_f1_f32(mgb_amg a, int level, const float* s, float t, float* g);
 int mgb_amg_f2_f32(mgb_amg a, int level, const float* s, float t, float* lower_vals);
 int mgb_amg_f1_template_f64(mgb_amg a, int level, const double* s, double t, double* g);
 int mgb_amg_f2_template_f64(mgb_amg a, int level, const double* s, double t, double* lower_vals);
+/* The line search's speculated objective on the buffers a solve uses (tests): the na (1..3) points x_a = s + alpha[a] * nstep
+ * (nstep nullable: x_a = s), with the fraction-to-the-boundary rule against phi_ref (n x nterms, nullable: no rule).
+ * mode 0: one fused launch for all points; 1: one fused launch per point; 2: the unfused path (x_a, apply_D, objective) per point.
+ * sums_host / sums_dev [2 na]: per point (sum w F, sum w <c, Dz>) as the kernels left them in pinned host memory and as
+ * copied from the device; s_out [na x N], dz [na x n x K], phi [na x n x nterms].  Single-GPU contexts. */
+int mgb_amg_trial_set(mgb_amg a, int level, const double* s, const double* nstep, int na, const double* alpha,
+                      const double* phi_ref, int mode, double* sums_host, double* sums_dev, double* s_out, double* dz,
+                      double* phi);
 int mgb_amg_chol_info(mgb_amg a, int level, int* split_world, double* exchange_doubles, int* launches);
 /* the launch chain of that factorisation (built now if needed; read-only: no numerics or launches change), in launch order:
  * *nlaunch launches, the kind code and the workgroup count of the first min(cap, *nlaunch).  Kind codes (GpuChol::Kind):

@@ -1014,6 +1014,30 @@ class AMG:
         call("mgb_amg_f2_template_f64", self.handle, l, dptr(s), float(t), dptr(vals))
         return vals
 
+    TRIAL_MODES = {"set": 0, "separate": 1, "unfused": 2}
+
+    def trial_set(self, l, s, nstep, alphas, phi_ref=None, mode="set"):
+        """The line search's objective at the points x_a = s + alphas[a] * nstep (1 to 3 of them; nstep None: x_a = s) on the
+        buffers a solve uses (tests).  phi_ref (n x nterms, None: no rule): the fraction-to-the-boundary rule against these cone
+        distances.  mode "set": one fused launch for all points; "separate": one fused launch per point; "unfused": x_a,
+        apply_D and the objective kernel per point.  Returns a dict: sums_host / sums (na x 2: sum w F, sum w <c, Dz>, as left in
+        pinned host memory / copied from the device), s_out (na x N), dz (na x n x K), phi (na x n x nterms)."""
+        s, alphas = f64(s), f64(np.asarray(alphas).reshape(-1))
+        nstep = None if nstep is None else f64(nstep)
+        N, na, nt = self.level_size(l)[0], alphas.size, len(self.cones)
+        if s.shape != (N,) or (nstep is not None and nstep.shape != (N,)):
+            raise ValueError("trial_set: s and nstep hold one value per unknown of the level")
+        if phi_ref is not None:
+            phi_ref = f64(phi_ref)
+            if phi_ref.shape != (self.n_local, nt):
+                raise ValueError("trial_set: phi_ref holds one value per node and barrier term")
+        out = dict(sums_host=np.empty((na, 2)), sums=np.empty((na, 2)), s_out=np.empty((na, N)),
+                   dz=np.empty((na, self.n_local, self.K)), phi=np.empty((na, self.n_local, nt)))
+        call("mgb_amg_trial_set", self.handle, int(l), dptr(s), dptr(nstep), na, dptr(alphas), dptr(phi_ref),
+             self.TRIAL_MODES[mode], dptr(out["sums_host"]), dptr(out["sums"]), dptr(out["s_out"]), dptr(out["dz"]),
+             dptr(out["phi"]))
+        return out
+
     def f2_hpc(self, l, s, t) -> HPCSparseMatrix:
         """The Newton matrix R'HR of level l as an HPCSparseMatrix (what `f2` returns in the reference and what
         test/test_newton_matrix_compare.jl:33-51 captures); `.local_block(rank, world)` gives the per-rank fields."""

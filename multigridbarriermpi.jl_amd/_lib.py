@@ -105,6 +105,8 @@ PROTOTYPES = {
     "mgb_amg_f2_f32": [H, C.c_int, c_flt_p, C.c_float, c_flt_p],
     "mgb_amg_f1_template_f64": [H, C.c_int, c_dbl_p, C.c_double, c_dbl_p],
     "mgb_amg_f2_template_f64": [H, C.c_int, c_dbl_p, C.c_double, c_dbl_p],
+    "mgb_amg_trial_set": [H, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p,
+                          c_dbl_p],
     "mgb_amg_solve_linear": [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_amg_solve_linear_gpu": [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_amg_set_solver": [H, C.c_int],

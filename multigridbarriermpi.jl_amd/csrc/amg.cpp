@@ -1514,6 +1514,75 @@ void Amg::f2(int l, const double* s_host, double t, double* avals_host) {
   lv.avals.download(avals_host, lv.plan.Apat.nnz());
 }
 
+// the speculated line search on the solve's own buffers (tests): see amg.hpp
+void Amg::trial_set(int l, const double* s_host, const double* nstep_host, int na, const double* alpha, const double* phi_ref_host,
+                    int mode, double* sums_host, double* sums_dev, double* s_out, double* dz, double* phi) {
+  if (ctx_.world > 1) throw ArgError("trial_set: single-GPU contexts only");
+  Level& lv = level(l);
+  resync_signals();
+  const size_t N = lv.plan.N, nK = (size_t)n_ * P_.K, nC = (size_t)n_ * P_.ncones;
+  lv.s.upload(s_host, N);
+  if (nstep_host) lv.nstep.upload(nstep_host, N);
+  if (phi_ref_host) phi_cur_.upload(phi_ref_host, nC);
+  const double* nstep = nstep_host ? lv.nstep.p : nullptr;
+  const double* phi_ref = phi_ref_host ? phi_cur_.p : nullptr;
+  double* const xs[3] = {lv.s_trial.p, lv.s_trial2.p, lv.s_trial3.p};
+  double* const dzs[3] = {DzA_.p, DzB_.p, DzC_.p};
+  double* const phis[3] = {phi_trial_.p, phi_trial2_.p, phi_trial3_.p};
+  double* const out = scal_.p + 4;
+  double* const out_h = host_scal(out);
+  // a result that a launch does not write must not pass for one: all-ones bytes are a NaN
+  for (int a = 0; a < na; ++a) {
+    hip_check(hipMemsetAsync(xs[a], 0xff, N * sizeof(double), ctx_.stream), "memset s_out");
+    hip_check(hipMemsetAsync(dzs[a], 0xff, nK * sizeof(double), ctx_.stream), "memset dz");
+    hip_check(hipMemsetAsync(phis[a], 0xff, nC * sizeof(double), ctx_.stream), "memset phi");
+  }
+  hip_check(hipMemsetAsync(out, 0xff, 6 * sizeof(double), ctx_.stream), "memset sums");
+  hip_check(hipStreamSynchronize(ctx_.stream), "sync trial_set");
+  for (int o = 0; o < 6; ++o) out_h[o] = std::nan("");
+  if (mode == 0) {
+    TrialSet T;
+    T.na = na;
+    for (int a = 0; a < na; ++a) {
+      T.alpha[a] = alpha[a];
+      T.s_out[a] = nstep ? xs[a] : nullptr;
+      T.dz[a] = dzs[a];
+      T.phi_out[a] = phis[a];
+    }
+    T.out_dev = out;
+    T.out_host = out_h;
+    launch_trial_set(ctx_.stream, lv.B.view, n_, P_, lv.s.p, nstep, T, Dz0_.p, w_.p, c_.p, phi_ref, kFracToBoundary, partials_.p,
+                     next_signal());
+  } else {
+    for (int a = 0; a < na; ++a) {
+      const HostSignal sig = a == na - 1 ? next_signal() : HostSignal();
+      if (mode == 1) {
+        launch_trial_f0(ctx_.stream, lv.B.view, n_, P_, lv.s.p, alpha[a], nstep, nstep ? xs[a] : nullptr, Dz0_.p, dzs[a], w_.p,
+                        c_.p, phi_ref, kFracToBoundary, phis[a], partials_.p, out + 2 * a, out_h + 2 * a, sig);
+      } else {
+        const double* x = lv.s.p;
+        if (nstep) {
+          launch_waxpby(ctx_.stream, (int)N, lv.s.p, alpha[a], nstep, xs[a]);
+          x = xs[a];
+        }
+        dev_apply(lv, x, dzs[a]);
+        launch_barrier_f0(ctx_.stream, n_, P_, dzs[a], w_.p, c_.p, phi_ref, kFracToBoundary, phis[a], partials_.p, out + 2 * a,
+                          out_h + 2 * a, sig);
+      }
+    }
+  }
+  hip_check(hipGetLastError(), "trial_set launch");
+  wait_signal("sync trial_set");      // as the line search: the sums are in pinned memory once the signal is
+  for (int o = 0; o < 2 * na; ++o) sums_host[o] = const_cast<const volatile double*>(out_h)[o];
+  hip_check(hipStreamSynchronize(ctx_.stream), "sync trial_set");
+  hip_check(hipMemcpy(sums_dev, out, 2 * na * sizeof(double), hipMemcpyDeviceToHost), "D2H sums");
+  for (int a = 0; a < na; ++a) {
+    hip_check(hipMemcpy(s_out + a * N, nstep ? xs[a] : lv.s.p, N * sizeof(double), hipMemcpyDeviceToHost), "D2H s_out");
+    hip_check(hipMemcpy(dz + a * nK, dzs[a], nK * sizeof(double), hipMemcpyDeviceToHost), "D2H dz");
+    hip_check(hipMemcpy(phi + a * nC, phis[a], nC * sizeof(double), hipMemcpyDeviceToHost), "D2H phi");
+  }
+}
+
 // ------------------------------------------------------------------ Float32 evaluation (kernels_f32.hip)
 void Amg::ensure_f32(Level& lv) {
   const size_t nK = (size_t)n_ * P_.K;

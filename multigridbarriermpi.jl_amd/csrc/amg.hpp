@@ -331,6 +331,14 @@ class Amg {
   double f0_trial(int l, const double* s_ref_host, const double* s_host, double t);
   void f1(int l, const double* s_host, double t, double* g_host);
   void f2(int l, const double* s_host, double t, double* avals_host);
+  // the line search's objective at the na (1..3) points x_a = s + alpha[a] * nstep (nstep nullable: x_a = s) on the buffers a
+  // solve uses -- the level's s / nstep / s_trial*, DzA..C, phi_cur_ (<- phi_ref_host, nullable: no rule), phi_trial*, partials_
+  // and scal_ + 4 with its pinned twin (tests).  mode 0: one launch_trial_set; 1: na launch_trial_f0; 2: waxpby, apply_D and
+  // barrier_f0_kernel per point, whatever fused_trial_rows_ says.  Every output buffer is filled with NaN before the launches.
+  // sums_host[2 na]: as the kernels left them in pinned memory; sums_dev[2 na]: copied from scal_ + 4; s_out[na x N] (x_a;
+  // without nstep the kernels write none: s), dz[na x n x K], phi[na x n x ncones].  Single-GPU contexts only.
+  void trial_set(int l, const double* s_host, const double* nstep_host, int na, const double* alpha, const double* phi_ref_host,
+                 int mode, double* sums_host, double* sums_dev, double* s_out, double* dz, double* phi);
   // Float32 evaluation of the same three pieces at level l (kernels_f32.hip; float operators and vectors are shadows of the
   // double ones, built on first use).  tpl64 != 0: the double instantiation of the SAME templates instead (tests).
   double f0_f32(int l, const float* s_host, float t);

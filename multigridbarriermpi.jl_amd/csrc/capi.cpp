@@ -796,6 +796,17 @@ int mgb_amg_f2_template_f64(mgb_amg a, int level, const double* s, double t, dou
     a->amg->f2_tpl64(level, s, t, lower_vals);
   });
 }
+int mgb_amg_trial_set(mgb_amg a, int level, const double* s, const double* nstep, int na, const double* alpha,
+                      const double* phi_ref, int mode, double* sums_host, double* sums_dev, double* s_out, double* dz,
+                      double* phi) {
+  return guard([&] {
+    need(a && s && alpha && sums_host && sums_dev && s_out && dz && phi && level >= 0 && level < a->amg->L(),
+         "trial_set: bad arguments");
+    need(na >= 1 && na <= 3, "trial_set: na must be 1, 2 or 3");
+    need(mode >= 0 && mode <= 2, "trial_set: mode must be 0, 1 or 2");
+    a->amg->trial_set(level, s, nstep, na, alpha, phi_ref, mode, sums_host, sums_dev, s_out, dz, phi);
+  });
+}
 int mgb_amg_chol_info(mgb_amg a, int level, int* split_world, double* exchange_doubles, int* launches) {
   return guard([&] {
     need(a && level >= 0 && level < a->amg->L(), "level out of range");

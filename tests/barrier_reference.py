@@ -163,7 +163,7 @@ def _power_cone(T, Y, a64, mu64):
         for cs_ in scols:
             H[(cs, cs_)] = hss
     kappa = (sa.v + qq.v) / phi.v
-    return dict(F=F, G=G, H=H, ok=ok, phi=phi.v, dist=phi.v / sa.v, kappa=kappa,
+    return dict(F=F, G=G, H=H, ok=ok, phi=phi.v, bphi=phi.e, dist=phi.v / sa.v, kappa=kappa,
                 inter=[sa.v, qq.v, phi.v, phi.v * phi.v, s.v * s.v, ds.v])
 
 
@@ -181,12 +181,12 @@ def _half_space(T, Y):
         G[i] = neg(div(const(ci, n), phi))
         for j, cj in zip(T["q"], T["coef"]):
             H[(i, j)] = mul(mul(const(ci, n), const(cj, n)), ip2)
-    return dict(F=F, G=G, H=H, ok=ok, phi=phi.v, dist=phi.v / mag, kappa=mag / phi.v, inter=[phi.v, phi.v * phi.v])
+    return dict(F=F, G=G, H=H, ok=ok, phi=phi.v, bphi=phi.e, dist=phi.v / mag, kappa=mag / phi.v, inter=[phi.v, phi.v * phi.v])
 
 
 class Rows:
     """F (n), F1 (n, K), F2 (n, K, K) in long double, their bounds bF, bF1, bF2 (units of u), per term the cone distance
-    `phi`, the relative distance `dist`, the amplification `kappa` (n, nterms; +inf where the term is masked out), `feasible`
+    `phi` with its bound `bphi`, the relative distance `dist`, the amplification `kappa` (n, nterms; +inf where the term is masked out), `feasible`
     (every active term strictly inside) and `in_range` (every exact intermediate inside RANGE)."""
 
 
@@ -202,6 +202,7 @@ def reference(terms, Y, a_node=None, mu_node=None, mask=None):
     G = [V(np.zeros(n, dtype=LD)) for _ in range(K)]
     H = [[V(np.zeros(n, dtype=LD)) for _ in range(K)] for _ in range(K)]
     R.phi, R.dist, R.kappa = (np.full((n, nt), np.inf, dtype=LD) for _ in range(3))
+    R.bphi = np.zeros((n, nt), dtype=LD)
     R.feasible, R.in_range = np.ones(n, dtype=bool), np.ones(n, dtype=bool)
     with np.errstate(all="ignore"):
         for ti, term in enumerate(terms):
@@ -221,6 +222,7 @@ def reference(terms, Y, a_node=None, mu_node=None, mask=None):
             for (ci, cj), h in t["H"].items():
                 H[ci][cj] = add(H[ci][cj], z(h))
             R.phi[:, ti] = np.where(act, t["phi"], np.inf)
+            R.bphi[:, ti] = np.where(act, t["bphi"], 0)
             R.dist[:, ti] = np.where(act, t["dist"], np.inf)
             R.kappa[:, ti] = np.where(act, t["kappa"], np.inf)
             R.feasible &= np.where(act, t["ok"], True)
