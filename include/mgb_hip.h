@@ -209,6 +209,7 @@ int mgb_amg_hessian_pattern(mgb_amg a, int level, int32_t* rowptr, int32_t* coli
 int mgb_amg_set_c(mgb_amg a, const double* c);     /* n x K row-major cost (f_grid) */
 int mgb_amg_set_z(mgb_amg a, const double* z);     /* S*n, [u; s] */
 int mgb_amg_get_z(mgb_amg a, double* z);           /* mpi_to_native(sol).z, src:422-474 */
+int mgb_amg_get_c(mgb_amg a, double* c);           /* the cost as the device holds it, n x K row-major (local rows); waits for the stream */
 /* barrier(F).f0/f1/f2 at level `level`, subspace coordinates s (N_l host values), parameter t:
  *   f0: test/test_apply_d.jl:44 + tools/profile_barrier.jl:45-59; parts = {sum w F, sum w c.Dz}
  *   f1: test/test_column_extract.jl:50-80;  f2: test/test_map_rows_compare.jl:102-123,165-170 */
@@ -264,6 +265,31 @@ int mgb_amg_sol_kernels(mgb_amg a, double* ms11, double* bytes11, long long* lau
  * hessian_assemble, barrier_f1, restrict, barrier_f0, trial_f0 (the fused trial point + apply_D + barrier_f0 launch of
  * launch-bound meshes), apply_D through the plain CSR kernel; bytes8[7] = 1 if slot 0 used the element-local view */
 int mgb_amg_time_kernels(mgb_amg a, int level, int reps, int nrot, double* ms8, double* bytes8);
+
+/* ---- time loop of parabolic_solve: the transition between two barrier solves, on the device (docs/src/guide.md "Time-Dependent
+ * (Parabolic) Problems"; time-dependent closures f1(t, x), g(t, x) are [UPSTREAM-UNVERIFIED], the contract is this project's) -- *
+ * For an AMG with the parabolic layout: S = 3 state variables [u; s1; s2] (z column-major), K = dim + 3 rows of D = (u id,
+ * u dx.., s1 id, s2 id), cones s1 >= u^2 and s2 >= |grad u|^p.  Single-GPU contexts.
+ * mgb_amg_parabolic_begin: bidx = the nb nodes whose u is Dirichlet data (the empty rows of the finest `dirichlet` subspace),
+ * kept on the device.  MGB_E_ARG -- before anything is launched -- on another layout, a sharded context, nb < 0 or an index
+ * outside [0, n).
+ * mgb_amg_parabolic_step: from t_k to t_{k+1} = t_k + h (finite h > 0, p >= 1), enqueued on the context stream in this order:
+ *   1. cost       c[i, 0] = f_nodes[i] - u[i] / h with the OLD u (a division, then a subtraction: bitwise what fp64 numpy gives for
+ *                 f - u / h), c[i, K-2] = 1 / (2h), c[i, K-1] = 1 / p (host scalars), 0 elsewhere;
+ *   2. boundary   u[bidx[j]] = gb[j] (gb null: kept); interior u, s1, s2 untouched;
+ *   3. violations Dz0 = D z, then v1 = max_i (u_i^2 - s1_i), v2 = max_i ((sum_d g_id^2)^(p/2) - s2_i), g = columns 1..dim of
+ *                 Dz0; a node with a non-finite u, g, s1 or s2 makes both maxima NaN (never dropped);
+ *   4. lift       lift_j = 1 + v_j if v_j >= 0, else exactly 0;  s_j += lift_j at every node (a constant shift, the closed-form
+ *                 feasibility phase of amgb); a column whose lift is 0 is not written; Dz0 = D z again.
+ * f_nodes (n) and gb (nb) are device vectors of the AMG's context.  lift2 null: the call does not wait for the device;
+ * non-null: as mgb_amg_parabolic_lifts.  The next mgb_amg_solve starts from this state.
+ * mgb_amg_parabolic_lifts: waits for the stream; (lift_1, lift_2) of the last step; MGB_E_NUMERIC if one is not finite.
+ * mgb_amg_snapshot: one launch, out[i * S + s] = z[s * n + i] (row-major n x S, the layout of an HPCMatrix); out is a device
+ * vector of n * S values owned by the caller; no host wait. */
+int mgb_amg_parabolic_begin(mgb_amg a, int nb, const int32_t* bidx);
+int mgb_amg_parabolic_step(mgb_amg a, double h, double p, mgb_vec f_nodes, mgb_vec gb_or_null, double* lift2_or_null);
+int mgb_amg_parabolic_lifts(mgb_amg a, double* lift2);
+int mgb_amg_snapshot(mgb_amg a, mgb_vec out);
 
 /* ---- multigrid pieces: SURVEY.md section 8 row a11 / 8(b) `mgb_hessian_apply / mgb_smooth / mgb_prolong / mgb_restrict` ------ *
  * The reference has no smoother: its "multigrid" is Newton on the nested subspaces R_l with MultiGridBarrier.solve -> MUMPS per

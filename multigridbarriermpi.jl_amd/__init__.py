@@ -934,6 +934,37 @@ class AMG:
         call("mgb_amg_get_z", self.handle, dptr(z))
         return z
 
+    def get_c(self):
+        """The cost as the device holds it, (n_local, K)."""
+        c = np.empty((self.n_local, self.K))
+        call("mgb_amg_get_c", self.handle, dptr(c))
+        return c
+
+    def parabolic_begin(self, bidx):
+        """Time loop of parabolic_solve on the device (include/mgb_hip.h): `bidx` = the nodes that carry Dirichlet data."""
+        bidx = i32(np.asarray(bidx).reshape(-1))
+        call("mgb_amg_parabolic_begin", self.handle, bidx.size, iptr(bidx))
+
+    def parabolic_step(self, h, p, f_nodes: "HPCVector", gb: Optional["HPCVector"] = None, wait=True):
+        """Cost from the old u, boundary overwrite, violations and lifts of one time step, enqueued behind each other.
+        wait=True returns (lift_1, lift_2); wait=False returns None without waiting for the device (see parabolic_lifts)."""
+        out = np.empty(2) if wait else None
+        call("mgb_amg_parabolic_step", self.handle, float(h), float(p), f_nodes.handle, None if gb is None else gb.handle, dptr(out))
+        return out
+
+    def parabolic_lifts(self):
+        out = np.empty(2)
+        call("mgb_amg_parabolic_lifts", self.handle, dptr(out))
+        return out
+
+    def snapshot(self) -> "HPCMatrix":
+        """The current z as an (n, S) HPCMatrix with device storage of its own, written by one kernel."""
+        out = HPCMatrix.__new__(HPCMatrix)
+        out.shape, out.backend = (self.n, self.S), self.geometry.x.backend
+        out._v = HPCVector(self.n * self.S, out.backend)
+        call("mgb_amg_snapshot", self.handle, out._v.handle)
+        return out
+
     def apply_D(self, l, s):
         s = f64(s)
         out = np.empty((self.n_local, self.K))
@@ -1429,44 +1460,63 @@ def fem2d_mpi_solve(L: int = 2, K=None, **kwargs) -> AMGBSOL:
 
 @dataclass
 class ParabolicSOL:
-    """src:512-516 field order: geometry, ts, u (one n x S snapshot per time step)."""
+    """src:512-516 field order: geometry, ts, u (one n x S snapshot per time step); `lift` (this project's, trailing): the
+    (nsteps, 2) slack shifts (lift_1, lift_2) applied before each step's barrier solve, None where the loop does not record them."""
     geometry: Geometry
     ts: np.ndarray
     u: list
+    lift: Optional[np.ndarray] = None
 
 
-def parabolic_solve(geometry: Geometry, h=0.2, t0=0.0, t1=1.0, p=1.0, f1=None, g=None, tol=None, verbose=False,
-                    schedule="fine", solver="gpu", **rest) -> ParabolicSOL:
-    """MultiGridBarrier.parabolic_solve on an MPI geometry (imported at src:22,54; kwargs h, t1, p, verbose as in
-    test/test_parabolic.jl:48 and docs/src/guide.md:367,377).  Implicit Euler for
-        u_t - div(|grad u|^(p-2) grad u) = -f1 ;
-    each step minimises int (1/2h)(s1 - 2 u u_k) + (1/p) s2 + f1 u subject to s1 >= u^2, s2 >= |grad u|^p with the
-    barrier of the two-cone intersection (one GPU barrier solve per step; the time loop is host control flow).
-    Dirichlet data = boundary trace of the initial condition g (time independent)."""
-    if geometry._geo is None:
-        raise TypeError("parabolic_solve: geometry must come from native_to_mpi / fem*d_mpi")
-    dim = geometry.discretization["dim"]
-    g = DEFAULT_G[dim] if g is None else g
-    f1 = (lambda x: 0.5) if f1 is None else f1
-    ops = ("dx", "dy", "dz")[:dim]
-    state = (("u", "dirichlet"), ("s1", "full"), ("s2", "full"))
-    D = (("u", "id"),) + tuple(("u", o) for o in ops) + (("s1", "id"), ("s2", "id"))
-    K = dim + 3
-    cones = [([0, K - 2], 2.0), (list(range(1, dim + 1)) + [K - 1], float(p))]
-    M = AMG(geometry, state, D, p, cones=cones)
-    x = geometry.x.to_numpy()
-    n = x.shape[0]
-    u0 = np.array([np.asarray(g(xi), dtype=np.float64).reshape(-1)[0] for xi in x])
-    grad2 = sum((geometry.operators[o].host @ u0) ** 2 for o in ops)
-    z = np.concatenate([u0, np.full(n, 1.0 + float(np.max(u0 * u0))),
-                        np.full(n, 1.0 + float(np.max(grad2 ** (p / 2.0))))])
-    fgrid = np.array([float(f1(xi)) for xi in x])
-    nsteps = int(round((t1 - t0) / h))
-    ts = t0 + h * np.arange(nsteps + 1)
-    backend = geometry.x.backend
+def _positional_arity(fn, name):
+    """Number of positional parameters of the closure `fn` (1: fn(x), 2: fn(t, x)); anything else is a TypeError naming `name`."""
+    import inspect
+    try:
+        params = inspect.signature(fn).parameters.values()
+    except (TypeError, ValueError):
+        raise TypeError("parabolic_solve: cannot read the signature of %s; pass a function of (x) or of (t, x)" % name)
+    k = sum(1 for q in params if q.kind in (q.POSITIONAL_ONLY, q.POSITIONAL_OR_KEYWORD))
+    if k not in (1, 2) or any(q.kind == q.VAR_POSITIONAL for q in params):
+        raise TypeError("parabolic_solve: %s must take (x) or (t, x), not %d positional parameters" % (name, k))
+    return k
+
+
+def _parabolic_times(h, t0, t1, ts):
+    """(ts, hs): the time grid and the step of every interval.  `ts=` overrides h, t0, t1 (h_k = ts[k+1] - ts[k]); without it the
+    grid is t0 + h * arange(nsteps + 1) and every step is h itself."""
+    if ts is None:
+        nsteps = int(round((t1 - t0) / h))
+        return t0 + h * np.arange(nsteps + 1), np.full(nsteps, float(h))
+    ts = np.array(ts, dtype=np.float64)
+    if ts.ndim != 1 or ts.size < 2:
+        raise ValueError("parabolic_solve: ts must be a 1-D array with at least 2 entries")
+    if not np.all(np.isfinite(ts)) or not np.all(np.diff(ts) > 0):
+        raise ValueError("parabolic_solve: ts must be finite and strictly increasing")
+    return ts, np.diff(ts)
+
+
+def _parabolic_forcing(f1, x, ts):
+    """(time_dependent, row): row(k) = the (n,) forcing of the step that ends at ts[k + 1] (implicit Euler: taken at the new time)."""
+    n, nsteps = x.shape[0], len(ts) - 1
+    if callable(f1):
+        if _positional_arity(f1, "f1") == 1:
+            fgrid = np.array([float(f1(xi)) for xi in x])
+            return False, lambda k: fgrid
+        return True, lambda k: np.array([float(f1(ts[k + 1], xi)) for xi in x])
+    fa = f64(np.asarray(f1))
+    if fa.shape == (n,):
+        return False, lambda k: fa
+    if fa.ndim == 2 and fa.shape == (nsteps, n):
+        return True, lambda k: fa[k]
+    raise ValueError("parabolic_solve: an array f1 must have shape (n,) = (%d,) or (len(ts) - 1, n) = (%d, %d), got %r"
+                     % (n, nsteps, n, tuple(fa.shape)))
+
+
+def _parabolic_host_loop(M, z, n, K, p, hs, fgrid, tol, verbose, schedule, solver, backend):
+    """The time loop through the host (sharded contexts): z down, cost built in numpy, cost and snapshot up, every step."""
     u = [HPCMatrix(z.reshape(n, 3, order="F"), backend)]
     M.set_z(z)
-    for _ in range(nsteps):
+    for h in hs:
         c = np.zeros((n, K))
         c[:, 0] = fgrid - z[:n] / h
         c[:, K - 2] = 1.0 / (2.0 * h)
@@ -1475,7 +1525,73 @@ def parabolic_solve(geometry: Geometry, h=0.2, t0=0.0, t1=1.0, p=1.0, f1=None, g
         M.solve(tol=tol, verbose=int(bool(verbose)), schedule=schedule, solver=solver)
         z = M.get_z()
         u.append(HPCMatrix(z.reshape(n, 3, order="F"), backend))
-    return ParabolicSOL(geometry, ts, u)
+    return u
+
+
+def parabolic_solve(geometry: Geometry, h=0.2, t0=0.0, t1=1.0, p=1.0, f1=None, g=None, tol=None, verbose=False,
+                    schedule="fine", solver="gpu", ts=None, **rest) -> ParabolicSOL:
+    """MultiGridBarrier.parabolic_solve on an MPI geometry (imported at src:22,54; kwargs h, t1, p, verbose as in
+    test/test_parabolic.jl:48 and docs/src/guide.md:367,377).  Implicit Euler for
+        u_t - div(|grad u|^(p-2) grad u) = -f1 ;
+    the step from t_k to t_{k+1} = t_k + h_k minimises int (1/2h_k)(s1 - 2 u u_k) + (1/p) s2 + f1 u subject to s1 >= u^2,
+    s2 >= |grad u|^p with the barrier of the two-cone intersection: one GPU barrier solve per step, and between two solves
+    the state stays on the device (cost, boundary values, slack lifts and snapshots are kernels).
+      f1: f1(x) | f1(t, x) | an (n,) array | a (len(ts) - 1, n) array, row k for the step that ends at ts[k + 1];
+      g:  g(x) | g(t, x); its first component is the initial condition at ts[0] and, on the boundary nodes, the Dirichlet
+          value at t_{k+1} (g(x): the boundary trace of the initial condition, time independent);
+      ts: strictly increasing times (overrides h, t0, t1; h_k = ts[k + 1] - ts[k]).
+    Forcing and boundary data are taken at the new time t_{k+1}.  Where new boundary values or a larger gradient push the old
+    slacks out of a cone, the slack is shifted by the constant lift = 1 + max violation (0 when nothing violates) before the
+    solve; the shifts are returned as `lift` (nsteps, 2).  Sharded contexts (world > 1) run time-independent data only."""
+    if geometry._geo is None:
+        raise TypeError("parabolic_solve: geometry must come from native_to_mpi / fem*d_mpi")
+    dim = geometry.discretization["dim"]
+    g = DEFAULT_G[dim] if g is None else g
+    f1 = (lambda x: 0.5) if f1 is None else f1
+    g_arity = _positional_arity(g, "g")
+    explicit_ts = ts is not None
+    ts, hs = _parabolic_times(h, t0, t1, ts)
+    nsteps = len(hs)
+    ops = ("dx", "dy", "dz")[:dim]
+    state = (("u", "dirichlet"), ("s1", "full"), ("s2", "full"))
+    D = (("u", "id"),) + tuple(("u", o) for o in ops) + (("s1", "id"), ("s2", "id"))
+    K = dim + 3
+    cones = [([0, K - 2], 2.0), (list(range(1, dim + 1)) + [K - 1], float(p))]
+    x = geometry.x.to_numpy()
+    n = x.shape[0]
+    f_timed, f_row = _parabolic_forcing(f1, x, ts)
+    backend = geometry.x.backend
+    if backend.world > 1 and (f_timed or g_arity == 2 or explicit_ts):
+        raise NotImplementedError("parabolic_solve: sharded contexts (world > 1) are not supported with f1(t, x), g(t, x) or ts=")
+    g_at = (lambda t, xi: g(t, xi)) if g_arity == 2 else (lambda t, xi: g(xi))
+    M = AMG(geometry, state, D, p, cones=cones)
+    u0 = np.array([np.asarray(g_at(ts[0], xi), dtype=np.float64).reshape(-1)[0] for xi in x])
+    grad2 = sum((geometry.operators[o].host @ u0) ** 2 for o in ops)
+    z = np.concatenate([u0, np.full(n, 1.0 + float(np.max(u0 * u0))),
+                        np.full(n, 1.0 + float(np.max(grad2 ** (p / 2.0))))])
+    if backend.world > 1:
+        return ParabolicSOL(geometry, ts, _parabolic_host_loop(M, z, n, K, p, hs, f_row(0), tol, verbose, schedule, solver, backend))
+    bidx = np.flatnonzero(np.diff(geometry.subspaces["dirichlet"][-1].host.indptr) == 0)
+    M.set_z(z)
+    M.parabolic_begin(bidx)
+    u = [M.snapshot()]
+    lift = np.zeros((nsteps, 2))
+    fv = None
+    for k in range(nsteps):
+        if fv is None or f_timed:
+            fv = HPCVector(f_row(k), backend)
+        gb = None
+        if g_arity == 2:
+            gb = HPCVector(np.array([np.asarray(g(ts[k + 1], x[b]), dtype=np.float64).reshape(-1)[0] for b in bidx]), backend)
+        M.parabolic_step(hs[k], p, fv, gb, wait=False)      # enqueued: the solve starts behind it without a host round trip
+        try:
+            M.solve(tol=tol, verbose=int(bool(verbose)), schedule=schedule, solver=solver)
+        except MGBError:
+            M.parabolic_lifts()      # a non-finite state is the cause if there is one: report that instead
+            raise
+        lift[k] = M.parabolic_lifts()
+        u.append(M.snapshot())
+    return ParabolicSOL(geometry, ts, u, lift)
 
 
 # --------------------------------------------------------------------------- evaluation at arbitrary points
@@ -1724,7 +1840,7 @@ def convergence(sols, exact=None, grad=None, q=2.0) -> Convergence:
 def mpi_to_native(obj):
     """src:355-517: gather device objects back to native numpy/scipy types."""
     if isinstance(obj, ParabolicSOL):                                   # src:495-517
-        return ParabolicSOL(mpi_to_native(obj.geometry), obj.ts, [_to_cpu_array(uk) for uk in obj.u])
+        return ParabolicSOL(mpi_to_native(obj.geometry), obj.ts, [_to_cpu_array(uk) for uk in obj.u], obj.lift)
     if isinstance(obj, Geometry):
         conv = lambda m: m.to_scipy() if isinstance(m, HPCSparseMatrix) else m
         return Geometry(dict(obj.discretization), _to_cpu_array(obj.x), _to_cpu_array(obj.w),

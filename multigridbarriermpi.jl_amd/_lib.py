@@ -94,6 +94,11 @@ PROTOTYPES = {
     "mgb_amg_set_c": [H, c_dbl_p],
     "mgb_amg_set_z": [H, c_dbl_p],
     "mgb_amg_get_z": [H, c_dbl_p],
+    "mgb_amg_get_c": [H, c_dbl_p],
+    "mgb_amg_parabolic_begin": [H, C.c_int, c_i32_p],
+    "mgb_amg_parabolic_step": [H, C.c_double, C.c_double, H, H, c_dbl_p],
+    "mgb_amg_parabolic_lifts": [H, c_dbl_p],
+    "mgb_amg_snapshot": [H, H],
     "mgb_amg_apply_D": [H, C.c_int, c_dbl_p, c_dbl_p],
     "mgb_amg_f0": [H, C.c_int, c_dbl_p, C.c_double, c_dbl_p, c_dbl_p],
     "mgb_amg_f0_trial": [H, C.c_int, c_dbl_p, c_dbl_p, C.c_double, c_dbl_p],

@@ -1,4 +1,5 @@
 #include "amg.hpp"
+#include "parabolic.hpp"
 
 
 #include <chrono>
@@ -741,6 +742,56 @@ void Amg::get_z(double* z_host) {
   ctx_.allreduce_sum(zg.p, (long long)zg.n);
   hip_check(hipStreamSynchronize(ctx_.stream), "sync");
   zg.download(z_host, zg.n);
+}
+
+void Amg::get_c(double* c_host) {
+  hip_check(hipStreamSynchronize(ctx_.stream), "sync");
+  c_.download(c_host, (size_t)n_ * P_.K);
+}
+
+// ------------------------------------------------------------------ time loop of parabolic_solve (parabolic.hpp)
+
+void Amg::parabolic_begin(int nb, const int* bidx) {
+  if (ctx_.world != 1) throw ArgError("parabolic_begin: single-GPU contexts only (a sharded context keeps the host loop)");
+  if (S_ != 3 || P_.K != geo_.dim + 3)
+    throw ArgError("parabolic_begin: needs the parabolic layout, 3 state variables [u; s1; s2] and dim + 3 rows of D");
+  if (nb < 0 || (nb > 0 && !bidx)) throw ArgError("parabolic_begin: bad boundary list");
+  for (int j = 0; j < nb; ++j)
+    if (bidx[j] < 0 || bidx[j] >= n_) throw ArgError("parabolic_begin: boundary node out of range");
+  hip_check(hipSetDevice(ctx_.device), "hipSetDevice");
+  par_bidx_.upload(bidx, (size_t)nb);
+  if (par_scratch_.n < parabolic::scratch_doubles(n_)) par_scratch_.alloc(parabolic::scratch_doubles(n_));
+  par_nb_ = nb;
+}
+
+void Amg::parabolic_step(double h, double p, const double* f_dev, const double* gb_dev, double* lift2_host) {
+  if (par_nb_ < 0) throw ArgError("parabolic_step: call parabolic_begin first");
+  if (!(h > 0.0) || !std::isfinite(h) || !(p >= 1.0) || !std::isfinite(p)) throw ArgError("parabolic_step: needs a finite h > 0 and p >= 1");
+  if (!f_dev) throw ArgError("parabolic_step: null forcing");
+  hip_check(hipSetDevice(ctx_.device), "hipSetDevice");
+  double* res = par_scratch_.p + parabolic::results_offset(n_);
+  parabolic::launch_cost(ctx_.stream, n_, P_.K, h, 1.0 / (2.0 * h), 1.0 / p, f_dev, z_.p, c_.p);
+  if (gb_dev) parabolic::launch_boundary(ctx_.stream, par_nb_, par_bidx_.p, gb_dev, z_.p);      // behind the cost: it read the old boundary
+  refresh_dz0();
+  parabolic::launch_violations(ctx_.stream, n_, P_.K, p, z_.p, Dz0_.p, par_scratch_.p);
+  parabolic::launch_lift(ctx_.stream, n_, res + 2, z_.p);
+  refresh_dz0();      // Dz0 of the shifted z
+  hip_check(hipGetLastError(), "parabolic step launch");
+  if (lift2_host) parabolic_lifts(lift2_host);
+}
+
+void Amg::parabolic_lifts(double* lift2_host) {
+  if (par_nb_ < 0) throw ArgError("parabolic_lifts: call parabolic_begin first");
+  hip_check(hipStreamSynchronize(ctx_.stream), "sync parabolic step");
+  hip_check(hipMemcpy(lift2_host, par_scratch_.p + parabolic::results_offset(n_) + 2, 2 * sizeof(double), hipMemcpyDeviceToHost), "D2H lifts");
+  if (!std::isfinite(lift2_host[0]) || !std::isfinite(lift2_host[1]))
+    throw NumericError("parabolic_step: non-finite state (u, its gradient or a slack is NaN or Inf)");
+}
+
+void Amg::snapshot(double* out_dev) {
+  hip_check(hipSetDevice(ctx_.device), "hipSetDevice");
+  parabolic::launch_snapshot(ctx_.stream, n_, S_, z_.p, out_dev);
+  hip_check(hipGetLastError(), "snapshot launch");
 }
 
 static double csr_bytes(const DevCsr& A, bool y0) {

@@ -322,6 +322,19 @@ class Amg {
   void set_c(const double* c_host);
   void set_z(const double* z_host);
   void get_z(double* z_host);
+  void get_c(double* c_host);      // the local rows of c (tests; mirrors set_c on a single-GPU context)
+
+  // ---- time loop of parabolic_solve (parabolic.hpp): the transition between two barrier solves, on the device
+  // needs the parabolic layout (S = 3: [u; s1; s2], K = dim + 3) on a single-GPU context; bidx = the nb boundary nodes
+  // (0 <= bidx < n), kept on the device.  Throws ArgError before anything is launched.
+  void parabolic_begin(int nb, const int* bidx);
+  // cost from the old u, boundary overwrite (gb_dev nullable: boundary kept), Dz0, violations, lifts, Dz0 again -- all enqueued
+  // on the context stream.  lift2_host nullable: no host wait; else as parabolic_lifts
+  void parabolic_step(double h, double p, const double* f_dev, const double* gb_dev, double* lift2_host);
+  // waits for the stream; the (lift_1, lift_2) of the last step; NumericError if one is not finite
+  void parabolic_lifts(double* lift2_host);
+  void snapshot(double* out_dev);      // z (column-major n x S) -> row-major n x S, enqueued
+  int parabolic_nb() const { return par_nb_; }      // -1 before parabolic_begin
 
   // fine-grained evaluations at level l, s (N_l host values), barrier parameter t
   //   f0 -> returns objective, also fills parts[2] = {sum w F, sum w c.Dz}
@@ -538,6 +551,9 @@ class Amg {
   std::vector<std::unique_ptr<Level>> levels_;
   DevBuf<double> w_, c_, z_, z_save_, Dz0_, Dz0_save_, Dz_, DzA_, DzB_, DzC_, v_, Y_, partials_, scal_, phi_cur_, phi_trial_, phi_trial2_,
       phi_trial3_;
+  DevBuf<int> par_bidx_;          // parabolic_begin: boundary nodes
+  DevBuf<double> par_scratch_;    // ... and the partials / results of the violation reduction
+  int par_nb_ = -1;
   PinnedBuf<int> h_flag_;
   bool host_solve_ = false;
   PinnedBuf<double> h_scal_;

@@ -865,6 +865,46 @@ int mgb_amg_get_z(mgb_amg a, double* z) {
     a->amg->get_z(z);
   });
 }
+int mgb_amg_get_c(mgb_amg a, double* c) {
+  return guard([&] {
+    need(a && c, "null argument");
+    a->amg->get_c(c);
+  });
+}
+
+// ---- time loop of parabolic_solve (parabolic.hpp / parabolic.hip)
+int mgb_amg_parabolic_begin(mgb_amg a, int nb, const int32_t* bidx) {
+  return guard([&] {
+    need(a, "parabolic_begin: null amg");
+    a->amg->parabolic_begin(nb, bidx);
+  });
+}
+int mgb_amg_parabolic_step(mgb_amg a, double h, double p, mgb_vec f_nodes, mgb_vec gb, double* lift2) {
+  return guard([&] {
+    need(a && f_nodes, "parabolic_step: null argument");
+    need(a->amg->parabolic_nb() >= 0, "parabolic_step: call mgb_amg_parabolic_begin first");
+    need(f_nodes->ctx == a->ctx && (!gb || gb->ctx == a->ctx), "parabolic_step: vectors of another context");
+    need(f_nodes->n == a->amg->n(), "parabolic_step: f_nodes must hold n values");
+    need(!gb || gb->n == a->amg->parabolic_nb(), "parabolic_step: gb must hold one value per boundary node");
+    a->amg->parabolic_step(h, p, f_nodes->buf.p, gb ? gb->buf.p : nullptr, lift2);
+  });
+}
+int mgb_amg_parabolic_lifts(mgb_amg a, double* lift2) {
+  return guard([&] {
+    need(a && lift2, "parabolic_lifts: null argument");
+    a->amg->parabolic_lifts(lift2);
+  });
+}
+int mgb_amg_snapshot(mgb_amg a, mgb_vec out) {
+  return guard([&] {
+    need(a && out, "snapshot: null argument");
+    need(out->ctx == a->ctx, "snapshot: vector of another context");
+    need(a->ctx->ctx.world == 1, "snapshot: single-GPU contexts only");
+    need(out->n == (long long)a->amg->n() * a->amg->S(), "snapshot: out must hold n x S values");
+    a->amg->snapshot(out->buf.p);
+  });
+}
+
 int mgb_amg_apply_D(mgb_amg a, int level, const double* s, double* Dz) {
   return guard([&] {
     need(a && s && Dz && level >= 0 && level < a->amg->L(), "apply_D: bad arguments");
