@@ -391,6 +391,46 @@ int mgb_geo_field_norms_host(mgb_geo g, int S, const double* z, double q, const 
                              const double* ref_grads_or_null, mgb_geo other_or_null, const double* z_other_or_null,
                              double* out, long long* outside_or_null);
 
+/* ---- energy, flux and cone margin of p-Laplace solutions (what one reports, plots and monitors after a solve) ------------ *
+ * A field is an n x S row-major nodal matrix on the geometry of a locator, as for mgb_field_norms; single-GPU contexts, fp64.
+ * At node i, in i's OWN element e = i / block:
+ *   g_i  the physical gradient of column u at x_i (what the dx / dy / dz operator rows give),   a_i = |g_i|_2,
+ *   p_i  the exponent: the scalar p, or p_nodal[i] where p_nodal (n values) is given (p is then only checked),
+ *   P_i  = a_i^p_i  (p = 2 and p = 1 take no pow; 0 at a = 0),   s_i = column s,   f_i = nodal forcing (no f: 0),   w_i the weight.
+ * Per field one row of MGB_ENERGY_COLS doubles
+ *   [0] sum w P / p       the gradient energy  int (1/p) |grad u|^p
+ *   [1] sum w f u         the load             int f u
+ *   [2] sum w (s - P) / p the slack gap, summed term by term (it is not the difference of two sums)
+ *   [3] max a^(p-1)       the largest flux magnitude; at p = 1 it is 1 where a > 0 and 0 where a = 0
+ *   [4] max (P - s)       its negative is the cone margin; a positive value means a node outside the cone
+ * A non-finite u_i, s_i, f_i or gradient makes all five contributions of node i NaN, and so does an entry of a DEVICE p_nodal
+ * that is not a finite real >= 1 (the host restatement checks its p_nodal and returns MGB_E_ARG).  A NaN term makes its sum
+ * and its maximum NaN; it is never dropped and never turned into a maximum.  Other fields of the batch are unaffected, bit for bit.
+ * Flux: sigma_i = a_i^(p_i - 2) g_i, n x dim row-major -- g_i bit for bit at p = 2, g_i / a_i at p = 1, exactly 0 where a_i = 0
+ * for every p.
+ * Batching: B >= 1 fields on the same geometry (the snapshots of a parabolic run) are reduced by ONE pair of launches: partials
+ * on a grid (ceil(n / 256), B) of 256 threads, then one workgroup per field that combines its partials in ascending workgroup
+ * order.  No atomics; the result of a field depends on n alone, not on B or on its place in the batch: a batch returns the bits
+ * of B calls with B = 1.  The fields are B separate vectors (a device table of their B pointers is uploaded with every
+ * call; no field is copied).  f: f_rows = 1 -- n values shared by all fields -- or f_rows = B -- B x n, row b
+ * for field b.  The per-node arithmetic is compiled with fp contraction off (the products and the sums behind them are not
+ * fused), in the kernels and in the host restatement.
+ * MGB_E_ARG, before anything is launched: a null argument or field; B < 1 (device: B > 65535); S < 1; p not finite or < 1;
+ * u or s outside [0, S); u == s; a vector whose length is not exactly what the shapes above say; f_rows neither 1 nor B;
+ * vectors of another context; a sharded context (world > 1). */
+#define MGB_ENERGY_COLS 5
+/* two launches on the context stream; the B x MGB_ENERGY_COLS results are copied to the host and the call waits for them */
+int mgb_geo_field_energy(mgb_locator loc, int B, const mgb_vec* z /* B vectors of n x S */, int S, int u, int s, double p,
+                         mgb_vec p_nodal_or_null, mgb_vec f_or_null, int f_rows, double* out_host /* B x MGB_ENERGY_COLS */);
+/* host restatement (no context, no GPU): the same per-node routine on host arrays, field after field, summed serially in
+ * ascending node order; flux_or_null: B x n x dim */
+int mgb_geo_field_energy_host(mgb_geo g, int B, const double* const* z /* B arrays of n x S */, int S, int u, int s, double p,
+                              const double* p_nodal_or_null, const double* f_or_null, int f_rows,
+                              double* out /* B x MGB_ENERGY_COLS */, double* flux_or_null);
+/* one launch on the context stream, one thread per node; flux: a caller-owned device vector of n x dim values, not z; the call
+ * does not wait on the host (there is no slack column here: the u == s rule does not apply) */
+int mgb_geo_field_flux(mgb_locator loc, mgb_vec z, int S, int u, double p, mgb_vec p_nodal_or_null, mgb_vec flux);
+
 /* ---- host-only symbolic helpers (no GPU needed; used by the CPU test-suite) ----------------- */
 
 typedef struct mgb_plan_s* mgb_plan;  /* symbolic products of one level: R, B=D*R, B', Hessian plan T */

@@ -37,6 +37,7 @@ __all__ = [
     "backend_hip", "amgb_zeros", "amgb_all_isfinite", "amgb_diag", "amgb_blockdiag", "map_rows", "map_rows_gpu",
     "_raw_array", "_to_cpu_array", "MGBError", "device_count", "AMG", "amg", "hcat", "BarrierFn", "barrier_functions",
     "interpolate", "sample_grid", "norms", "error", "convergence", "FieldNorms", "Convergence",
+    "energy", "flux", "Energy",
 ]
 
 
@@ -1835,6 +1836,169 @@ def convergence(sols, exact=None, grad=None, q=2.0) -> Convergence:
         orders = {name: np.log2(v[:-1] / v[1:]) for name, v in cols.items()}
     return Convergence(errs, cols["lq"], cols["w1q"], cols["max"], cols["gradmax"], orders["lq"], orders["w1q"], orders["max"],
                        orders["gradmax"])
+
+
+# --------------------------------------------------------------------------- energy, flux and cone margin of solutions
+
+
+@dataclass
+class Energy:
+    """Result of energy(), by the nodal quadrature rule: `gradient` = int (1/p) |grad u|^p, `load` = int f u, `total` =
+    gradient + load, `slack_gap` = int (s - |grad u|^p) / p, `margin` = -max (|grad u|^p - s) (negative: a node lies outside its
+    cone), `flux_max` = max |grad u|^(p-1).  Floats for one field; arrays of len(ts) for a ParabolicSOL, whose `ts` is carried."""
+    gradient: object
+    load: object
+    total: object
+    slack_gap: object
+    margin: object
+    flux_max: object
+    ts: Optional[np.ndarray] = None
+
+
+def _energy_exponent(p, x, who):
+    """(scalar p, per-node exponents or None) of a scalar, a callable p(x) or an (n,) array: the forms amgb takes."""
+    n = x.shape[0]
+    if callable(p):
+        pn = np.array([float(p(xi)) for xi in x])
+    elif np.isscalar(p):
+        if isinstance(p, (str, bytes)):
+            raise TypeError("%s: p must be a scalar, a callable p(x) or an (n,) array, got %r" % (who, p))
+        p = float(p)
+        if not (math.isfinite(p) and p >= 1.0):
+            raise ValueError("%s: p must be a finite real >= 1, got %r" % (who, p))
+        return p, None
+    else:
+        try:
+            pn = f64(np.asarray(_to_cpu_array(p)))
+        except (TypeError, ValueError):
+            raise TypeError("%s: p must be a scalar, a callable p(x) or an (n,) array" % who)
+        if pn.shape != (n,):
+            raise ValueError("%s: an array p must have shape (n,) = (%d,), got %r" % (who, n, tuple(pn.shape)))
+    if not (np.all(np.isfinite(pn)) and np.all(pn >= 1.0)):
+        raise ValueError("%s: p must give one finite value >= 1 per node" % who)
+    return float(pn[0]), pn
+
+
+def _energy_forcing(f, x, ts, B, who):
+    """None or the (rows, n) forcing, rows 1 or B, of a scalar, f(x), an (n,) array or -- with ts -- f(t, x) / (len(ts), n).
+    A callable is f(x) or f(t, x) by the number of its positional parameters WITHOUT a default."""
+    n = x.shape[0]
+    if f is None:
+        return None
+    if callable(f):
+        import inspect
+        try:
+            params = inspect.signature(f).parameters.values()
+            k = sum(1 for q in params if q.kind in (q.POSITIONAL_ONLY, q.POSITIONAL_OR_KEYWORD) and q.default is q.empty)
+        except (TypeError, ValueError):
+            k = 1
+        if k == 2:
+            if ts is None:
+                raise TypeError("%s: f(t, x) goes with a ParabolicSOL; pass f(x) here" % who)
+            return np.array([[float(f(t, xi)) for xi in x] for t in ts])
+        if k != 1:
+            raise TypeError("%s: f must take (x) or (t, x), not %d positional parameters without a default" % (who, k))
+        return np.array([float(f(xi)) for xi in x]).reshape(1, n)
+    if np.isscalar(f):
+        return np.full((1, n), float(f))
+    fa = f64(np.asarray(_to_cpu_array(f)))
+    if fa.shape == (n,):
+        return fa.reshape(1, n)
+    if ts is not None and fa.shape == (B, n):
+        return fa
+    if ts is not None:
+        raise ValueError("%s: an array f must have shape (n,) = (%d,) or (len(ts), n) = (%d, %d), got %r"
+                         % (who, n, B, n, tuple(fa.shape)))
+    raise ValueError("%s: an array f must have shape (n,) = (%d,), got %r" % (who, n, tuple(fa.shape)))
+
+
+def _energy_column(v, S, name, who):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError("%s: %s must be a column index (an int), got %r" % (who, name, v))
+    c = int(v) + S if v < 0 else int(v)
+    if not 0 <= c < S:
+        raise ValueError("%s: column %s = %d is outside the %d columns of z" % (who, name, v, S))
+    return c
+
+
+def energy(obj, p, f=None, u=0, s=-1, z=None) -> Energy:
+    """Energy J(u) = int (1/p) |grad u|^p + f u, slack gap, cone margin and largest flux of a solution, reduced on the device
+    (csrc/energy.hip; contract in include/mgb_hip.h and DESIGN.md section 4g).  `obj`: an AMGBSOL, a device Geometry with `z=`
+    an (n, S) array or HPCMatrix, or a ParabolicSOL, whose len(ts) snapshots are reduced by ONE pair of launches.  `p`: a
+    scalar, a callable p(x) or an (n,) array; `f`: None (no load), a scalar, f(x), an (n,) array, and for a ParabolicSOL also
+    f(t, x) or a (len(ts), n) array, row k going with snapshot k; `u`, `s`: the columns of the solution and of its slack
+    (negative: from the end)."""
+    ts = None
+    if isinstance(obj, ParabolicSOL):
+        if z is not None:
+            raise ValueError("energy: z= does not go with a ParabolicSOL (its snapshots are the fields)")
+        geometry, fields, ts = obj.geometry, list(obj.u), np.asarray(obj.ts)
+        if len(fields) != len(ts) or not fields:
+            raise ValueError("energy: the ParabolicSOL has %d snapshots for %d times" % (len(fields), len(ts)))
+    elif isinstance(obj, (AMGBSOL, Geometry)):
+        geometry, z = _field_of(obj, "energy", z)
+        fields = [z]
+    else:
+        raise TypeError("energy: expected an AMGBSOL, a ParabolicSOL or a Geometry")
+    if geometry._geo is None:
+        raise TypeError("energy: geometry must come from native_to_mpi / fem*d_mpi")
+    if geometry.x.backend.world > 1:
+        raise NotImplementedError("energy: sharded contexts (world > 1) are not supported")
+    loc, backend = _locator_of(geometry)
+    vecs = [_nodal_values(geometry, zk, backend, "energy") for zk in fields]
+    B, S = len(vecs), vecs[0][1]
+    if any(Sk != S for _, Sk in vecs):
+        raise ValueError("energy: the snapshots have different numbers of columns")
+    if S < 2:
+        raise ValueError("energy: z must have a solution column and a slack column, got %d column" % S)
+    u, s = _energy_column(u, S, "u", "energy"), _energy_column(s, S, "s", "energy")
+    if u == s:
+        raise ValueError("energy: u and s are the same column (%d)" % u)
+    x = np.asarray(_to_cpu_array(geometry.x)).reshape(len(geometry.w), -1)
+    p0, pn = _energy_exponent(p, x, "energy")
+    fa = _energy_forcing(f, x, ts, B, "energy")
+    pv = HPCVector(pn, backend) if pn is not None else None
+    fv = HPCVector(fa, backend) if fa is not None else None
+    table = (C.c_void_p * B)(*[v.handle.value for v, _ in vecs])
+    out = np.empty((B, 5))
+    call("mgb_geo_field_energy", loc, B, table, S, u, s, p0, pv.handle if pv is not None else None,
+         fv.handle if fv is not None else None, fa.shape[0] if fa is not None else 1, dptr(out))
+    cols = [out[:, 0].copy(), out[:, 1].copy(), out[:, 0] + out[:, 1], out[:, 2].copy(), -out[:, 4], out[:, 3].copy()]
+    if ts is None:
+        return Energy(*[float(c[0]) for c in cols])
+    return Energy(*cols, ts=ts)
+
+
+def flux(obj, p, u=0, z=None, k=-1) -> HPCMatrix:
+    """The flux sigma = |grad u|^(p-2) grad u at the nodes, each in its own element: an (n, dim) HPCMatrix that stays on the
+    device (csrc/energy.hip).  `obj`, `p`, `u`: as for energy; `k` selects the snapshot of a ParabolicSOL.  It is the gradient
+    itself at p = 2 and exactly 0 where the gradient vanishes."""
+    if isinstance(obj, ParabolicSOL):
+        if z is not None:
+            raise ValueError("flux: z= does not go with a ParabolicSOL (k= selects a snapshot)")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not -len(obj.u) <= k < len(obj.u):
+            raise ValueError("flux: k = %r is not one of the %d snapshots" % (k, len(obj.u)))
+        geometry, z = obj.geometry, obj.u[int(k)]
+    elif isinstance(obj, (AMGBSOL, Geometry)):
+        geometry, z = _field_of(obj, "flux", z)
+    else:
+        raise TypeError("flux: expected an AMGBSOL, a ParabolicSOL or a Geometry")
+    if geometry._geo is None:
+        raise TypeError("flux: geometry must come from native_to_mpi / fem*d_mpi")
+    if geometry.x.backend.world > 1:
+        raise NotImplementedError("flux: sharded contexts (world > 1) are not supported")
+    loc, backend = _locator_of(geometry)
+    zv, S = _nodal_values(geometry, z, backend, "flux")
+    u = _energy_column(u, S, "u", "flux")
+    n, dim = len(geometry.w), geometry.discretization["dim"]
+    p0, pn = _energy_exponent(p, np.asarray(_to_cpu_array(geometry.x)).reshape(n, -1), "flux")
+    pv = HPCVector(pn, backend) if pn is not None else None
+    out = HPCMatrix.__new__(HPCMatrix)
+    out.shape, out.backend = (n, dim), backend
+    out._v = HPCVector(n * dim, backend)
+    call("mgb_geo_field_flux", loc, zv.handle, S, u, p0, pv.handle if pv is not None else None, out._v.handle)
+    out._inputs = (zv, pv)      # the launch is not waited for: what it reads lives as long as what it writes
+    return out
 
 
 def mpi_to_native(obj):

@@ -134,6 +134,10 @@ PROTOTYPES = {
     "mgb_geo_interpolate_host": [H, C.c_int, c_dbl_p, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_i32_p],
     "mgb_field_norms": [H, C.c_int, H, C.c_double, H, H, H, H, c_dbl_p, c_ll_p],
     "mgb_geo_field_norms_host": [H, C.c_int, c_dbl_p, C.c_double, c_dbl_p, c_dbl_p, H, c_dbl_p, c_dbl_p, c_ll_p],
+    "mgb_geo_field_energy": [H, C.c_int, C.POINTER(H), C.c_int, C.c_int, C.c_int, C.c_double, H, H, C.c_int, c_dbl_p],
+    "mgb_geo_field_energy_host": [H, C.c_int, C.POINTER(c_dbl_p), C.c_int, C.c_int, C.c_int, C.c_double, c_dbl_p, c_dbl_p, C.c_int,
+                                  c_dbl_p, c_dbl_p],
+    "mgb_geo_field_flux": [H, H, C.c_int, C.c_int, C.c_double, H, H],
     "mgb_plan_prolongation": [H, H, c_int_p, c_int_p, c_int_p, c_i32_p, c_i32_p, c_dbl_p],
     "mgb_amg_solve": [H, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int],
     "mgb_amg_sol_info": [H, c_int_p, c_dbl_p, c_dbl_p, c_ll_p],

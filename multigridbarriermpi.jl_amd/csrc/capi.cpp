@@ -9,6 +9,7 @@
 
 #include "amg.hpp"
 #include "interp.hpp"
+#include "energy.hpp"
 #include "norms.hpp"
 
 using namespace mgb;
@@ -47,6 +48,8 @@ struct mgb_locator_s {
   DevBuf<double> x, w;
   DevBuf<double> norm_scratch;      // mgb_field_norms: partials and results, grown on demand
   DevBuf<long long> norm_counts;
+  DevBuf<double> energy_scratch;                   // mgb_geo_field_energy: partials and results, grown on demand
+  DevBuf<const double*> energy_table;              // ... and the device table of field pointers, uploaded per call
 };
 struct mgb_plan_s {
   LevelPlan plan;
@@ -1275,6 +1278,108 @@ int mgb_geo_field_norms_host(mgb_geo g, int S, const double* z, double q, const 
     A.S = S;
     A.q = q;
     norms::field_norms_host(L.dim, L.k, A, out, outside);
+  });
+}
+
+// ---- energy, flux and cone margin of p-Laplace solutions (energy.hpp / energy.hip)
+namespace {
+// what the three entry points check alike; s < 0: no slack column (flux)
+void need_energy_shape(const char* who, int B, int S, int u, int s, double p, int f_rows, bool has_f) {
+  const std::string w(who);
+  if (B < 1) throw std::invalid_argument(w + ": B must be >= 1");
+  if (S < 1) throw std::invalid_argument(w + ": S must be >= 1");
+  if (!good_q(p)) throw std::invalid_argument(w + ": p must be finite and >= 1");
+  if (u < 0 || u >= S) throw std::invalid_argument(w + ": column u outside [0, S)");
+  if (s >= S) throw std::invalid_argument(w + ": column s outside [0, S)");
+  if (u == s) throw std::invalid_argument(w + ": u and s are the same column");
+  if (has_f && f_rows != 1 && f_rows != B) throw std::invalid_argument(w + ": f must have 1 or B rows");
+}
+}  // namespace
+int mgb_geo_field_energy(mgb_locator loc, int B, const mgb_vec* z, int S, int u, int s, double p, mgb_vec p_nodal, mgb_vec f,
+                         int f_rows, double* out_host) {
+  return guard([&] {
+    need(loc && z && out_host, "geo_field_energy: null argument");
+    need_energy_shape("geo_field_energy", B, S, u, s, p, f_rows, f != nullptr);
+    need(s >= 0, "geo_field_energy: column s outside [0, S)");
+    need(loc->ctx->ctx.world == 1, "geo_field_energy: sharded contexts are not supported");
+    const interp::Locator& L = loc->loc;
+    std::vector<const double*> table((size_t)B);
+    for (int b = 0; b < B; ++b) {
+      need(z[b] != nullptr, "geo_field_energy: null field");
+      need(z[b]->n == (long long)L.n * S, "geo_field_energy: every z must hold n x S values");
+      need(z[b]->ctx == loc->ctx, "geo_field_energy: vectors of another context");
+      table[b] = z[b]->buf.p;
+    }
+    need(!p_nodal || p_nodal->n == L.n, "geo_field_energy: p_nodal must hold n values");
+    need(!f || f->n == (long long)f_rows * L.n, "geo_field_energy: f must hold f_rows x n values");
+    need((!p_nodal || p_nodal->ctx == loc->ctx) && (!f || f->ctx == loc->ctx), "geo_field_energy: vectors of another context");
+    need(B <= 65535, "geo_field_energy: at most 65535 fields per call");
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const size_t nd = energy::scratch_doubles(L.n, B);
+    if (loc->energy_scratch.n < nd) loc->energy_scratch.alloc(nd);
+    loc->energy_table.upload(table.data(), table.size());      // every earlier launch that read it has been waited for
+    energy::Args A;
+    A.own = L.view(loc->cellptr.p, loc->cellelem.p, loc->x.p);
+    A.w = loc->w.p;
+    A.p_nodal = p_nodal ? p_nodal->buf.p : nullptr;
+    A.p = p;
+    A.z = loc->energy_table.p;
+    A.f = f ? f->buf.p : nullptr;
+    A.f_stride = f && f_rows == B && B > 1 ? L.n : 0;
+    A.n = L.n, A.S = S, A.u = u, A.s = s, A.B = B;
+    energy::launch_field_energy(st, L.dim, L.k, A, loc->energy_scratch.p);
+    hip_check(hipGetLastError(), "geo_field_energy launch");
+    hip_check(hipStreamSynchronize(st), "sync geo_field_energy");
+    const size_t nwg = (size_t)energy::workgroups(L.n);
+    hip_check(hipMemcpy(out_host, loc->energy_scratch.p + nwg * B * energy::kCols, (size_t)B * energy::kCols * sizeof(double),
+                        hipMemcpyDeviceToHost), "D2H");
+  });
+}
+int mgb_geo_field_energy_host(mgb_geo g, int B, const double* const* z, int S, int u, int s, double p, const double* p_nodal,
+                              const double* f, int f_rows, double* out, double* flux) {
+  return guard([&] {
+    need(g && z && out, "geo_field_energy_host: null argument");
+    need_energy_shape("geo_field_energy_host", B, S, u, s, p, f_rows, f != nullptr);
+    need(s >= 0, "geo_field_energy_host: column s outside [0, S)");
+    for (int b = 0; b < B; ++b) need(z[b] != nullptr, "geo_field_energy_host: null field");
+    need(g->g.w.size() == (size_t)g->g.n, "geo_field_energy_host: the geometry must carry one weight per node");
+    if (p_nodal)
+      for (int i = 0; i < g->g.n; ++i) need(good_q(p_nodal[i]), "geo_field_energy_host: every p_nodal must be finite and >= 1");
+    const interp::Locator L = interp::build_locator(g->g);
+    energy::Args A;
+    A.own = L.view(L.cellptr.data(), L.cellelem.data(), g->g.x.data());
+    A.w = g->g.w.data();
+    A.p_nodal = p_nodal;
+    A.p = p;
+    A.z = z;
+    A.f = f;
+    A.f_stride = f && f_rows == B && B > 1 ? L.n : 0;
+    A.n = L.n, A.S = S, A.u = u, A.s = s, A.B = B;
+    energy::field_energy_host(L.dim, L.k, A, out, flux);
+  });
+}
+int mgb_geo_field_flux(mgb_locator loc, mgb_vec z, int S, int u, double p, mgb_vec p_nodal, mgb_vec flux) {
+  return guard([&] {
+    need(loc && z && flux, "geo_field_flux: null argument");
+    need_energy_shape("geo_field_flux", 1, S, u, -1, p, 1, false);
+    need(loc->ctx->ctx.world == 1, "geo_field_flux: sharded contexts are not supported");
+    const interp::Locator& L = loc->loc;
+    need(z->n == (long long)L.n * S, "geo_field_flux: z must hold n x S values");
+    need(flux->n == (long long)L.n * L.dim, "geo_field_flux: flux must hold n x dim values");
+    need(!p_nodal || p_nodal->n == L.n, "geo_field_flux: p_nodal must hold n values");
+    need(z->ctx == loc->ctx && flux->ctx == loc->ctx && (!p_nodal || p_nodal->ctx == loc->ctx),
+         "geo_field_flux: vectors of another context");
+    need(z != flux, "geo_field_flux: flux must not be z");
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    energy::Args A;
+    A.own = L.view(loc->cellptr.p, loc->cellelem.p, loc->x.p);
+    A.w = loc->w.p;
+    A.p_nodal = p_nodal ? p_nodal->buf.p : nullptr;
+    A.p = p;
+    A.n = L.n, A.S = S, A.u = u, A.B = 1;
+    energy::launch_field_flux(loc->ctx->ctx.stream, L.dim, L.k, A, z->buf.p, flux->buf.p);
+    hip_check(hipGetLastError(), "geo_field_flux launch");
   });
 }
 
