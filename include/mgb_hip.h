@@ -431,6 +431,69 @@ int mgb_geo_field_energy_host(mgb_geo g, int B, const double* const* z /* B arra
  * does not wait on the host (there is no slack column here: the u == s rule does not apply) */
 int mgb_geo_field_flux(mgb_locator loc, mgb_vec z, int S, int u, double p, mgb_vec p_nodal_or_null, mgb_vec flux);
 
+/* ---- boundary facets of a geometry and boundary integrals of p-Laplace solutions --------------------------------------- *
+ * The elements are broken and their quadrature is nodal: every node of a boundary facet is a row of x and z already, so the
+ * boundary rule of a geometry is a list of nf facets of q nodes each: q global rows, q weights omega, the outward unit normal n,
+ * the measure and the centre of the facet, and its own element.  Built once per geometry, on the host.
+ * Finding the boundary: a facet of an element is a boundary facet when the sorted tuple of the continuous dofs of its CORNER
+ * nodes occurs in exactly one element.  The dofs are the columns of subspaces "full" at the finest level, which must have
+ * exactly one entry of value 1 per row.  Facets come in ascending (element, local facet) order:
+ *   1-D  local facets = local nodes 0, 1              q = 1          omega = 1                  n = sign(x - element centre)
+ *   2-D  edge i = local rows i, 3 + i, (i + 1) % 3    q = 3          |e| (1/6, 4/6, 1/6)        n perpendicular to v_a -> v_b,
+ *        (v_i, m_{i,i+1}, v_{i+1}), i = 0..2                         (Simpson)                  n . (midpoint - centroid) > 0
+ *   3-D  x-, x+, y-, y+, z-, z+: the (k+1)^2 nodes    q = (k+1)^2    area x the tensor of the   n = +- the axis, by
+ *        of the side in ascending local index                        closed Newton-Cotes        sign(face coordinate - element
+ *                                                                    weights of degree k        centre)
+ * The measure of a facet is 1, |e|, the face area; its centre the node, the edge midpoint, the face centre.
+ * MGB_E_ARG: a null argument; a geometry without a full subspace, or whose finest full subspace has not one row per node with
+ * exactly one entry 1; a corner tuple that occurs more than twice (non-manifold mesh); elements the locator refuses.
+ *
+ * Boundary integrals.  At facet node j of facet f, row i = nodes[f q + j], of a field z (n x S row-major, as for
+ * mgb_geo_field_energy; single-GPU contexts, fp64):
+ *   sigma_i = |grad u|^(p_i - 2) grad u at x_i in i's OWN element (the arithmetic of mgb_geo_field_flux),
+ *   sn = sigma_i . n_f,   t = sigma_i - sn n_f   (the tangential part).
+ * Per field one row of MGB_BOUNDARY_COLS doubles
+ *   [0] sum omega sn      the flow through the selected facets,   int sigma . n ds
+ *   [1] sum omega u_i     int u ds  (divide by [2] for the mean of the trace)
+ *   [2] sum omega         the measure of the selected facets
+ *   [3] max |sn|          the largest normal flux
+ *   [4] max |t|_2         the largest tangential flux
+ * mask (nf bytes on the HOST, copied on the context stream; null: every facet): a facet whose byte is 0 is left out of every
+ * sum and maximum.  An empty selection gives five zeros.  facet_flux (host, B x nf; null: not wanted): sum_j omega sn of every
+ * facet, its q terms added in ascending j; 0 for a facet left out.
+ * A SELECTED node whose u_i or sigma_i is not finite, or whose exponent is not a finite real >= 1, makes all five results of
+ * that field NaN (and the value of its facet); it is never dropped.  Nodes off the selected facets are not looked at.  Other
+ * fields of the batch are unaffected, bit for bit.
+ * Batching: B >= 1 fields are reduced by ONE pair of launches: partials on a grid (ceil(nf / (256 / q)), B) of 256 threads, one
+ * thread per (facet, facet node), whole facets per workgroup; then one workgroup per field that combines its partials in
+ * ascending workgroup order.  No atomics; a field's result depends on the facet list and the mask alone, not on B or on its place
+ * in the batch: a batch returns the bits of B calls with B = 1, and a call repeated returns the same bits.  The per-node
+ * arithmetic is compiled with fp contraction off, in the kernels and in the host restatement.
+ * MGB_E_ARG, before anything is launched: a null argument or field; B < 1 (device: B > 65535); S < 1; p not finite or < 1;
+ * u outside [0, S); a vector whose length is not n x S (p_nodal: n); vectors of another context; a sharded context. */
+#define MGB_BOUNDARY_COLS 5
+typedef struct mgb_boundary_s* mgb_boundary;   /* boundary facets of a geometry, device resident */
+/* the locator must be the one of geometry g and must outlive the boundary */
+int mgb_boundary_create(mgb_locator loc, mgb_geo g, mgb_boundary* out);
+int mgb_boundary_destroy(mgb_boundary b);
+int mgb_boundary_dims(mgb_boundary b, int* nf, int* q, int* dim);
+/* host arrays, each nullable: element nf, nodes nf x q, weights nf x q, normal nf x dim, measure nf, centre nf x dim */
+int mgb_boundary_get(mgb_boundary b, int32_t* element, int32_t* nodes, double* weights, double* normal, double* measure,
+                     double* centre);
+/* two launches on the context stream; the results are copied to the host and the call waits for them */
+int mgb_boundary_flux(mgb_boundary b, int B, const mgb_vec* z /* B vectors of n x S */, int S, int u, double p,
+                      mgb_vec p_nodal_or_null, const unsigned char* mask_host_or_null, double* facet_flux_host_or_null /* B x nf */,
+                      double* out_host /* B x MGB_BOUNDARY_COLS */);
+/* host only (no context, no GPU): the facet list of a geometry ... */
+int mgb_geo_boundary_dims(mgb_geo g, int* nf, int* q, int* dim);
+int mgb_geo_boundary_get(mgb_geo g, int32_t* element, int32_t* nodes, double* weights, double* normal, double* measure,
+                         double* centre);
+/* ... and the host restatement: the same per-node routine on host arrays, field after field, summed serially in ascending
+ * (facet, facet node) order */
+int mgb_geo_boundary_flux_host(mgb_geo g, int B, const double* const* z /* B arrays of n x S */, int S, int u, double p,
+                               const double* p_nodal_or_null, const unsigned char* mask_or_null,
+                               double* facet_flux_or_null /* B x nf */, double* out /* B x MGB_BOUNDARY_COLS */);
+
 /* ---- host-only symbolic helpers (no GPU needed; used by the CPU test-suite) ----------------- */
 
 typedef struct mgb_plan_s* mgb_plan;  /* symbolic products of one level: R, B=D*R, B', Hessian plan T */

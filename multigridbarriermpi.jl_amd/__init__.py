@@ -26,7 +26,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from . import _lib
-from ._lib import MGBError, call, dptr, f64, i32, iptr
+from ._lib import MGBError, call, dptr, f64, i32, iptr, u8ptr
 
 import ctypes as C
 
@@ -38,6 +38,7 @@ __all__ = [
     "_raw_array", "_to_cpu_array", "MGBError", "device_count", "AMG", "amg", "hcat", "BarrierFn", "barrier_functions",
     "interpolate", "sample_grid", "norms", "error", "convergence", "FieldNorms", "Convergence",
     "energy", "flux", "Energy",
+    "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
 ]
 
 
@@ -560,8 +561,16 @@ class Geometry:
     _geo: object = field(default=None, repr=False)     # mgb_geo handle (MPI geometries only)
     _geo_ref: object = field(default=None, repr=False) # shared owner of that handle, when the library built the geometry
     _locator: object = field(default=None, repr=False) # mgb_locator handle, made by the first interpolate() and freed here
+    _boundary: object = field(default=None, repr=False)      # Boundary (host arrays), made by the first boundary()
+    _boundary_dev: object = field(default=None, repr=False)  # mgb_boundary handle, made by the first boundary_flux(); it uses the locator
 
     def __del__(self):
+        try:
+            if self._boundary_dev is not None:
+                _lib.load().mgb_boundary_destroy(self._boundary_dev)
+                self._boundary_dev = None
+        except Exception:
+            pass
         try:
             if self._locator is not None:
                 _lib.load().mgb_locator_destroy(self._locator)
@@ -1999,6 +2008,137 @@ def flux(obj, p, u=0, z=None, k=-1) -> HPCMatrix:
     call("mgb_geo_field_flux", loc, zv.handle, S, u, p0, pv.handle if pv is not None else None, out._v.handle)
     out._inputs = (zv, pv)      # the launch is not waited for: what it reads lives as long as what it writes
     return out
+
+
+# --------------------------------------------------------------------------- boundary facets and boundary integrals
+
+
+@dataclass
+class Boundary:
+    """The boundary facets of a geometry, in ascending (element, local facet) order (contract in include/mgb_hip.h, DESIGN.md
+    section 4h): `element` (nf,) the own element of a facet, `nodes` (nf, q) its rows of x, `weights` (nf, q) the facet
+    quadrature weights at those rows, `normal` (nf, dim) the outward unit normal, `measure` (nf,), `centre` (nf, dim)."""
+    element: np.ndarray
+    nodes: np.ndarray
+    weights: np.ndarray
+    normal: np.ndarray
+    measure: np.ndarray
+    centre: np.ndarray
+
+    def __len__(self):
+        return len(self.element)
+
+
+@dataclass
+class BoundaryFlux:
+    """Result of boundary_flux(), by the nodal rule on the selected boundary facets: `flux` = int sigma . n ds with sigma =
+    |grad u|^(p-2) grad u, `trace` = int u ds (trace / measure is the mean of the trace), `measure` = int ds, `normal_max` =
+    max |sigma . n|, `tangential_max` = max |sigma - (sigma . n) n|.  Floats for one field; arrays of len(ts) for a ParabolicSOL,
+    whose `ts` is carried.  `facets` (per_facet=True): int_facet sigma . n of every facet, (nf,) or (len(ts), nf)."""
+    flux: object
+    trace: object
+    measure: object
+    normal_max: object
+    tangential_max: object
+    ts: Optional[np.ndarray] = None
+    facets: Optional[np.ndarray] = None
+
+
+def boundary(geometry: Geometry) -> Boundary:
+    """The boundary facets of a native or a device geometry, found on the host from subspaces["full"] at the finest level
+    (csrc/boundary.hpp) and kept on the geometry."""
+    if not isinstance(geometry, Geometry):
+        raise TypeError("boundary: expected a Geometry")
+    if geometry._boundary is not None:
+        return geometry._boundary
+    h, own = geometry._geo, False
+    if h is None:                                                        # a native geometry: x, w and the finest full subspace
+        x = f64(np.asarray(geometry.x))
+        x = x.reshape(x.shape[0], -1)
+        w, L = f64(geometry.w), len(geometry.refine)
+        h = C.c_void_p()
+        call("mgb_geo_create", x.shape[0], x.shape[1], L, int(geometry.discretization.get("block", 1)), dptr(x), dptr(w), C.byref(h))
+        own = True
+    try:
+        if own and "full" in geometry.subspaces:
+            S = sp.csr_matrix(geometry.subspaces["full"][L - 1], dtype=np.float64)
+            S.sort_indices()
+            S.sum_duplicates()
+            rp, ci, va = i32(S.indptr), i32(S.indices), f64(S.data)
+            call("mgb_geo_set_matrix", h, ("sub:full:%d" % (L - 1)).encode(), S.shape[0], S.shape[1], iptr(rp), iptr(ci), dptr(va))
+        nf, q, dim = C.c_int(), C.c_int(), C.c_int()
+        call("mgb_geo_boundary_dims", h, C.byref(nf), C.byref(q), C.byref(dim))
+        nf, q, dim = nf.value, q.value, dim.value
+        b = Boundary(np.empty(nf, dtype=np.int32), np.empty((nf, q), dtype=np.int32), np.empty((nf, q)), np.empty((nf, dim)),
+                     np.empty(nf), np.empty((nf, dim)))
+        call("mgb_geo_boundary_get", h, iptr(b.element), iptr(b.nodes), dptr(b.weights), dptr(b.normal), dptr(b.measure), dptr(b.centre))
+    finally:
+        if own:
+            call("mgb_geo_destroy", h)
+    geometry._boundary = b
+    return b
+
+
+def _boundary_selection(where, b: Boundary, who):
+    """None or the (nf,) uint8 mask of `where`: a boolean (nf,) array or a callable on a facet centre."""
+    if where is None:
+        return None
+    if callable(where):
+        return np.array([1 if where(c) else 0 for c in b.centre], dtype=np.uint8).reshape(len(b))
+    m = np.asarray(where)
+    if m.dtype != np.bool_ or m.shape != (len(b),):
+        raise ValueError("%s: where must be None, a boolean array of shape (nf,) = (%d,) or a callable on a facet centre, got %s %r"
+                         % (who, len(b), m.dtype, tuple(m.shape)))
+    return np.ascontiguousarray(m, dtype=np.uint8)
+
+
+def boundary_flux(obj, p, u=0, z=None, where=None, per_facet=False) -> BoundaryFlux:
+    """Flow rate int sigma . n ds, int u ds, measure and the largest normal and tangential flux of a solution on its boundary
+    facets, sigma = |grad u|^(p-2) grad u, reduced on the device (csrc/boundary.hip; contract in include/mgb_hip.h and
+    DESIGN.md section 4h).  `obj`, `p`, `u`, `z`: as for energy -- an AMGBSOL, a device Geometry with `z=`, or a ParabolicSOL,
+    whose len(ts) snapshots are reduced by ONE pair of launches.  `where` selects facets: None (all of them), a boolean (nf,)
+    array in the order of boundary(geometry), or a callable on a facet centre.  `per_facet=True` also returns every facet's own
+    integral."""
+    ts = None
+    if isinstance(obj, ParabolicSOL):
+        if z is not None:
+            raise ValueError("boundary_flux: z= does not go with a ParabolicSOL (its snapshots are the fields)")
+        geometry, fields, ts = obj.geometry, list(obj.u), np.asarray(obj.ts)
+        if len(fields) != len(ts) or not fields:
+            raise ValueError("boundary_flux: the ParabolicSOL has %d snapshots for %d times" % (len(fields), len(ts)))
+    elif isinstance(obj, (AMGBSOL, Geometry)):
+        geometry, z = _field_of(obj, "boundary_flux", z)
+        fields = [z]
+    else:
+        raise TypeError("boundary_flux: expected an AMGBSOL, a ParabolicSOL or a Geometry")
+    if geometry._geo is None:
+        raise TypeError("boundary_flux: geometry must come from native_to_mpi / fem*d_mpi")
+    if geometry.x.backend.world > 1:
+        raise NotImplementedError("boundary_flux: sharded contexts (world > 1) are not supported")
+    loc, backend = _locator_of(geometry)
+    b = boundary(geometry)
+    if geometry._boundary_dev is None:
+        h = C.c_void_p()
+        call("mgb_boundary_create", loc, geometry._geo, C.byref(h))
+        geometry._boundary_dev = h
+    vecs = [_nodal_values(geometry, zk, backend, "boundary_flux") for zk in fields]
+    B, S = len(vecs), vecs[0][1]
+    if any(Sk != S for _, Sk in vecs):
+        raise ValueError("boundary_flux: the snapshots have different numbers of columns")
+    u = _energy_column(u, S, "u", "boundary_flux")
+    x = np.asarray(_to_cpu_array(geometry.x)).reshape(len(geometry.w), -1)
+    p0, pn = _energy_exponent(p, x, "boundary_flux")
+    mask = _boundary_selection(where, b, "boundary_flux")
+    pv = HPCVector(pn, backend) if pn is not None else None
+    table = (C.c_void_p * B)(*[v.handle.value for v, _ in vecs])
+    out = np.empty((B, 5))
+    facets = np.empty((B, len(b))) if per_facet else None
+    call("mgb_boundary_flux", geometry._boundary_dev, B, table, S, u, p0, pv.handle if pv is not None else None, u8ptr(mask),
+         dptr(facets), dptr(out))
+    cols = [out[:, k].copy() for k in range(5)]
+    if ts is None:
+        return BoundaryFlux(*[float(c[0]) for c in cols], facets=facets[0] if per_facet else None)
+    return BoundaryFlux(*cols, ts=ts, facets=facets)
 
 
 def mpi_to_native(obj):

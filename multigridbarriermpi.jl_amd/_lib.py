@@ -14,6 +14,7 @@ c_i32_p = C.POINTER(C.c_int32)
 c_dbl_p = C.POINTER(C.c_double)
 c_flt_p = C.POINTER(C.c_float)
 c_ll_p = C.POINTER(C.c_longlong)
+c_u8_p = C.POINTER(C.c_ubyte)
 c_str_arr = C.POINTER(C.c_char_p)
 H = C.c_void_p
 # mgb_allreduce_fn: int (*)(void* user, double* dev_ptr, long long count); the pointer is passed as an integer
@@ -138,6 +139,14 @@ PROTOTYPES = {
     "mgb_geo_field_energy_host": [H, C.c_int, C.POINTER(c_dbl_p), C.c_int, C.c_int, C.c_int, C.c_double, c_dbl_p, c_dbl_p, C.c_int,
                                   c_dbl_p, c_dbl_p],
     "mgb_geo_field_flux": [H, H, C.c_int, C.c_int, C.c_double, H, H],
+    "mgb_boundary_create": [H, H, C.POINTER(H)],
+    "mgb_boundary_destroy": [H],
+    "mgb_boundary_dims": [H, c_int_p, c_int_p, c_int_p],
+    "mgb_boundary_get": [H, c_i32_p, c_i32_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p],
+    "mgb_boundary_flux": [H, C.c_int, C.POINTER(H), C.c_int, C.c_int, C.c_double, H, c_u8_p, c_dbl_p, c_dbl_p],
+    "mgb_geo_boundary_dims": [H, c_int_p, c_int_p, c_int_p],
+    "mgb_geo_boundary_get": [H, c_i32_p, c_i32_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p],
+    "mgb_geo_boundary_flux_host": [H, C.c_int, C.POINTER(c_dbl_p), C.c_int, C.c_int, C.c_double, c_dbl_p, c_u8_p, c_dbl_p, c_dbl_p],
     "mgb_plan_prolongation": [H, H, c_int_p, c_int_p, c_int_p, c_i32_p, c_i32_p, c_dbl_p],
     "mgb_amg_solve": [H, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int],
     "mgb_amg_sol_info": [H, c_int_p, c_dbl_p, c_dbl_p, c_ll_p],
@@ -209,6 +218,10 @@ def dptr(a):
 
 def iptr(a):
     return None if a is None else a.ctypes.data_as(c_i32_p)
+
+
+def u8ptr(a):
+    return None if a is None else a.ctypes.data_as(c_u8_p)
 
 
 def f64(a):

@@ -1,0 +1,114 @@
+// Boundary integrals of nodal fields on gfx950.  B fields on one geometry are reduced over its boundary
+// facets by ONE pair of plain launches on one stream, the way energy.hip reduces over the nodes:
+//   boundary_kernel<DIM, K>: grid (workgroups(nf, q), B); a workgroup takes 256 / q whole facets, one thread per (facet, facet
+//     node) -- thread t is node t % q of the workgroup's facet t / q, so the facet tables are read contiguously and a facet never
+//     straddles two workgroups; threads past the last whole facet, and those of facets the mask leaves out, contribute the
+//     identity.  Each thread runs boundary.hpp's Node (sigma through energy.hpp's Node, sigma . n, the tangential part); the
+//     workgroup reduces the five columns -- wave shuffles, then LDS across the four waves -- and writes ONE partial row per
+//     (field, workgroup).  With a per-facet output the threads leave omega sigma . n in LDS and node 0 of every facet sums its
+//     facet's q values in ascending order.
+//   boundary_finish: grid (B); the workgroup of a field combines that field's partials in ascending workgroup order.
+// What a field's result is made of depends on the facet list alone, never on B or on the field's place in the batch.  No atomics
+// and no hand-off between workgroups inside a launch; every word is written by one thread with a vector store.
+#include "boundary.hpp"
+
+namespace mgb {
+namespace boundary {
+namespace {
+
+static_assert(kThreads == 256, "four waves of 64");
+constexpr int kWaves = kThreads / 64;
+
+// Reduce c[0..4] over the workgroup; the result is valid in thread 0.
+__device__ inline void block_combine(double* c, double (*red)[kCols]) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    double t[kCols];
+#pragma unroll
+    for (int k = 0; k < kCols; ++k) t[k] = __shfl_down(c[k], o, 64);
+    combine(c, t);
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < kCols; ++k) red[wave][k] = c[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int v = 1; v < kWaves; ++v) combine(c, red[v]);
+  }
+}
+
+template <int DIM, int K>
+__global__ void __launch_bounds__(kThreads) boundary_kernel(Args A, double* __restrict__ partials, double* __restrict__ facet_flux) {
+  __shared__ double red[kWaves][kCols];
+  __shared__ double per_node[kThreads];
+  const int q = A.q, fpw = kThreads / q;
+  const int lf = threadIdx.x / q, j = threadIdx.x - lf * q;
+  const long long f = (long long)blockIdx.x * fpw + lf;
+  const int b = blockIdx.y;
+  const bool mine = lf < fpw && f < A.nf;      // idle threads stay for the reduction and contribute nothing
+  double c[kCols];
+  identity(c);
+  if (mine && (!A.mask || A.mask[f])) Node<DIM, K>::contributions(A, A.E.z[b], (int)f, j, c);
+  if (facet_flux) {      // uniform over the launch
+    per_node[threadIdx.x] = c[0];
+    __syncthreads();
+    if (mine && j == 0) {
+      double s = 0.0;
+      for (int t = 0; t < q; ++t) s += per_node[threadIdx.x + t];
+      facet_flux[(size_t)b * A.nf + f] = s;
+    }
+  }
+  block_combine(c, red);
+  if (threadIdx.x == 0) {
+    double* row = partials + ((size_t)b * gridDim.x + blockIdx.x) * kCols;
+#pragma unroll
+    for (int k = 0; k < kCols; ++k) row[k] = c[k];
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) boundary_finish(const double* __restrict__ partials, int nwg, double* __restrict__ out) {
+  __shared__ double red[kWaves][kCols];
+  const int b = blockIdx.x;
+  const int chunk = (nwg + kThreads - 1) / kThreads;
+  const long long b0 = (long long)threadIdx.x * chunk;
+  const long long b1 = b0 + chunk < nwg ? b0 + chunk : nwg;
+  double c[kCols];
+  identity(c);
+  for (long long g = b0; g < b1; ++g) combine(c, partials + ((size_t)b * nwg + g) * kCols);
+  block_combine(c, red);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < kCols; ++k) out[(size_t)b * kCols + k] = c[k];
+  }
+}
+
+struct LaunchFlux {
+  hipStream_t stream;
+  Args A;
+  double* scratch;
+  double* facet_flux;
+  template <int DIM, int K>
+  void operator()() const {
+    const long long nwg = workgroups(A.nf, A.q);
+    hipLaunchKernelGGL((boundary_kernel<DIM, K>), dim3((unsigned)nwg, (unsigned)A.E.B), dim3(kThreads), 0, stream, A, scratch,
+                       facet_flux);
+    hipLaunchKernelGGL(boundary_finish, dim3((unsigned)A.E.B), dim3(kThreads), 0, stream, scratch, (int)nwg,
+                       scratch + (size_t)nwg * A.E.B * kCols);
+  }
+};
+
+}  // namespace
+
+void launch_boundary_flux(hipStream_t stream, int dim, int k, const Args& A, double* scratch, double* facet_flux) {
+  if (A.E.n <= 0 || A.E.S <= 0 || A.E.B <= 0 || A.E.B > 65535) throw ArgError("boundary_flux: empty field, or more than 65535 fields");
+  if (A.nf < 0 || A.q < 1 || A.q > kThreads) throw ArgError("boundary_flux: bad facet list");
+  if (workgroups(A.nf, A.q) > 2147483647LL) throw ArgError("boundary_flux: too many facets");
+  LaunchFlux l{stream, A, scratch, facet_flux};
+  interp::dispatch(dim, k, l);
+}
+
+}  // namespace boundary
+}  // namespace mgb

@@ -1,0 +1,272 @@
+// Boundary facets of a geometry and boundary integrals of p-Laplace solutions: the facet list, built
+// ONCE per geometry on the host, and what ONE facet node contributes, written ONCE.  The gfx950 kernels (boundary.hip) and the
+// host restatement (mgb_geo_boundary_flux_host) both run Node below; sigma is energy.hpp's Node::flux, combine is norms.hpp's.
+//   The elements are broken and their quadrature is nodal: every node of a boundary facet is a row of x and z already, so a
+//   boundary rule is a list of (row, weight) pairs per facet plus the facet's outward unit normal.
+//   A facet of an element is a BOUNDARY facet when the sorted tuple of the continuous dofs (subspaces["full"][L-1], one entry 1
+//   per row) of its corner nodes occurs in exactly one element.  Facets come in ascending (element, local facet) order.
+//     1-D: local facets = local nodes 0, 1; q = 1; weight 1; normal sign(x - element centre).
+//     2-D: edge i = (v_i, m_{i,i+1}, v_{i+1}) = local rows i, 3 + i, (i + 1) % 3; q = 3; Simpson |e| (1/6, 4/6, 1/6); the normal is
+//          perpendicular to v_a -> v_b with n . (edge midpoint - centroid of the own triangle) > 0.
+//     3-D: x-, x+, y-, y+, z-, z+; the (k+1)^2 nodes of the side in ascending local index; face area times the tensor of the
+//          closed Newton-Cotes weights of degree k (fem3d_native's); normal +- the axis by sign(face coordinate - element centre).
+//   At facet node j of facet f, row i = nodes[f q + j], for a field z (n x S row-major):
+//     sigma = |grad u|^(p-2) grad u in i's own element (energy::Node::init + flux),  sn = sigma . n,  t = sigma - sn n.
+//   Five contributions: omega sn | omega u_i | omega | |sn| | |t|_2   (three sums, two NaN-sticky maxima).
+//   A non-finite u_i or sigma, or an exponent that is not a finite real >= 1, makes all five NaN.  A facet left out by the mask
+//   contributes nothing; its per-facet value is 0.  The per-facet value is the sum of omega sn over j = 0..q-1 in that order.
+// The arithmetic of Node::contributions is kept as written (fp contract off), as energy.hpp's is.
+#pragma once
+#include <array>
+
+#include "energy.hpp"
+
+namespace mgb {
+namespace boundary {
+
+constexpr int kCols = 5;      // MGB_BOUNDARY_COLS
+static_assert(kCols == norms::kCols, "norms::combine takes three sums, then two NaN-sticky maxima: the columns of this module");
+using norms::combine;
+
+// the facet list of one geometry, on the host
+struct Facets {
+  int dim = 0, k = 0, q = 0, nf = 0;
+  std::vector<int> element;        // nf
+  std::vector<int> nodes;          // nf x q global rows
+  std::vector<double> weights;     // nf x q
+  std::vector<double> normal;      // nf x dim outward unit normals
+  std::vector<double> measure;     // nf
+  std::vector<double> centre;      // nf x dim
+};
+
+// what all fields of one call share
+struct Args {
+  energy::Args E;                          // geometry, exponent, the table of fields, S and u (s, f unused)
+  const int* nodes = nullptr;              // nf x q
+  const double* weights = nullptr;         // nf x q
+  const double* normal = nullptr;          // nf x dim
+  const unsigned char* mask = nullptr;     // nf bytes or null: 0 leaves the facet out
+  int nf = 0, q = 0;
+};
+
+// all five columns are sums of, or maxima over, non-negative or signed terms whose empty value is 0
+MGB_HD void identity(double* c) { c[0] = c[1] = c[2] = c[3] = c[4] = 0.0; }
+
+template <int DIM, int K>
+struct Node {
+  // the five contributions of facet node j of facet f for the field z
+  MGB_HD static void contributions(const Args& A, const double* z, int f, int j, double* c) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const int i = A.nodes[(size_t)f * A.q + j];
+    const double om = A.weights[(size_t)f * A.q + j];
+    const double* n = A.normal + (size_t)f * DIM;
+    energy::Node<DIM, K> N;
+    N.init(A.E, i);
+    double sigma[DIM];
+    N.flux(z, A.E.S, A.E.u, sigma);
+    const double ui = z[(size_t)i * A.E.S + A.E.u];
+    double sn = 0.0;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) sn += sigma[k] * n[k];
+    double ts = 0.0;
+    bool good = N.p >= 1.0;
+    good = good & interp::finite(N.p);
+    good = good & interp::finite(ui);
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {
+      const double t = sigma[k] - sn * n[k];
+      ts += t * t;
+      good = good & interp::finite(sigma[k]);
+    }
+    if (!good) {
+      c[0] = c[1] = c[2] = c[3] = c[4] = std::numeric_limits<double>::quiet_NaN();
+      return;
+    }
+    c[0] = om * sn;
+    c[1] = om * ui;
+    c[2] = om;
+    c[3] = fabs(sn);
+    c[4] = sqrt(ts);
+  }
+};
+
+// host restatement: the same per-node routine, serially, field after field in ascending (facet, facet node) order
+struct HostFlux {
+  Args A;
+  double* out;          // B x kCols
+  double* facets;       // B x nf or null
+  template <int DIM, int K>
+  void operator()() const {
+    for (int b = 0; b < A.E.B; ++b) {
+      double* acc = out + (size_t)b * kCols;
+      identity(acc);
+      for (int f = 0; f < A.nf; ++f) {
+        double fsum = 0.0;
+        if (!A.mask || A.mask[f])
+          for (int j = 0; j < A.q; ++j) {
+            double c[kCols];
+            Node<DIM, K>::contributions(A, A.E.z[b], f, j, c);
+            combine(acc, c);
+            fsum += c[0];
+          }
+        if (facets) facets[(size_t)b * A.nf + f] = fsum;
+      }
+    }
+  }
+};
+
+inline void boundary_flux_host(int dim, int k, const Args& A, double* out, double* facets) {
+  HostFlux h{A, out, facets};
+  interp::dispatch(dim, k, h);
+}
+
+// ---------------------------------------------------------------------------------------------------- host setup
+// continuous dof of every row from subspaces["full"][L-1]
+inline std::vector<int> continuous_dofs(const GeometryHost& g) {
+  auto it = g.subspaces.find("full");
+  if (it == g.subspaces.end() || g.L < 1 || (int)it->second.size() < g.L)
+    throw ArgError("boundary: the geometry has no full subspace");
+  const Csr& F = it->second[g.L - 1];
+  if (F.rows != g.n || (int)F.rowptr.size() != g.n + 1) throw ArgError("boundary: the finest full subspace must have one row per node");
+  std::vector<int> dof((size_t)g.n);
+  for (int r = 0; r < g.n; ++r) {
+    if (F.rowptr[r + 1] - F.rowptr[r] != 1 || F.vals[F.rowptr[r]] != 1.0)
+      throw ArgError("boundary: the finest full subspace must have exactly one entry of value 1 per row");
+    dof[r] = F.colidx[F.rowptr[r]];
+  }
+  return dof;
+}
+
+// local rows of local facet lf in ascending local index, and the positions (within them) of its corner nodes
+inline void local_facet(int dim, int k, int lf, std::vector<int>& rows, std::vector<int>& corners) {
+  rows.clear();
+  corners.clear();
+  if (dim == 1) {
+    rows = {lf};
+    corners = {0};
+  } else if (dim == 2) {
+    rows = {lf, 3 + lf, (lf + 1) % 3};
+    corners = {0, 2};
+  } else {
+    const int m1 = k + 1, axis = lf / 2, fixed = (lf & 1) ? k : 0;
+    for (int b = 0; b < m1; ++b)
+      for (int a = 0; a < m1; ++a) {      // a runs along the lower of the two free axes: ascending local index
+        int idx[3];
+        idx[axis] = fixed;
+        idx[axis == 0 ? 1 : 0] = a;
+        idx[axis == 2 ? 1 : 2] = b;
+        if ((a == 0 || a == k) && (b == 0 || b == k)) corners.push_back((int)rows.size());
+        rows.push_back(idx[0] + m1 * (idx[1] + m1 * idx[2]));
+      }
+  }
+}
+
+inline Facets build_facets(const GeometryHost& g) {
+  const interp::Locator L = interp::build_locator(g);      // validates x, dim, block and the shape of every element
+  const std::vector<int> dof = continuous_dofs(g);
+  const int dim = L.dim, k = L.k, block = L.block, nel = L.nel;
+  const int nlf = dim == 1 ? 2 : dim == 2 ? 3 : 6;
+  const int q = dim == 1 ? 1 : dim == 2 ? 3 : (k + 1) * (k + 1);
+  std::vector<std::vector<int>> rows(nlf), corners(nlf);
+  for (int lf = 0; lf < nlf; ++lf) local_facet(dim, k, lf, rows[lf], corners[lf]);
+  // (sorted corner dofs, element, local facet), sorted: facets with the same dofs are neighbours
+  struct Key {
+    std::array<int, 4> d;
+    int e, lf;
+  };
+  std::vector<Key> keys;
+  keys.reserve((size_t)nel * nlf);
+  for (int e = 0; e < nel; ++e)
+    for (int lf = 0; lf < nlf; ++lf) {
+      Key key{{-1, -1, -1, -1}, e, lf};
+      for (size_t c = 0; c < corners[lf].size(); ++c) key.d[c] = dof[(size_t)e * block + rows[lf][corners[lf][c]]];
+      std::sort(key.d.begin(), key.d.end());
+      keys.push_back(key);
+    }
+  std::sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) {
+    if (a.d != b.d) return a.d < b.d;
+    return a.e != b.e ? a.e < b.e : a.lf < b.lf;
+  });
+  std::vector<std::pair<int, int>> bnd;      // (element, local facet)
+  for (size_t i = 0; i < keys.size();) {
+    size_t j = i + 1;
+    while (j < keys.size() && keys[j].d == keys[i].d) ++j;
+    if (j - i > 2) throw ArgError("boundary: a facet is shared by more than two elements (non-manifold mesh)");
+    if (j - i == 2 && keys[i].e == keys[i + 1].e) throw ArgError("boundary: two facets of one element share their corner dofs");
+    if (j - i == 1) bnd.emplace_back(keys[i].e, keys[i].lf);
+    i = j;
+  }
+  std::sort(bnd.begin(), bnd.end());
+  Facets F;
+  F.dim = dim, F.k = k, F.q = q, F.nf = (int)bnd.size();
+  F.element.resize(F.nf);
+  F.nodes.resize((size_t)F.nf * q);
+  F.weights.resize((size_t)F.nf * q);
+  F.normal.assign((size_t)F.nf * dim, 0.0);
+  F.measure.resize(F.nf);
+  F.centre.resize((size_t)F.nf * dim);
+  const double nc[3][4] = {{0.5, 0.5, 0, 0}, {1.0 / 6, 4.0 / 6, 1.0 / 6, 0}, {1.0 / 8, 3.0 / 8, 3.0 / 8, 1.0 / 8}};      // fem3d_native's
+  for (int f = 0; f < F.nf; ++f) {
+    const int e = bnd[f].first, lf = bnd[f].second;
+    const double* xe = g.x.data() + (size_t)e * block * dim;
+    F.element[f] = e;
+    for (int j = 0; j < q; ++j) F.nodes[(size_t)f * q + j] = e * block + rows[lf][j];
+    double* w = F.weights.data() + (size_t)f * q;
+    double* n = F.normal.data() + (size_t)f * dim;
+    double* c = F.centre.data() + (size_t)f * dim;
+    if (dim == 2) {
+      const double* a = xe + 2 * rows[lf][0];
+      const double* m = xe + 2 * rows[lf][1];
+      const double* b = xe + 2 * rows[lf][2];
+      const double dx = b[0] - a[0], dy = b[1] - a[1], len = std::sqrt(dx * dx + dy * dy);
+      const double cx = (xe[0] + xe[2] + xe[4]) / 3.0, cy = (xe[1] + xe[3] + xe[5]) / 3.0;
+      n[0] = dy / len, n[1] = -dx / len;
+      if (n[0] * (m[0] - cx) + n[1] * (m[1] - cy) < 0.0) n[0] = -n[0], n[1] = -n[1];
+      w[0] = len * (1.0 / 6), w[1] = len * (4.0 / 6), w[2] = len * (1.0 / 6);
+      F.measure[f] = len;
+      c[0] = m[0], c[1] = m[1];
+    } else {
+      const double* lo = xe;                                   // first and last row: opposite corners of the box, in either order
+      const double* hi = xe + (size_t)(block - 1) * dim;
+      const int axis = dim == 1 ? 0 : lf / 2;
+      const double* p = xe + (size_t)rows[lf][0] * dim;        // a node of the facet: it carries the facet coordinate
+      double area = 1.0;
+      for (int d = 0; d < dim; ++d) {
+        c[d] = d == axis ? p[d] : 0.5 * (lo[d] + hi[d]);
+        if (d != axis) area *= std::fabs(hi[d] - lo[d]);
+      }
+      n[axis] = p[axis] > 0.5 * (lo[axis] + hi[axis]) ? 1.0 : -1.0;
+      F.measure[f] = area;
+      if (dim == 1) {
+        w[0] = 1.0;
+      } else {
+        const int m1 = k + 1;
+        for (int b = 0; b < m1; ++b)
+          for (int a = 0; a < m1; ++a) w[a + m1 * b] = area * (nc[k - 1][a] * nc[k - 1][b]);
+      }
+    }
+  }
+  return F;
+}
+
+// facets per workgroup (a facet never straddles two workgroups), workgroups per field, doubles of scratch of the two launches
+constexpr int kThreads = 256;
+inline int facets_per_workgroup(int q) { return kThreads / q; }
+inline long long workgroups(int nf, int q) {
+  const int fpw = facets_per_workgroup(q);
+  return nf > 0 ? ((long long)nf + fpw - 1) / fpw : 1;
+}
+inline size_t scratch_doubles(int nf, int q, int B) { return (size_t)(workgroups(nf, q) + 1) * B * kCols; }      // partials, then B x kCols results
+
+#if defined(__HIPCC__)
+// boundary.hip: two launches on `stream` -- partials on grid (workgroups, B), one thread per (facet, facet node), then one
+// workgroup per field that combines that field's partials in ascending workgroup order; all pointers of A are device pointers
+// (A.E.z a device table of B device pointers); the B x kCols results are at scratch + workgroups * B * kCols; facet_flux
+// (nullable): B x nf device doubles
+void launch_boundary_flux(hipStream_t stream, int dim, int k, const Args& A, double* scratch, double* facet_flux);
+#endif
+
+}  // namespace boundary
+}  // namespace mgb

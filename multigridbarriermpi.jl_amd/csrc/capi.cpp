@@ -8,6 +8,7 @@
 #include <thread>
 
 #include "amg.hpp"
+#include "boundary.hpp"
 #include "interp.hpp"
 #include "energy.hpp"
 #include "norms.hpp"
@@ -50,6 +51,15 @@ struct mgb_locator_s {
   DevBuf<long long> norm_counts;
   DevBuf<double> energy_scratch;                   // mgb_geo_field_energy: partials and results, grown on demand
   DevBuf<const double*> energy_table;              // ... and the device table of field pointers, uploaded per call
+};
+struct mgb_boundary_s {
+  mgb_locator_s* loc;      // not owned: the locator (x, w, context) must outlive the boundary
+  boundary::Facets F;
+  DevBuf<int> nodes;
+  DevBuf<double> weights, normal;
+  DevBuf<unsigned char> mask;                      // mgb_boundary_flux: the facet mask of the call
+  DevBuf<double> scratch, facet_scratch;           // ... partials and results, per-facet values, grown on demand
+  DevBuf<const double*> table;                     // ... and the device table of field pointers, uploaded per call
 };
 struct mgb_plan_s {
   LevelPlan plan;
@@ -1380,6 +1390,155 @@ int mgb_geo_field_flux(mgb_locator loc, mgb_vec z, int S, int u, double p, mgb_v
     A.n = L.n, A.S = S, A.u = u, A.B = 1;
     energy::launch_field_flux(loc->ctx->ctx.stream, L.dim, L.k, A, z->buf.p, flux->buf.p);
     hip_check(hipGetLastError(), "geo_field_flux launch");
+  });
+}
+
+// ---- boundary facets and boundary integrals of p-Laplace solutions (boundary.hpp / boundary.hip)
+namespace {
+void need_boundary_shape(const char* who, int B, int S, int u, double p) {
+  const std::string w(who);
+  if (B < 1) throw std::invalid_argument(w + ": B must be >= 1");
+  if (S < 1) throw std::invalid_argument(w + ": S must be >= 1");
+  if (!good_q(p)) throw std::invalid_argument(w + ": p must be finite and >= 1");
+  if (u < 0 || u >= S) throw std::invalid_argument(w + ": column u outside [0, S)");
+}
+void copy_facets(const boundary::Facets& F, int32_t* element, int32_t* nodes, double* weights, double* normal, double* measure,
+                 double* centre) {
+  if (element) std::copy(F.element.begin(), F.element.end(), element);
+  if (nodes) std::copy(F.nodes.begin(), F.nodes.end(), nodes);
+  if (weights) std::copy(F.weights.begin(), F.weights.end(), weights);
+  if (normal) std::copy(F.normal.begin(), F.normal.end(), normal);
+  if (measure) std::copy(F.measure.begin(), F.measure.end(), measure);
+  if (centre) std::copy(F.centre.begin(), F.centre.end(), centre);
+}
+}  // namespace
+int mgb_boundary_create(mgb_locator loc, mgb_geo g, mgb_boundary* out) {
+  return guard([&] {
+    need(loc && g && out, "boundary_create: null argument");
+    const interp::Locator& L = loc->loc;
+    need(L.n == g->g.n && L.dim == g->g.dim && L.block == g->g.block, "boundary_create: the locator belongs to another geometry");
+    auto* b = new mgb_boundary_s{loc, boundary::build_facets(g->g), {}, {}, {}, {}, {}, {}, {}};
+    try {
+      hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+      b->nodes.upload(b->F.nodes.data(), b->F.nodes.size());
+      b->weights.upload(b->F.weights.data(), b->F.weights.size());
+      b->normal.upload(b->F.normal.data(), b->F.normal.size());
+    } catch (...) {
+      delete b;
+      throw;
+    }
+    *out = b;
+  });
+}
+int mgb_boundary_destroy(mgb_boundary b) {
+  return guard([&] { delete b; });
+}
+int mgb_boundary_dims(mgb_boundary b, int* nf, int* q, int* dim) {
+  return guard([&] {
+    need(b, "boundary_dims: null boundary");
+    if (nf) *nf = b->F.nf;
+    if (q) *q = b->F.q;
+    if (dim) *dim = b->F.dim;
+  });
+}
+int mgb_boundary_get(mgb_boundary b, int32_t* element, int32_t* nodes, double* weights, double* normal, double* measure,
+                     double* centre) {
+  return guard([&] {
+    need(b, "boundary_get: null boundary");
+    copy_facets(b->F, element, nodes, weights, normal, measure, centre);
+  });
+}
+int mgb_boundary_flux(mgb_boundary bd, int B, const mgb_vec* z, int S, int u, double p, mgb_vec p_nodal,
+                      const unsigned char* mask_host, double* facet_flux_host, double* out_host) {
+  return guard([&] {
+    need(bd && z && out_host, "boundary_flux: null argument");
+    need_boundary_shape("boundary_flux", B, S, u, p);
+    mgb_locator_s* loc = bd->loc;
+    need(loc->ctx->ctx.world == 1, "boundary_flux: sharded contexts are not supported");
+    const interp::Locator& L = loc->loc;
+    const boundary::Facets& F = bd->F;
+    std::vector<const double*> table((size_t)B);
+    for (int b = 0; b < B; ++b) {
+      need(z[b] != nullptr, "boundary_flux: null field");
+      need(z[b]->n == (long long)L.n * S, "boundary_flux: every z must hold n x S values");
+      need(z[b]->ctx == loc->ctx, "boundary_flux: vectors of another context");
+      table[b] = z[b]->buf.p;
+    }
+    need(!p_nodal || p_nodal->n == L.n, "boundary_flux: p_nodal must hold n values");
+    need(!p_nodal || p_nodal->ctx == loc->ctx, "boundary_flux: vectors of another context");
+    need(B <= 65535, "boundary_flux: at most 65535 fields per call");
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const size_t nd = boundary::scratch_doubles(F.nf, F.q, B);
+    if (bd->scratch.n < nd) bd->scratch.alloc(nd);
+    const size_t nfac = (size_t)B * F.nf;
+    if (facet_flux_host && bd->facet_scratch.n < nfac) bd->facet_scratch.alloc(nfac);
+    bd->table.upload(table.data(), table.size());      // every earlier launch that read it has been waited for
+    if (mask_host && F.nf) {
+      if (bd->mask.n < (size_t)F.nf) bd->mask.alloc((size_t)F.nf);
+      hip_check(hipMemcpyAsync(bd->mask.p, mask_host, (size_t)F.nf, hipMemcpyHostToDevice, st), "H2D mask");
+    }
+    boundary::Args A;
+    A.E.own = L.view(loc->cellptr.p, loc->cellelem.p, loc->x.p);
+    A.E.w = loc->w.p;
+    A.E.p_nodal = p_nodal ? p_nodal->buf.p : nullptr;
+    A.E.p = p;
+    A.E.z = bd->table.p;
+    A.E.n = L.n, A.E.S = S, A.E.u = u, A.E.B = B;
+    A.nodes = bd->nodes.p;
+    A.weights = bd->weights.p;
+    A.normal = bd->normal.p;
+    A.mask = mask_host && F.nf ? bd->mask.p : nullptr;
+    A.nf = F.nf, A.q = F.q;
+    boundary::launch_boundary_flux(st, L.dim, L.k, A, bd->scratch.p, facet_flux_host && nfac ? bd->facet_scratch.p : nullptr);
+    hip_check(hipGetLastError(), "boundary_flux launch");
+    hip_check(hipStreamSynchronize(st), "sync boundary_flux");
+    const size_t nwg = (size_t)boundary::workgroups(F.nf, F.q);
+    hip_check(hipMemcpy(out_host, bd->scratch.p + nwg * B * boundary::kCols, (size_t)B * boundary::kCols * sizeof(double),
+                        hipMemcpyDeviceToHost), "D2H");
+    if (facet_flux_host && nfac)
+      hip_check(hipMemcpy(facet_flux_host, bd->facet_scratch.p, nfac * sizeof(double), hipMemcpyDeviceToHost), "D2H");
+  });
+}
+int mgb_geo_boundary_dims(mgb_geo g, int* nf, int* q, int* dim) {
+  return guard([&] {
+    need(g, "geo_boundary_dims: null geometry");
+    const boundary::Facets F = boundary::build_facets(g->g);
+    if (nf) *nf = F.nf;
+    if (q) *q = F.q;
+    if (dim) *dim = F.dim;
+  });
+}
+int mgb_geo_boundary_get(mgb_geo g, int32_t* element, int32_t* nodes, double* weights, double* normal, double* measure,
+                         double* centre) {
+  return guard([&] {
+    need(g, "geo_boundary_get: null geometry");
+    copy_facets(boundary::build_facets(g->g), element, nodes, weights, normal, measure, centre);
+  });
+}
+int mgb_geo_boundary_flux_host(mgb_geo g, int B, const double* const* z, int S, int u, double p, const double* p_nodal,
+                               const unsigned char* mask, double* facet_flux, double* out) {
+  return guard([&] {
+    need(g && z && out, "geo_boundary_flux_host: null argument");
+    need_boundary_shape("geo_boundary_flux_host", B, S, u, p);
+    for (int b = 0; b < B; ++b) need(z[b] != nullptr, "geo_boundary_flux_host: null field");
+    need(g->g.w.size() == (size_t)g->g.n, "geo_boundary_flux_host: the geometry must carry one weight per node");
+    const boundary::Facets F = boundary::build_facets(g->g);
+    boundary::Args A;
+    A.E.own.block = g->g.block;
+    A.E.own.nel = g->g.n / g->g.block;
+    A.E.own.x = g->g.x.data();
+    A.E.w = g->g.w.data();
+    A.E.p_nodal = p_nodal;
+    A.E.p = p;
+    A.E.z = z;
+    A.E.n = g->g.n, A.E.S = S, A.E.u = u, A.E.B = B;
+    A.nodes = F.nodes.data();
+    A.weights = F.weights.data();
+    A.normal = F.normal.data();
+    A.mask = mask;
+    A.nf = F.nf, A.q = F.q;
+    boundary::boundary_flux_host(F.dim, F.k, A, out, facet_flux);
   });
 }
 
