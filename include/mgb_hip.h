@@ -494,6 +494,43 @@ int mgb_geo_boundary_flux_host(mgb_geo g, int B, const double* const* z /* B arr
                                const double* p_nodal_or_null, const unsigned char* mask_or_null,
                                double* facet_flux_or_null /* B x nf */, double* out /* B x MGB_BOUNDARY_COLS */);
 
+/* ---- mixed boundary conditions: Dirichlet on part of the boundary, Neumann data on the rest ------- *
+ * Single-GPU contexts, fp64.
+ * Dirichlet subspace.  mgb_geo_dirichlet_on adds "sub:<name>:<l>" for every level l (read back with mgb_geo_matrix_info / _get;
+ * name it in the state variables of mgb_amg_create*).  The pinned rows are the rows of the selected boundary facets (the facet
+ * list of mgb_geo_boundary_get; facet_mask nf bytes, null = every facet); the set is closed, facet end points belong to it.  Per
+ * level, a column of "sub:full:<l>" is dropped when it has a non-zero value in a pinned row of the finest mesh (stored zeros do
+ * not count); kept columns keep their order and their bits, stored zeros included.  Every facet selected gives the matrices of
+ * "dirichlet", none those of "full".  MGB_E_ARG, nothing added: a null argument; the name is full, dirichlet or fixed, is
+ * already present, is empty or holds ':'; the geometry has no full subspace; a level of it is missing; a mesh that
+ * mgb_geo_boundary_get refuses.
+ * Neumann load.  The objective is sum_i w_i c_i . (Dz)_i, so  int_Gamma h u ds  is the addition of
+ *     l_i = (sum over the facet nodes (f, j) whose row is i of  omega_fj h_fj) / w_i
+ * to the (u, id) column of c at the boundary rows.  The facet list carries a row-sorted incidence table: the nb distinct rows of
+ * the facet nodes in ascending order, nb + 1 row starts, and the facet-node indices f q + j in ascending order within a row.
+ * For boundary row r the kernel and the host restatement add omega h over its incidences in table order, skipping the facets
+ * the mask leaves out (their h is not read: a NaN there is not seen), then divide once by w_r; a row with no selected incidence
+ * gives exactly 0.  fp contraction is off in both.  h holds B fields (time levels) of nf x q doubles in HOST memory, copied on
+ * the context stream like the mask; the output is compact, B x nb.  One launch on grid (ceil(nb / 256), B), one thread per
+ * distinct row; no atomics, no LDS; a batch returns the bits of its singles and a repeated call repeats.
+ * mgb_boundary_load_add: y[rows[j] stride + offset] += alpha load[k nb + j], one thread per j (the rows are distinct);
+ * (stride, offset) = (1, 0) adds to a forcing vector of n values.  mgb_amg_add_cost_rows does the same into column col of the
+ * AMG's cost, (stride, offset) = (K, col), on the context stream behind mgb_amg_set_c: only values of the cost buffer change.
+ * None of the three waits for the device.  MGB_E_ARG, before anything is launched: a null argument; B outside [1, 65535]; a
+ * vector of the wrong length or of another context; k outside [0, B); a bad stride, offset or column; a row outside y; a
+ * non-finite alpha; a sharded context. */
+int mgb_geo_dirichlet_on(mgb_geo g, const char* name, const uint8_t* facet_mask_or_null /* nf bytes */);
+/* host arrays, each nullable: nb, the number of incidences nf q, rows nb, start nb + 1, idx nf q */
+int mgb_geo_boundary_incidence(mgb_geo g, int* nb, int* ninc, int32_t* rows, int32_t* start, int32_t* idx);
+int mgb_boundary_incidence(mgb_boundary b, int* nb, int* ninc, int32_t* rows, int32_t* start, int32_t* idx);
+/* host only: the serial restatement of the load, out B x nb */
+int mgb_geo_boundary_load_host(mgb_geo g, int B, const double* h /* B x nf x q */, const uint8_t* facet_mask_or_null, double* out);
+int mgb_boundary_load(mgb_boundary b, int B, const double* h_host /* B x nf x q */, const uint8_t* mask_host_or_null,
+                      mgb_vec out /* B x nb */);
+int mgb_boundary_load_add(mgb_boundary b, mgb_vec load /* B x nb */, int k, double alpha, mgb_vec y, long long stride,
+                          long long offset);
+int mgb_amg_add_cost_rows(mgb_amg a, mgb_boundary b, mgb_vec load /* B x nb */, int k, double alpha, int col);
+
 /* ---- host-only symbolic helpers (no GPU needed; used by the CPU test-suite) ----------------- */
 
 typedef struct mgb_plan_s* mgb_plan;  /* symbolic products of one level: R, B=D*R, B', Hessian plan T */

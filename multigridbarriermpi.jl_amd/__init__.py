@@ -39,6 +39,7 @@ __all__ = [
     "interpolate", "sample_grid", "norms", "error", "convergence", "FieldNorms", "Convergence",
     "energy", "flux", "Energy",
     "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
+    "dirichlet_on", "neumann_load", "NeumannLoad",
 ]
 
 
@@ -563,6 +564,8 @@ class Geometry:
     _locator: object = field(default=None, repr=False) # mgb_locator handle, made by the first interpolate() and freed here
     _boundary: object = field(default=None, repr=False)      # Boundary (host arrays), made by the first boundary()
     _boundary_dev: object = field(default=None, repr=False)  # mgb_boundary handle, made by the first boundary_flux(); it uses the locator
+    _boundary_rows: object = field(default=None, repr=False) # the distinct rows of the facet nodes, ascending (neumann_load)
+    _mixed: object = field(default=None, repr=False)         # facet selection (mask bytes) -> name of its dirichlet_on() subspace
 
     def __del__(self):
         try:
@@ -949,6 +952,12 @@ class AMG:
         c = np.empty((self.n_local, self.K))
         call("mgb_amg_get_c", self.handle, dptr(c))
         return c
+
+    def add_cost_rows(self, load: "NeumannLoad", col: int, k: int = 0, alpha: float = 1.0):
+        """c[load.rows, col] += alpha * load.values[k], on the device behind set_c (include/mgb_hip.h: mgb_amg_add_cost_rows)."""
+        if load.geometry is not self.geometry:
+            raise ValueError("add_cost_rows: the load belongs to another geometry")
+        call("mgb_amg_add_cost_rows", self.handle, self.geometry._boundary_dev, load.values._v.handle, int(k), float(alpha), int(col))
 
     def parabolic_begin(self, bidx):
         """Time loop of parabolic_solve on the device (include/mgb_hip.h): `bidx` = the nodes that carry Dirichlet data."""
@@ -1381,21 +1390,42 @@ def _amgb_float32(geometry, M: "AMG", z0, tol, t, kappa, maxit, verbose):
 
 def amgb(geometry: Geometry, p=1.0, state_variables=DEFAULT_STATE, D=None, f=None, g=None, tol=None, t=0.1,
          maxit=10000, kappa=10.0, verbose=False, logfile=None, schedule="fine", solver="gpu", cones=None, stop_rule="fixed",
-         centering="exact", T=np.float64, **rest) -> AMGBSOL:
+         centering="exact", T=np.float64, dirichlet=None, neumann=None, **rest) -> AMGBSOL:
     """MultiGridBarrier.amgb on an MPI geometry (called at src:599,666).  kwargs as documented in
     docs/src/guide.md:148-152; unknown kwargs (e.g. `L`, forwarded by fem*d_mpi_solve, src:663-666)
     are ignored like Julia's `kwargs...` fan-out.  `cones` (upstream kwarg `Q`: the convex set) selects the barrier terms,
-    see `AMG`; default = the p-Laplace power cone."""
+    see `AMG`; default = the p-Laplace power cone.
+    Mixed boundary conditions (single-GPU contexts, T = float64): `dirichlet=where` (a boolean (nf,) array
+    over boundary(geometry) or a callable on a facet centre) keeps the variables of the "dirichlet" space fixed at g on the
+    selected facets only -- the subspace of dirichlet_on(), built once per geometry and selection; `neumann=h` (see
+    neumann_load) adds int h u ds over the facets NOT selected to the cost, in the first row of D that is (that variable, "id").
+    h enters as f does: for the default problem the natural condition on the free part is p |grad u|^(p-2) du/dn = -h.  p = 1
+    is not coercive with a free boundary: whether the problem is bounded then depends on f and h, at the caller's risk."""
+    if neumann is not None and dirichlet is None:
+        raise ValueError("amgb: neumann= needs dirichlet= (the load acts on the facets that dirichlet= does not select)")
     if geometry._geo is None:
         raise TypeError("amgb: geometry must come from native_to_mpi / fem*d_mpi")
     dim = geometry.discretization["dim"]
     f = DEFAULT_F[dim] if f is None else f
     g = DEFAULT_G[dim] if g is None else g
+    load = None
+    if dirichlet is not None:
+        if np.dtype(T) != np.float64:
+            raise NotImplementedError("amgb: dirichlet= / neumann= are not supported with T = float32")
+        state_variables, free, load_var = _mixed_state(geometry, state_variables, dirichlet, "amgb")
+        if neumann is not None:
+            pairs = [tuple(d) for d in (DEFAULT_D[dim] if D is None else D)]
+            if (load_var, "id") not in pairs:
+                raise ValueError("amgb: neumann= needs a row (%r, 'id') of D" % (load_var,))
+            load = (neumann_load(geometry, neumann, where=free), pairs.index((load_var, "id")))
     M = AMG(geometry, state_variables, D, p, cones=cones, select=rest.get("select"))
     x = geometry.x.to_numpy()
     z0 = _rows(g, x)        # g_grid (n, S)
     c = _rows(f, x)         # f_grid (n, K)
     M.set_c(c)
+    if load is not None:
+        M.add_cost_rows(load[0], load[1])
+        c = M.get_c()       # the cost the feasibility phase scales its penalty by
     M.set_z(z0.reshape(-1, order="F"))
     Nf = M.level_size(M.L - 1)[0]
     y0 = M.f0(M.L - 1, np.zeros(Nf), 0.0)
@@ -1478,16 +1508,16 @@ class ParabolicSOL:
     lift: Optional[np.ndarray] = None
 
 
-def _positional_arity(fn, name):
+def _positional_arity(fn, name, who="parabolic_solve"):
     """Number of positional parameters of the closure `fn` (1: fn(x), 2: fn(t, x)); anything else is a TypeError naming `name`."""
     import inspect
     try:
         params = inspect.signature(fn).parameters.values()
     except (TypeError, ValueError):
-        raise TypeError("parabolic_solve: cannot read the signature of %s; pass a function of (x) or of (t, x)" % name)
+        raise TypeError("%s: cannot read the signature of %s; pass a function of (x) or of (t, x)" % (who, name))
     k = sum(1 for q in params if q.kind in (q.POSITIONAL_ONLY, q.POSITIONAL_OR_KEYWORD))
     if k not in (1, 2) or any(q.kind == q.VAR_POSITIONAL for q in params):
-        raise TypeError("parabolic_solve: %s must take (x) or (t, x), not %d positional parameters" % (name, k))
+        raise TypeError("%s: %s must take (x) or (t, x), not %d positional parameters" % (who, name, k))
     return k
 
 
@@ -1539,7 +1569,7 @@ def _parabolic_host_loop(M, z, n, K, p, hs, fgrid, tol, verbose, schedule, solve
 
 
 def parabolic_solve(geometry: Geometry, h=0.2, t0=0.0, t1=1.0, p=1.0, f1=None, g=None, tol=None, verbose=False,
-                    schedule="fine", solver="gpu", ts=None, **rest) -> ParabolicSOL:
+                    schedule="fine", solver="gpu", ts=None, dirichlet=None, neumann=None, **rest) -> ParabolicSOL:
     """MultiGridBarrier.parabolic_solve on an MPI geometry (imported at src:22,54; kwargs h, t1, p, verbose as in
     test/test_parabolic.jl:48 and docs/src/guide.md:367,377).  Implicit Euler for
         u_t - div(|grad u|^(p-2) grad u) = -f1 ;
@@ -1552,7 +1582,13 @@ def parabolic_solve(geometry: Geometry, h=0.2, t0=0.0, t1=1.0, p=1.0, f1=None, g
       ts: strictly increasing times (overrides h, t0, t1; h_k = ts[k + 1] - ts[k]).
     Forcing and boundary data are taken at the new time t_{k+1}.  Where new boundary values or a larger gradient push the old
     slacks out of a cone, the slack is shifted by the constant lift = 1 + max violation (0 when nothing violates) before the
-    solve; the shifts are returned as `lift` (nsteps, 2).  Sharded contexts (world > 1) run time-independent data only."""
+    solve; the shifts are returned as `lift` (nsteps, 2).  Sharded contexts (world > 1) run time-independent data only.
+      dirichlet, neumann (single-GPU contexts): `dirichlet=where` keeps u at g on the selected boundary
+          facets only (dirichlet_on); `neumann=` h(x) | h(t, x), taken at t_{k+1} like f1, adds int h u ds over the other
+          facets: the natural condition there is |grad u|^(p-2) du/dn = -h.  The loads of all steps come from one launch and
+          are added to the step's forcing vector on the device.  p = 1 with a free boundary is at the caller's risk."""
+    if neumann is not None and dirichlet is None:
+        raise ValueError("parabolic_solve: neumann= needs dirichlet= (the load acts on the facets that dirichlet= does not select)")
     if geometry._geo is None:
         raise TypeError("parabolic_solve: geometry must come from native_to_mpi / fem*d_mpi")
     dim = geometry.discretization["dim"]
@@ -1574,6 +1610,15 @@ def parabolic_solve(geometry: Geometry, h=0.2, t0=0.0, t1=1.0, p=1.0, f1=None, g
     if backend.world > 1 and (f_timed or g_arity == 2 or explicit_ts):
         raise NotImplementedError("parabolic_solve: sharded contexts (world > 1) are not supported with f1(t, x), g(t, x) or ts=")
     g_at = (lambda t, xi: g(t, xi)) if g_arity == 2 else (lambda t, xi: g(xi))
+    space, load, load_timed = "dirichlet", None, False
+    if dirichlet is not None:
+        state, free, _ = _mixed_state(geometry, state, dirichlet, "parabolic_solve")
+        space = state[0][1]
+        if neumann is not None:
+            if not callable(neumann):
+                raise TypeError("parabolic_solve: neumann must be a function h(x) or h(t, x)")
+            load_timed = _positional_arity(neumann, "neumann") == 2
+            load = neumann_load(geometry, neumann, where=free, ts=ts[1:] if load_timed else None)      # every step: ONE launch
     M = AMG(geometry, state, D, p, cones=cones)
     u0 = np.array([np.asarray(g_at(ts[0], xi), dtype=np.float64).reshape(-1)[0] for xi in x])
     grad2 = sum((geometry.operators[o].host @ u0) ** 2 for o in ops)
@@ -1581,15 +1626,17 @@ def parabolic_solve(geometry: Geometry, h=0.2, t0=0.0, t1=1.0, p=1.0, f1=None, g
                         np.full(n, 1.0 + float(np.max(grad2 ** (p / 2.0))))])
     if backend.world > 1:
         return ParabolicSOL(geometry, ts, _parabolic_host_loop(M, z, n, K, p, hs, f_row(0), tol, verbose, schedule, solver, backend))
-    bidx = np.flatnonzero(np.diff(geometry.subspaces["dirichlet"][-1].host.indptr) == 0)
+    bidx = np.flatnonzero(np.diff(geometry.subspaces[space][-1].host.indptr) == 0)
     M.set_z(z)
     M.parabolic_begin(bidx)
     u = [M.snapshot()]
     lift = np.zeros((nsteps, 2))
     fv = None
     for k in range(nsteps):
-        if fv is None or f_timed:
+        if fv is None or f_timed or load_timed:
             fv = HPCVector(f_row(k), backend)
+            if load is not None:
+                load.add_to(fv, k if load_timed else 0)
         gb = None
         if g_arity == 2:
             gb = HPCVector(np.array([np.asarray(g(ts[k + 1], x[b]), dtype=np.float64).reshape(-1)[0] for b in bidx]), backend)
@@ -2139,6 +2186,175 @@ def boundary_flux(obj, p, u=0, z=None, where=None, per_facet=False) -> BoundaryF
     if ts is None:
         return BoundaryFlux(*[float(c[0]) for c in cols], facets=facets[0] if per_facet else None)
     return BoundaryFlux(*cols, ts=ts, facets=facets)
+
+
+# --------------------------------------------------------------------------- mixed boundary conditions
+
+
+_TAKEN_SUBSPACES = ("full", "dirichlet", "fixed")
+
+
+def _host_geo_with_full(geometry: Geometry):
+    """A temporary host mgb_geo of a native geometry: x, w and every level of subspaces["full"] (the caller destroys it)."""
+    x = f64(np.asarray(geometry.x))
+    x = x.reshape(x.shape[0], -1)
+    w, L = f64(geometry.w), len(geometry.refine)
+    h = C.c_void_p()
+    call("mgb_geo_create", x.shape[0], x.shape[1], L, int(geometry.discretization.get("block", 1)), dptr(x), dptr(w), C.byref(h))
+    try:
+        for l, S in enumerate(geometry.subspaces.get("full", [])[:L]):
+            S = sp.csr_matrix(S, dtype=np.float64)
+            S.sort_indices()
+            rp, ci, va = i32(S.indptr), i32(S.indices), f64(S.data)
+            call("mgb_geo_set_matrix", h, ("sub:full:%d" % l).encode(), S.shape[0], S.shape[1], iptr(rp), iptr(ci), dptr(va))
+    except Exception:
+        call("mgb_geo_destroy", h)
+        raise
+    return h
+
+
+def dirichlet_on(geometry: Geometry, where, name: str = "mixed") -> str:
+    """Dirichlet conditions on part of the boundary: adds geometry.subspaces[name], one matrix per level, and returns `name` for
+    use in `state_variables` (amgb(dirichlet=where) does both).  A variable in that space is fixed on the rows of the selected
+    boundary facets, end points included, and free everywhere else.  `where`: a boolean (nf,) array in the order of
+    boundary(geometry) or a callable on a facet centre; None is refused (it would be "dirichlet"); a selection with no facet
+    gives "full".  Rule (csrc/mixed.hpp): per level, the columns of subspaces["full"] without those that
+    are non-zero in a selected row of the finest mesh.  Native (scipy) and device geometries."""
+    if not isinstance(geometry, Geometry):
+        raise TypeError("dirichlet_on: expected a Geometry")
+    if where is None:
+        raise ValueError('dirichlet_on: where=None would select every facet: that is the subspace "dirichlet"')
+    name = str(name)
+    if name in _TAKEN_SUBSPACES or name in geometry.subspaces or not name or ":" in name:
+        raise ValueError("dirichlet_on: the subspace name %r is taken or not usable" % name)
+    if geometry._geo is not None and geometry.x.backend.world > 1:
+        raise NotImplementedError("dirichlet_on: sharded contexts (world > 1) are not supported")
+    mask = _boundary_selection(where, boundary(geometry), "dirichlet_on")
+    L = len(geometry.refine)
+    if geometry._geo is None:
+        h = _host_geo_with_full(geometry)
+        try:
+            call("mgb_geo_dirichlet_on", h, name.encode(), u8ptr(mask))
+            mats = [_geo_matrix(h, "sub:%s:%d" % (name, l)) for l in range(L)]
+        finally:
+            call("mgb_geo_destroy", h)
+    else:
+        call("mgb_geo_dirichlet_on", geometry._geo, name.encode(), u8ptr(mask))
+        backend = geometry.x.backend
+        if geometry._geo_ref is not None:
+            mats = [_GeoMatrix(geometry._geo_ref, "sub:%s:%d" % (name, l), backend) for l in range(L)]
+        else:
+            mats = [HPCSparseMatrix(_geo_matrix(geometry._geo, "sub:%s:%d" % (name, l)), backend) for l in range(L)]
+    geometry.subspaces[name] = mats
+    if geometry._mixed is None:
+        geometry._mixed = {}
+    geometry._mixed.setdefault(mask.tobytes(), name)
+    return name
+
+
+def _mixed_state(geometry: Geometry, state_variables, where, who):
+    """(state_variables with "dirichlet" replaced by the subspace of the selection `where`, the boolean mask of the facets NOT
+    selected, the first replaced variable).  The subspace is built once per geometry and selection."""
+    if geometry.x.backend.world > 1:
+        raise NotImplementedError("%s: dirichlet= / neumann= are not supported on sharded contexts (world > 1)" % who)
+    if where is None:
+        raise ValueError("%s: dirichlet=None selects nothing to replace" % who)
+    mask = _boundary_selection(where, boundary(geometry), who)
+    name = (geometry._mixed or {}).get(mask.tobytes())
+    if name is None:
+        k = 0
+        while "mixed%d" % k in geometry.subspaces:
+            k += 1
+        name = dirichlet_on(geometry, mask.astype(np.bool_), "mixed%d" % k)
+    state = tuple((v, name if sub == "dirichlet" else sub) for v, sub in state_variables)
+    moved = [v for v, sub in state_variables if sub == "dirichlet"]
+    if not moved:
+        raise ValueError('%s: dirichlet= needs a state variable in the "dirichlet" space' % who)
+    return state, mask == 0, moved[0]
+
+
+@dataclass
+class NeumannLoad:
+    """Result of neumann_load(): `rows` (nb,) the distinct rows of the boundary facet nodes, ascending; `values` the loads on
+    the device, (B, nb); `ts` the times of the B fields of an h(t, x)."""
+    geometry: Geometry
+    rows: np.ndarray
+    values: "HPCMatrix"
+    ts: Optional[np.ndarray] = None
+    _host: object = field(default=None, repr=False)      # the host data the copy on the context stream reads
+
+    def add_to(self, y: "HPCVector", k: int = 0, alpha: float = 1.0, stride: int = 1, offset: int = 0):
+        """y[rows * stride + offset] += alpha * values[k], on the device."""
+        call("mgb_boundary_load_add", self.geometry._boundary_dev, self.values._v.handle, int(k), float(alpha), y.handle,
+             int(stride), int(offset))
+        return y
+
+    def dense(self, k: int = 0) -> "HPCVector":
+        """Field k as a vector of n nodal values, zero off the boundary rows."""
+        return self.add_to(HPCVector(len(self.geometry.w), self.values.backend), k)
+
+
+def _neumann_data(geometry: Geometry, h, where, ts, who="neumann_load"):
+    """((B, nf, q) values of h at the facet nodes, the uint8 facet mask or None, the times or None); host only."""
+    b = boundary(geometry)
+    nf, q = b.nodes.shape
+    mask = _boundary_selection(where, b, who)
+    times = None
+    if callable(h):
+        x = np.asarray(_to_cpu_array(geometry.x), dtype=np.float64).reshape(len(geometry.w), -1)[b.nodes]      # (nf, q, dim)
+        if _positional_arity(h, "h", who) == 1:
+            hv = np.array([[float(h(xi)) for xi in xf] for xf in x]).reshape(1, nf, q)
+        else:
+            if ts is None:
+                raise ValueError("%s: h(t, x) needs ts=" % who)
+            times = np.array(ts, dtype=np.float64).reshape(-1)
+            if times.size < 1:
+                raise ValueError("%s: ts is empty" % who)
+            hv = np.array([[[float(h(t, xi)) for xi in xf] for xf in x] for t in times]).reshape(len(times), nf, q)
+    elif np.isscalar(h):
+        hv = np.full((1, nf, q), float(h))
+    else:
+        hv = f64(np.asarray(h))
+        if hv.shape == (nf, q):
+            hv = hv.reshape(1, nf, q)
+        if hv.ndim != 3 or hv.shape[1:] != (nf, q) or hv.shape[0] < 1:
+            raise ValueError("%s: an array h must have shape (nf, q) = (%d, %d) or (B, nf, q), got %r" % (who, nf, q, tuple(np.shape(h))))
+    sel = np.ones(nf, dtype=bool) if mask is None else mask.astype(bool)
+    if not np.isfinite(hv[:, sel]).all():
+        raise ValueError("%s: h is not finite on a selected facet" % who)
+    return np.ascontiguousarray(hv), mask, times
+
+
+def neumann_load(geometry: Geometry, h, where=None, ts=None) -> NeumannLoad:
+    """The load of Neumann data on the boundary facets of a device geometry, computed on the device (csrc/boundary.hip; contract
+    in include/mgb_hip.h and DESIGN.md section 4i): l_i = (sum of omega h over the facet nodes at row i) / w_i, the addition to
+    the (u, id) column of the cost that stands for int h u ds.  `h`: a scalar, a callable h(x), a callable h(t, x) with `ts=`
+    (one field per time), an (nf, q) array of values at the facet nodes, or a (B, nf, q) array.  `where` selects facets as in
+    boundary_flux.  All B fields come from one launch.  A non-finite h on a selected facet raises ValueError."""
+    if not isinstance(geometry, Geometry):
+        raise TypeError("neumann_load: expected a Geometry")
+    hv, mask, times = _neumann_data(geometry, h, where, ts)
+    if geometry._geo is None:
+        raise TypeError("neumann_load: geometry must come from native_to_mpi / fem*d_mpi")
+    if geometry.x.backend.world > 1:
+        raise NotImplementedError("neumann_load: sharded contexts (world > 1) are not supported")
+    loc, backend = _locator_of(geometry)
+    if geometry._boundary_dev is None:
+        hd = C.c_void_p()
+        call("mgb_boundary_create", loc, geometry._geo, C.byref(hd))
+        geometry._boundary_dev = hd
+    if geometry._boundary_rows is None:
+        nb = C.c_int()
+        call("mgb_boundary_incidence", geometry._boundary_dev, C.byref(nb), None, None, None, None)
+        rows = np.empty(nb.value, dtype=np.int32)
+        call("mgb_boundary_incidence", geometry._boundary_dev, None, None, iptr(rows), None, None)
+        geometry._boundary_rows = rows
+    rows = geometry._boundary_rows
+    B = hv.shape[0]
+    vals = HPCMatrix.__new__(HPCMatrix)
+    vals.shape, vals.backend, vals._v = (B, len(rows)), backend, HPCVector(B * len(rows), backend)
+    call("mgb_boundary_load", geometry._boundary_dev, B, dptr(hv), u8ptr(mask), vals._v.handle)
+    return NeumannLoad(geometry, rows, vals, times, (hv, mask))
 
 
 def mpi_to_native(obj):

@@ -147,6 +147,13 @@ PROTOTYPES = {
     "mgb_geo_boundary_dims": [H, c_int_p, c_int_p, c_int_p],
     "mgb_geo_boundary_get": [H, c_i32_p, c_i32_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_geo_boundary_flux_host": [H, C.c_int, C.POINTER(c_dbl_p), C.c_int, C.c_int, C.c_double, c_dbl_p, c_u8_p, c_dbl_p, c_dbl_p],
+    "mgb_geo_dirichlet_on": [H, C.c_char_p, c_u8_p],
+    "mgb_geo_boundary_incidence": [H, c_int_p, c_int_p, c_i32_p, c_i32_p, c_i32_p],
+    "mgb_boundary_incidence": [H, c_int_p, c_int_p, c_i32_p, c_i32_p, c_i32_p],
+    "mgb_geo_boundary_load_host": [H, C.c_int, c_dbl_p, c_u8_p, c_dbl_p],
+    "mgb_boundary_load": [H, C.c_int, c_dbl_p, c_u8_p, H],
+    "mgb_boundary_load_add": [H, H, C.c_int, C.c_double, H, C.c_longlong, C.c_longlong],
+    "mgb_amg_add_cost_rows": [H, H, H, C.c_int, C.c_double, C.c_int],
     "mgb_plan_prolongation": [H, H, c_int_p, c_int_p, c_int_p, c_i32_p, c_i32_p, c_dbl_p],
     "mgb_amg_solve": [H, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int],
     "mgb_amg_sol_info": [H, c_int_p, c_dbl_p, c_dbl_p, c_ll_p],

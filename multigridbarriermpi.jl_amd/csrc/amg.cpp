@@ -1,4 +1,5 @@
 #include "amg.hpp"
+#include "boundary.hpp"
 #include "parabolic.hpp"
 
 
@@ -747,6 +748,14 @@ void Amg::get_z(double* z_host) {
 void Amg::get_c(double* c_host) {
   hip_check(hipStreamSynchronize(ctx_.stream), "sync");
   c_.download(c_host, (size_t)n_ * P_.K);
+}
+
+void Amg::add_cost_rows(int nb, const int* rows_dev, const double* load_dev, double alpha, int col) {
+  if (ctx_.world != 1) throw ArgError("add_cost_rows: single-GPU contexts only");
+  if (nb < 0 || col < 0 || col >= P_.K || (nb > 0 && (!rows_dev || !load_dev))) throw ArgError("add_cost_rows: bad arguments");
+  hip_check(hipSetDevice(ctx_.device), "hipSetDevice");
+  boundary::launch_boundary_load_add(ctx_.stream, nb, rows_dev, load_dev, alpha, P_.K, col, c_.p);
+  hip_check(hipGetLastError(), "add_cost_rows launch");
 }
 
 // ------------------------------------------------------------------ time loop of parabolic_solve (parabolic.hpp)

@@ -323,6 +323,9 @@ class Amg {
   void set_z(const double* z_host);
   void get_z(double* z_host);
   void get_c(double* c_host);      // the local rows of c (tests; mirrors set_c on a single-GPU context)
+  // c[rows[j], col] += alpha * load[j] for j < nb on the context stream, behind set_c (boundary.hip: boundary_load_add); rows are
+  // distinct device row indices < n, load nb device doubles.  Only values of the cost buffer change.
+  void add_cost_rows(int nb, const int* rows_dev, const double* load_dev, double alpha, int col);
 
   // ---- time loop of parabolic_solve (parabolic.hpp): the transition between two barrier solves, on the device
   // needs the parabolic layout (S = 3: [u; s1; s2], K = dim + 3) on a single-GPU context; bidx = the nb boundary nodes

@@ -8,6 +8,7 @@
 //     (field, workgroup).  With a per-facet output the threads leave omega sigma . n in LDS and node 0 of every facet sums its
 //     facet's q values in ascending order.
 //   boundary_finish: grid (B); the workgroup of a field combines that field's partials in ascending workgroup order.
+//   boundary_load_kernel / boundary_load_add_kernel: the Neumann load of DESIGN.md section 4i, see below.
 // What a field's result is made of depends on the facet list alone, never on B or on the field's place in the batch.  No atomics
 // and no hand-off between workgroups inside a launch; every word is written by one thread with a vector store.
 #include "boundary.hpp"
@@ -100,7 +101,42 @@ struct LaunchFlux {
   }
 };
 
+// Neumann load (boundary.hpp: load_row): one thread per distinct boundary row, grid (ceil(nb / 256), B).  rows, start and the
+// output are contiguous in the thread index; omega, h and the mask are gathered through the incidence table.  No atomics, no
+// LDS, no hand-off: every word of the compact B x nb output is written by one thread with a vector store.
+__global__ void __launch_bounds__(kThreads) boundary_load_kernel(LoadArgs A, const double* __restrict__ h, double* __restrict__ out) {
+  const long long r = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (r >= A.nb) return;
+  const size_t b = blockIdx.y;
+  out[b * A.nb + r] = load_row(A, h + b * A.nf * A.q, (int)r);
+}
+
+__global__ void __launch_bounds__(kThreads) boundary_load_add_kernel(int nb, const int* __restrict__ rows, const double* __restrict__ load,
+                                                                     double alpha, long long stride, long long offset,
+                                                                     double* __restrict__ y) {
+#pragma clang fp contract(off)
+  const long long j = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (j >= nb) return;
+  const long long at = (long long)rows[j] * stride + offset;
+  y[at] = y[at] + alpha * load[j];
+}
+
 }  // namespace
+
+void launch_boundary_load(hipStream_t stream, const LoadArgs& A, int B, const double* h, double* out) {
+  if (A.nb < 0 || A.nf < 0 || A.q < 1 || B < 1 || B > 65535) throw ArgError("boundary_load: bad incidence table, or B outside [1, 65535]");
+  if (A.nb == 0) return;
+  const unsigned nwg = (unsigned)(((long long)A.nb + kThreads - 1) / kThreads);
+  hipLaunchKernelGGL(boundary_load_kernel, dim3(nwg, (unsigned)B), dim3(kThreads), 0, stream, A, h, out);
+}
+
+void launch_boundary_load_add(hipStream_t stream, int nb, const int* rows, const double* load, double alpha, long long stride,
+                              long long offset, double* y) {
+  if (nb < 0 || stride < 1 || offset < 0 || offset >= stride) throw ArgError("boundary_load_add: bad stride or offset");
+  if (nb == 0) return;
+  const unsigned nwg = (unsigned)(((long long)nb + kThreads - 1) / kThreads);
+  hipLaunchKernelGGL(boundary_load_add_kernel, dim3(nwg), dim3(kThreads), 0, stream, nb, rows, load, alpha, stride, offset, y);
+}
 
 void launch_boundary_flux(hipStream_t stream, int dim, int k, const Args& A, double* scratch, double* facet_flux) {
   if (A.E.n <= 0 || A.E.S <= 0 || A.E.B <= 0 || A.E.B > 65535) throw ArgError("boundary_flux: empty field, or more than 65535 fields");

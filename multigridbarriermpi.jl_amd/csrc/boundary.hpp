@@ -260,7 +260,81 @@ inline long long workgroups(int nf, int q) {
 }
 inline size_t scratch_doubles(int nf, int q, int B) { return (size_t)(workgroups(nf, q) + 1) * B * kCols; }      // partials, then B x kCols results
 
+// ---------------------------------------------------------------------------------------------------- Neumann load
+//   The objective is sum_i w_i c_i . (Dz)_i, so  int_Gamma h u ds  adds
+//     l_i = (sum over the facet nodes (f, j) with row(f, j) = i of  omega_fj h_fj) / w_i
+// to the (u, id) column of c at the boundary rows.  A row can sit in several facets of its own element (a triangle with two
+// boundary edges: 2; a cube corner: 3), so the facet list carries a row-sorted incidence table, built once on the host:
+//   rows   the nb distinct rows of the facet nodes, ascending
+//   start  nb + 1 row starts into idx
+//   idx    facet-node indices f q + j, ascending within a row
+// load_row below is the contract, run by boundary_load_kernel (boundary.hip) and by the host restatement: for boundary row r add
+// omega h over its incidences in table order, skipping the facets the mask leaves out -- their h is not read, so a NaN there
+// is not seen -- then divide once by w_r; a row with no selected incidence gives exactly 0.  Arithmetic kept as written (fp
+// contract off).
+struct Incidence {
+  std::vector<int> rows, start, idx;
+  int nb() const { return (int)rows.size(); }
+};
+
+inline Incidence build_incidence(const Facets& F) {
+  const size_t m = (size_t)F.nf * F.q;
+  std::vector<std::pair<int, int>> pairs(m);      // (row, facet node)
+  for (size_t t = 0; t < m; ++t) pairs[t] = {F.nodes[t], (int)t};
+  std::sort(pairs.begin(), pairs.end());
+  Incidence I;
+  I.idx.resize(m);
+  for (size_t t = 0; t < m; ++t) {
+    if (t == 0 || pairs[t].first != pairs[t - 1].first) {
+      I.rows.push_back(pairs[t].first);
+      I.start.push_back((int)t);
+    }
+    I.idx[t] = pairs[t].second;
+  }
+  I.start.push_back((int)m);
+  return I;
+}
+
+struct LoadArgs {
+  const int* rows = nullptr;               // nb
+  const int* start = nullptr;              // nb + 1
+  const int* idx = nullptr;                // nf x q facet nodes, grouped by row
+  const double* weights = nullptr;         // nf x q
+  const unsigned char* mask = nullptr;     // nf bytes or null: 0 leaves the facet out
+  const double* w = nullptr;               // n nodal weights
+  int nb = 0, nf = 0, q = 0;
+};
+
+// the load of boundary row r for one field h (nf x q)
+MGB_HD double load_row(const LoadArgs& A, const double* h, int r) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double s = 0.0;
+  bool any = false;
+  const int t1 = A.start[r + 1];
+  for (int t = A.start[r]; t < t1; ++t) {
+    const int fj = A.idx[t];
+    if (A.mask && !A.mask[fj / A.q]) continue;
+    s += A.weights[fj] * h[fj];
+    any = true;
+  }
+  return any ? s / A.w[A.rows[r]] : 0.0;
+}
+
+// host restatement: out is B x nb, h is B x nf x q
+inline void boundary_load_host(const LoadArgs& A, int B, const double* h, double* out) {
+  for (int b = 0; b < B; ++b)
+    for (int r = 0; r < A.nb; ++r) out[(size_t)b * A.nb + r] = load_row(A, h + (size_t)b * A.nf * A.q, r);
+}
+
 #if defined(__HIPCC__)
+// boundary.hip: boundary_load_kernel on grid (ceil(nb / 256), B), one thread per distinct row, compact output B x nb; all
+// pointers of A, h and out are device pointers
+void launch_boundary_load(hipStream_t stream, const LoadArgs& A, int B, const double* h, double* out);
+// y[rows[j] * stride + offset] += alpha * load[j], one thread per j < nb (rows are distinct: no conflicts)
+void launch_boundary_load_add(hipStream_t stream, int nb, const int* rows, const double* load, double alpha, long long stride,
+                              long long offset, double* y);
 // boundary.hip: two launches on `stream` -- partials on grid (workgroups, B), one thread per (facet, facet node), then one
 // workgroup per field that combines that field's partials in ascending workgroup order; all pointers of A are device pointers
 // (A.E.z a device table of B device pointers); the B x kCols results are at scratch + workgroups * B * kCols; facet_flux

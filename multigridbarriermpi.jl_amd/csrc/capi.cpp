@@ -11,6 +11,7 @@
 #include "boundary.hpp"
 #include "interp.hpp"
 #include "energy.hpp"
+#include "mixed.hpp"
 #include "norms.hpp"
 
 using namespace mgb;
@@ -60,6 +61,9 @@ struct mgb_boundary_s {
   DevBuf<unsigned char> mask;                      // mgb_boundary_flux: the facet mask of the call
   DevBuf<double> scratch, facet_scratch;           // ... partials and results, per-facet values, grown on demand
   DevBuf<const double*> table;                     // ... and the device table of field pointers, uploaded per call
+  boundary::Incidence inc;                         // mgb_boundary_load: the row-sorted incidence table, built with the facets
+  DevBuf<int> inc_rows, inc_start, inc_idx;
+  DevBuf<double> load_h;                           // ... the B x nf x q data of the call, grown on demand
 };
 struct mgb_plan_s {
   LevelPlan plan;
@@ -1423,6 +1427,10 @@ int mgb_boundary_create(mgb_locator loc, mgb_geo g, mgb_boundary* out) {
       b->nodes.upload(b->F.nodes.data(), b->F.nodes.size());
       b->weights.upload(b->F.weights.data(), b->F.weights.size());
       b->normal.upload(b->F.normal.data(), b->F.normal.size());
+      b->inc = boundary::build_incidence(b->F);
+      b->inc_rows.upload(b->inc.rows.data(), b->inc.rows.size());
+      b->inc_start.upload(b->inc.start.data(), b->inc.start.size());
+      b->inc_idx.upload(b->inc.idx.data(), b->inc.idx.size());
     } catch (...) {
       delete b;
       throw;
@@ -1539,6 +1547,122 @@ int mgb_geo_boundary_flux_host(mgb_geo g, int B, const double* const* z, int S, 
     A.mask = mask;
     A.nf = F.nf, A.q = F.q;
     boundary::boundary_flux_host(F.dim, F.k, A, out, facet_flux);
+  });
+}
+
+// ---- mixed boundary conditions: Dirichlet subspace on part of the boundary (mixed.hpp), Neumann load (boundary.hpp / boundary.hip)
+int mgb_geo_dirichlet_on(mgb_geo g, const char* name, const uint8_t* facet_mask) {
+  return guard([&] {
+    need(g && name, "geo_dirichlet_on: null argument");
+    mixed::dirichlet_on(g->g, name, facet_mask);
+  });
+}
+int mgb_geo_boundary_incidence(mgb_geo g, int* nb, int* ninc, int32_t* rows, int32_t* start, int32_t* idx) {
+  return guard([&] {
+    need(g, "geo_boundary_incidence: null geometry");
+    const boundary::Incidence I = boundary::build_incidence(boundary::build_facets(g->g));
+    if (nb) *nb = I.nb();
+    if (ninc) *ninc = (int)I.idx.size();
+    if (rows) std::copy(I.rows.begin(), I.rows.end(), rows);
+    if (start) std::copy(I.start.begin(), I.start.end(), start);
+    if (idx) std::copy(I.idx.begin(), I.idx.end(), idx);
+  });
+}
+int mgb_geo_boundary_load_host(mgb_geo g, int B, const double* h, const uint8_t* facet_mask, double* out) {
+  return guard([&] {
+    need(g && h && out, "geo_boundary_load_host: null argument");
+    need(B >= 1, "geo_boundary_load_host: B must be >= 1");
+    need(g->g.w.size() == (size_t)g->g.n, "geo_boundary_load_host: the geometry must carry one weight per node");
+    const boundary::Facets F = boundary::build_facets(g->g);
+    const boundary::Incidence I = boundary::build_incidence(F);
+    boundary::LoadArgs A;
+    A.rows = I.rows.data(), A.start = I.start.data(), A.idx = I.idx.data();
+    A.weights = F.weights.data();
+    A.mask = facet_mask;
+    A.w = g->g.w.data();
+    A.nb = I.nb(), A.nf = F.nf, A.q = F.q;
+    boundary::boundary_load_host(A, B, h, out);
+  });
+}
+int mgb_boundary_incidence(mgb_boundary b, int* nb, int* ninc, int32_t* rows, int32_t* start, int32_t* idx) {
+  return guard([&] {
+    need(b, "boundary_incidence: null boundary");
+    const boundary::Incidence& I = b->inc;
+    if (nb) *nb = I.nb();
+    if (ninc) *ninc = (int)I.idx.size();
+    if (rows) std::copy(I.rows.begin(), I.rows.end(), rows);
+    if (start) std::copy(I.start.begin(), I.start.end(), start);
+    if (idx) std::copy(I.idx.begin(), I.idx.end(), idx);
+  });
+}
+int mgb_boundary_load(mgb_boundary bd, int B, const double* h_host, const uint8_t* mask_host, mgb_vec out) {
+  return guard([&] {
+    need(bd && h_host && out, "boundary_load: null argument");
+    mgb_locator_s* loc = bd->loc;
+    need(loc->ctx->ctx.world == 1, "boundary_load: sharded contexts are not supported");
+    need(out->ctx == loc->ctx, "boundary_load: vector of another context");
+    need(B >= 1 && B <= 65535, "boundary_load: B must be in [1, 65535]");
+    const boundary::Facets& F = bd->F;
+    const int nb = bd->inc.nb();
+    need(out->n == (long long)B * nb, "boundary_load: out must hold B x nb values");
+    if (nb == 0) return;
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const size_t nh = (size_t)B * F.nf * F.q;
+    if (bd->load_h.n < nh) {      // an earlier launch may still read the old buffer
+      hip_check(hipStreamSynchronize(st), "sync boundary_load");
+      bd->load_h.alloc(nh);
+    }
+    hip_check(hipMemcpyAsync(bd->load_h.p, h_host, nh * sizeof(double), hipMemcpyHostToDevice, st), "H2D h");
+    if (mask_host) {
+      if (bd->mask.n < (size_t)F.nf) {
+        hip_check(hipStreamSynchronize(st), "sync boundary_load");
+        bd->mask.alloc((size_t)F.nf);
+      }
+      hip_check(hipMemcpyAsync(bd->mask.p, mask_host, (size_t)F.nf, hipMemcpyHostToDevice, st), "H2D mask");
+    }
+    boundary::LoadArgs A;
+    A.rows = bd->inc_rows.p, A.start = bd->inc_start.p, A.idx = bd->inc_idx.p;
+    A.weights = bd->weights.p;
+    A.mask = mask_host ? bd->mask.p : nullptr;
+    A.w = loc->w.p;
+    A.nb = nb, A.nf = F.nf, A.q = F.q;
+    boundary::launch_boundary_load(st, A, B, bd->load_h.p, out->buf.p);
+    hip_check(hipGetLastError(), "boundary_load launch");
+  });
+}
+int mgb_boundary_load_add(mgb_boundary bd, mgb_vec load, int k, double alpha, mgb_vec y, long long stride, long long offset) {
+  return guard([&] {
+    need(bd && load && y, "boundary_load_add: null argument");
+    mgb_locator_s* loc = bd->loc;
+    need(loc->ctx->ctx.world == 1, "boundary_load_add: sharded contexts are not supported");
+    need(load->ctx == loc->ctx && y->ctx == loc->ctx, "boundary_load_add: vectors of another context");
+    const int nb = bd->inc.nb();
+    need(nb == 0 ? load->n == 0 : (load->n > 0 && load->n % nb == 0), "boundary_load_add: load must hold B x nb values");
+    if (nb == 0) return;
+    need(k >= 0 && k < load->n / nb, "boundary_load_add: field k outside [0, B)");
+    need(stride >= 1 && offset >= 0 && offset < stride, "boundary_load_add: needs stride >= 1 and 0 <= offset < stride");
+    need((long long)bd->inc.rows.back() * stride + offset < (long long)y->n, "boundary_load_add: a boundary row lies outside y");
+    need(std::isfinite(alpha), "boundary_load_add: alpha must be finite");
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    boundary::launch_boundary_load_add(loc->ctx->ctx.stream, nb, bd->inc_rows.p, load->buf.p + (size_t)k * nb, alpha, stride, offset,
+                                       y->buf.p);
+    hip_check(hipGetLastError(), "boundary_load_add launch");
+  });
+}
+int mgb_amg_add_cost_rows(mgb_amg a, mgb_boundary bd, mgb_vec load, int k, double alpha, int col) {
+  return guard([&] {
+    need(a && bd && load, "amg_add_cost_rows: null argument");
+    need(a->ctx->ctx.world == 1, "amg_add_cost_rows: sharded contexts are not supported");
+    need(bd->loc->ctx == a->ctx && load->ctx == a->ctx, "amg_add_cost_rows: objects of another context");
+    need(bd->loc->loc.n == a->amg->n(), "amg_add_cost_rows: the boundary belongs to another geometry");
+    const int nb = bd->inc.nb();
+    need(nb == 0 ? load->n == 0 : (load->n > 0 && load->n % nb == 0), "amg_add_cost_rows: load must hold B x nb values");
+    if (nb == 0) return;
+    need(k >= 0 && k < load->n / nb, "amg_add_cost_rows: field k outside [0, B)");
+    need(col >= 0 && col < a->amg->params().K, "amg_add_cost_rows: column outside [0, K)");
+    need(std::isfinite(alpha), "amg_add_cost_rows: alpha must be finite");
+    a->amg->add_cost_rows(nb, bd->inc_rows.p, load->buf.p + (size_t)k * nb, alpha, col);
   });
 }
 
