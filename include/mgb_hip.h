@@ -494,6 +494,52 @@ int mgb_geo_boundary_flux_host(mgb_geo g, int B, const double* const* z /* B arr
                                const double* p_nodal_or_null, const unsigned char* mask_or_null,
                                double* facet_flux_or_null /* B x nf */, double* out /* B x MGB_BOUNDARY_COLS */);
 
+/* ---- residual error indicators ------------------------------------------------------------------- *
+ * Single-GPU contexts, fp64.  Where the error of a solve sits: per element three numbers, and five totals.
+ * Interior facets.  A facet whose sorted corner dofs occur in exactly two elements.  The first side is the one with the smaller
+ * (element, local facet); the facets come in ascending (element, local facet) order of their first side.  Per facet: the two
+ * elements; the q rows of the first side in the order of the boundary facets' nodes, then the q rows of the second side permuted
+ * so that node j of both sides has the same continuous dof; weights, measure, centre and the unit normal pointing out of the
+ * first side, by the formulas of the boundary facets.  elem_facet (nel x nlf, nlf = 2 / 3 / 6): the interior facet of (element,
+ * local facet), or -1 - f for boundary facet f; every local facet is one or the other.  MGB_E_ARG: a mesh that
+ * mgb_geo_boundary_get refuses, or two sides that cannot be matched node by node.
+ * Indicator.  Sigma (n x dim) is the nodal flux of mgb_geo_field_flux (the same launch, the same bits).  lambda_i is `scale`
+ * when own_scale != 0, else the exponent p_i (the problem  min int f u + s, s >= |grad u|^p  has the strong form
+ * f - p div sigma = 0  and the natural condition  p sigma . n + h = 0;  scale = 1 is the convention of mgb_geo_field_energy).
+ *   node i:            rho_i = f_i - lambda_i sum_k d_k (I Sigma_k)(x_i), the divergence of the element interpolant of Sigma in
+ *                      i's own element, k ascending (f null: 0)
+ *   interior facet F:  J_Fj = lambda_a ((Sigma_a - Sigma_b) . n_F) with rows a, b of the two sides;  J_F = sum_j omega_Fj |J_Fj|^r
+ *   Neumann facet F:   N_F = sum_j omega_Fj |lambda_i (Sigma_i . n_F) + h_Fj|^r; h is nf x q as mgb_boundary_load takes it, null:
+ *                      the boundary contributes nothing; a facet the mask leaves out gives 0 and its h is not read
+ *   element e:         h_e = (sum_{i in e} w_i)^(1/dim);  vol = h_e^r sum_i w_i |rho_i|^r;  jump = (h_e / 2) sum J_F over its
+ *                      interior facets;  neu = h_e sum N_F over its boundary facets;  eta_e^r = (vol + jump) + neu
+ * All inner sums run in ascending order (local node, facet node, local facet).  eta holds nel x 3: vol, jump, neu.  The
+ * MGB_ESTIMATE_COLS totals: sum vol | sum jump | sum neu | max_e eta_e^r | max |J_Fj|.  A non-finite u, sigma, f or h, or an
+ * exponent that is not a finite real >= 1, makes every number it feeds NaN -- the element's three numbers, those of its facet
+ * neighbours where a jump is hit, and the totals; the maxima are NaN-sticky.  fp contraction is off in the kernels and in the
+ * host restatement; powers go through the rule of mgb_field_norms (no pow for r = 2 and r = 1).
+ * mgb_estimate: the flux launch, then facet_terms_kernel (one thread per facet node, 256 / q whole facets per workgroup; left
+ * out when there is no facet), element_indicator_kernel (one thread per node, 256 / block whole elements per workgroup) and
+ * estimate_finish (one workgroup, partials in ascending workgroup order) on the context stream; h and the mask are copied on
+ * that stream; the call waits and copies the totals to the host.  No atomics; a repeated call repeats bit for bit.
+ * MGB_E_ARG, before anything is launched or written: a null argument; S < 1; u outside [0, S); p or r not finite or < 1; a
+ * non-finite scale; a vector of the wrong length or of another context; eta == z; a sharded context. */
+#define MGB_ESTIMATE_COLS 5
+int mgb_geo_interior_dims(mgb_geo g, int* nif, int* q, int* dim, int* nel, int* nlf);
+/* host arrays, each nullable: elements nif x 2, nodes nif x 2 x q, weights nif x q, normal nif x dim, measure nif, centre
+ * nif x dim, elem_facet nel x nlf */
+int mgb_geo_interior_get(mgb_geo g, int32_t* elements, int32_t* nodes, double* weights, double* normal, double* measure,
+                         double* centre, int32_t* elem_facet);
+/* the tables live in the mgb_boundary of the geometry */
+int mgb_estimate(mgb_boundary b, mgb_vec z /* n x S */, int S, int u, double p, mgb_vec p_nodal_or_null, mgb_vec f_or_null, double r,
+                 int own_scale, double scale, const double* h_host_or_null /* nf x q */, const unsigned char* mask_host_or_null,
+                 mgb_vec eta /* nel x 3 */, double* out_host /* MGB_ESTIMATE_COLS */);
+/* host only: the same per-node, per-facet and per-element routines, serially; J (nif), N (nf) and sigma (n x dim) nullable */
+int mgb_geo_estimate_host(mgb_geo g, const double* z /* n x S */, int S, int u, double p, const double* p_nodal_or_null,
+                          const double* f_or_null, double r, int own_scale, double scale, const double* h_or_null,
+                          const unsigned char* mask_or_null, double* eta /* nel x 3 */, double* J_or_null, double* N_or_null,
+                          double* sigma_or_null, double* out /* MGB_ESTIMATE_COLS */);
+
 /* ---- mixed boundary conditions: Dirichlet on part of the boundary, Neumann data on the rest ------- *
  * Single-GPU contexts, fp64.
  * Dirichlet subspace.  mgb_geo_dirichlet_on adds "sub:<name>:<l>" for every level l (read back with mgb_geo_matrix_info / _get;

@@ -40,6 +40,7 @@ __all__ = [
     "energy", "flux", "Energy",
     "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
     "dirichlet_on", "neumann_load", "NeumannLoad",
+    "interior", "InteriorFacets", "estimate", "ErrorIndicators", "mark", "refine_triangles", "adapt",
 ]
 
 
@@ -566,6 +567,7 @@ class Geometry:
     _boundary_dev: object = field(default=None, repr=False)  # mgb_boundary handle, made by the first boundary_flux(); it uses the locator
     _boundary_rows: object = field(default=None, repr=False) # the distinct rows of the facet nodes, ascending (neumann_load)
     _mixed: object = field(default=None, repr=False)         # facet selection (mask bytes) -> name of its dirichlet_on() subspace
+    _interior: object = field(default=None, repr=False)      # InteriorFacets (host arrays), made by the first interior()
 
     def __del__(self):
         try:
@@ -2186,6 +2188,320 @@ def boundary_flux(obj, p, u=0, z=None, where=None, per_facet=False) -> BoundaryF
     if ts is None:
         return BoundaryFlux(*[float(c[0]) for c in cols], facets=facets[0] if per_facet else None)
     return BoundaryFlux(*cols, ts=ts, facets=facets)
+
+
+# --------------------------------------------------------------------------- residual error indicators, adaptive coarse meshes
+
+
+@dataclass
+class InteriorFacets:
+    """The interior facets of a geometry (contract in include/mgb_hip.h), in ascending (element, local
+    facet) order of their first side: `elements` (nif, 2); `nodes` (nif, 2, q) the rows of the first side and those of the second
+    side, node j of both on the same continuous dof; `weights` (nif, q), `normal` (nif, dim) out of the first side, `measure`
+    (nif,), `centre` (nif, dim); `element_facets` (nel, nlf): the interior facet of a local facet, or -1 - f for boundary facet f."""
+    elements: np.ndarray
+    nodes: np.ndarray
+    weights: np.ndarray
+    normal: np.ndarray
+    measure: np.ndarray
+    centre: np.ndarray
+    element_facets: np.ndarray
+
+    def __len__(self):
+        return len(self.elements)
+
+
+def interior(geometry: Geometry) -> InteriorFacets:
+    """The interior facets of a native or a device geometry, found on the host by the key sort of boundary() (csrc/boundary.hpp)
+    and kept on the geometry."""
+    if not isinstance(geometry, Geometry):
+        raise TypeError("interior: expected a Geometry")
+    if geometry._interior is not None:
+        return geometry._interior
+    h, own = geometry._geo, False
+    if h is None:
+        x = f64(np.asarray(geometry.x))
+        x = x.reshape(x.shape[0], -1)
+        w, L = f64(geometry.w), len(geometry.refine)
+        h = C.c_void_p()
+        call("mgb_geo_create", x.shape[0], x.shape[1], L, int(geometry.discretization.get("block", 1)), dptr(x), dptr(w), C.byref(h))
+        own = True
+    try:
+        if own and "full" in geometry.subspaces:
+            S = sp.csr_matrix(geometry.subspaces["full"][L - 1], dtype=np.float64)
+            S.sort_indices()
+            S.sum_duplicates()
+            rp, ci, va = i32(S.indptr), i32(S.indices), f64(S.data)
+            call("mgb_geo_set_matrix", h, ("sub:full:%d" % (L - 1)).encode(), S.shape[0], S.shape[1], iptr(rp), iptr(ci), dptr(va))
+        nif, q, dim, nel, nlf = (C.c_int() for _ in range(5))
+        call("mgb_geo_interior_dims", h, C.byref(nif), C.byref(q), C.byref(dim), C.byref(nel), C.byref(nlf))
+        nif, q, dim, nel, nlf = nif.value, q.value, dim.value, nel.value, nlf.value
+        I = InteriorFacets(np.empty((nif, 2), dtype=np.int32), np.empty((nif, 2, q), dtype=np.int32), np.empty((nif, q)),
+                           np.empty((nif, dim)), np.empty(nif), np.empty((nif, dim)), np.empty((nel, nlf), dtype=np.int32))
+        call("mgb_geo_interior_get", h, iptr(I.elements), iptr(I.nodes), dptr(I.weights), dptr(I.normal), dptr(I.measure),
+             dptr(I.centre), iptr(I.element_facets))
+    finally:
+        if own:
+            call("mgb_geo_destroy", h)
+    geometry._interior = I
+    return I
+
+
+class ErrorIndicators:
+    """Result of estimate().  `parts` (nel, 3): vol_e, jump_e, neu_e, the three numbers whose sum is
+    eta_e^r; `eta` (nel,) = eta_e, its r-th root.  Both stay on the device until first used.  `volume`, `jump`, `neumann`: the sums
+    of the three columns; `total` = (volume + jump + neumann)^(1/r); `eta_max` = max_e eta_e; `jump_max` = max |J_Fj| over the
+    interior facet nodes; `r` the power; `columns` the five totals as the C ABI returns them (sum vol, sum jump, sum neu, max
+    eta_e^r, max |J_Fj|).  A non-finite input shows as NaN in the elements it feeds and in the totals."""
+
+    def __init__(self, geometry, parts_dev, cols, r):
+        self.geometry, self.r = geometry, float(r)
+        self._dev, self._parts = parts_dev, None
+        self.columns = np.array(cols, dtype=np.float64)
+        self.volume, self.jump, self.neumann = float(cols[0]), float(cols[1]), float(cols[2])
+        self.total = float((cols[0] + cols[1] + cols[2]) ** (1.0 / self.r))
+        self.eta_max = float(cols[3] ** (1.0 / self.r))
+        self.jump_max = float(cols[4])
+
+    @property
+    def parts(self) -> np.ndarray:
+        if self._parts is None:
+            self._parts = self._dev.to_numpy().reshape(-1, 3)
+            self._dev = None
+        return self._parts
+
+    @property
+    def eta(self) -> np.ndarray:
+        P = self.parts
+        return ((P[:, 0] + P[:, 1]) + P[:, 2]) ** (1.0 / self.r)
+
+    def coarse(self, L: Optional[int] = None) -> np.ndarray:
+        """eta^r summed over the 2^(L-1) / 4^(L-1) / 8^(L-1) consecutive elements of each element of the coarse mesh (element
+        c e + k is child k of e at every refinement); L defaults to the geometry's number of levels."""
+        L = len(self.geometry.refine) if L is None else int(L)
+        P = self.parts
+        group = (2 ** self.geometry.discretization["dim"]) ** (L - 1)
+        if L < 1 or len(P) % group:
+            raise ValueError("ErrorIndicators.coarse: %d elements are not groups of %d" % (len(P), group))
+        return ((P[:, 0] + P[:, 1]) + P[:, 2]).reshape(-1, group).sum(axis=1)
+
+    def __repr__(self):
+        return "ErrorIndicators(total=%r, volume=%r, jump=%r, neumann=%r, eta_max=%r, jump_max=%r, r=%r)" % (
+            self.total, self.volume, self.jump, self.neumann, self.eta_max, self.jump_max, self.r)
+
+
+def _estimate_forcing(f, x, who):
+    """None or the (n,) nodal forcing of u: a scalar, an (n,) array, or what amgb takes -- a callable f(x) or an (n, K) array whose
+    first entry is the cost of (u, id)."""
+    n = x.shape[0]
+    if f is None:
+        return None
+    if callable(f):
+        fa = _rows(f, x)
+    elif np.isscalar(f):
+        return np.full(n, float(f))
+    else:
+        fa = f64(np.asarray(_to_cpu_array(f)))
+    if fa.ndim == 2 and fa.shape[0] == n and fa.shape[1] >= 1:
+        fa = fa[:, 0]
+    if fa.shape != (n,):
+        raise ValueError("%s: f must give one value (or one row) per node, (%d,) or (%d, K), got %r" % (who, n, n, tuple(fa.shape)))
+    return np.ascontiguousarray(fa)
+
+
+def estimate(obj, p, f=None, u=0, z=None, r=2.0, scale=None, dirichlet=None, neumann=None) -> ErrorIndicators:
+    """Residual error indicators of a solution, per element and in total, computed on the device (csrc/estimate.hip; contract in
+    include/mgb_hip.h and DESIGN.md section 4j): the element residual f - lambda div sigma of the interpolated nodal flux sigma =
+    |grad u|^(p-2) grad u, the jumps of lambda sigma . n over the interior facets and the Neumann residual lambda sigma . n + h.
+    `obj`: an AMGBSOL, or a device Geometry with `z=`; `p`, `u`: as for energy; `f`: None (0), a scalar, an (n,) array, or amgb's
+    f(x) / (n, K) array, whose first entry is taken; `r` >= 1 the power; `scale`: lambda, None meaning lambda_i = p_i -- amgb's
+    problem min int f u + s, s >= |grad u|^p -- and 1 the convention of energy().  `dirichlet`, `neumann`: as in amgb -- the
+    Neumann data h act on the boundary facets NOT selected by `dirichlet` (h = 0 when only `dirichlet` is given); with neither,
+    the boundary contributes nothing."""
+    if isinstance(obj, ParabolicSOL):
+        raise TypeError("estimate: a ParabolicSOL is not supported (the residual of a time step has a term this function does not know)")
+    if not isinstance(obj, (AMGBSOL, Geometry)):
+        raise TypeError("estimate: expected an AMGBSOL or a Geometry")
+    if neumann is not None and dirichlet is None:
+        raise ValueError("estimate: neumann= needs dirichlet= (the data act on the facets that dirichlet= does not select)")
+    geometry, z = _field_of(obj, "estimate", z)
+    if geometry._geo is None:
+        raise TypeError("estimate: geometry must come from native_to_mpi / fem*d_mpi")
+    if geometry.x.backend.world > 1:
+        raise NotImplementedError("estimate: sharded contexts (world > 1) are not supported")
+    if isinstance(r, (str, bytes)) or not np.isscalar(r) or not (math.isfinite(float(r)) and float(r) >= 1.0):
+        raise ValueError("estimate: r must be a finite real >= 1, got %r" % (r,))
+    if scale is not None and (isinstance(scale, (str, bytes)) or not np.isscalar(scale) or not math.isfinite(float(scale))):
+        raise ValueError("estimate: scale must be None or a finite real, got %r" % (scale,))
+    loc, backend = _locator_of(geometry)
+    b = boundary(geometry)
+    zv, S = _nodal_values(geometry, z, backend, "estimate")
+    u = _energy_column(u, S, "u", "estimate")
+    x = np.asarray(_to_cpu_array(geometry.x)).reshape(len(geometry.w), -1)
+    p0, pn = _energy_exponent(p, x, "estimate")
+    fa = _estimate_forcing(f, x, "estimate")
+    hv = mask = None
+    if dirichlet is not None:
+        sel = _boundary_selection(dirichlet, b, "estimate")
+        if sel is None:
+            raise ValueError("estimate: dirichlet=None selects nothing")
+        hv, mask, _ = _neumann_data(geometry, 0.0 if neumann is None else neumann, sel == 0, None, "estimate")
+        hv = hv[0]
+    if geometry._boundary_dev is None:
+        hd = C.c_void_p()
+        call("mgb_boundary_create", loc, geometry._geo, C.byref(hd))
+        geometry._boundary_dev = hd
+    nel = len(geometry.w) // geometry.discretization["block"]
+    pv = HPCVector(pn, backend) if pn is not None else None
+    fv = HPCVector(fa, backend) if fa is not None else None
+    parts = HPCVector(3 * nel, backend)
+    out = np.empty(5)
+    call("mgb_estimate", geometry._boundary_dev, zv.handle, S, u, p0, pv.handle if pv is not None else None,
+         fv.handle if fv is not None else None, float(r), 0 if scale is None else 1, 1.0 if scale is None else float(scale),
+         dptr(hv), u8ptr(mask), parts.handle, dptr(out))
+    return ErrorIndicators(geometry, parts, out, r)
+
+
+def mark(values, theta=0.5) -> np.ndarray:
+    """Doerfler marking on the host: the indices of the shortest prefix of `values`, in stable descending order (ties to the
+    lower index), whose np.cumsum reaches theta times the total.  `theta` in (0, 1]; values must be finite and >= 0; an
+    all-zero array marks nothing."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    theta = float(theta)
+    if not (0.0 < theta <= 1.0):
+        raise ValueError("mark: theta must lie in (0, 1], got %r" % (theta,))
+    if not np.isfinite(v).all():
+        raise ValueError("mark: the values must be finite")
+    if (v < 0.0).any():
+        raise ValueError("mark: the values must be >= 0")
+    if v.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    order = np.argsort(-v, kind="stable")
+    cs = np.cumsum(v[order])
+    if not cs[-1] > 0.0:
+        return np.zeros(0, dtype=np.int64)
+    k = int(np.argmax(cs >= theta * cs[-1]))
+    return order[:k + 1].astype(np.int64)
+
+
+_DEFAULT_K = np.array([[-1, -1], [1, -1], [-1, 1], [1, -1], [1, 1], [-1, 1]], dtype=np.float64)      # fem2d's default square
+
+
+def refine_triangles(K, marked) -> np.ndarray:
+    """Rivara longest-edge bisection with closure of a conforming 2-D triangle list K (3m x 2, as fem2d takes it), on the host: no
+    triangle of `marked` (indices into the m triangles) survives and the result is conforming.  To bisect t, look across its
+    longest edge: bisect both sides when the neighbour's longest edge is that edge (or there is no neighbour), else bisect the
+    neighbour first.  Equal lengths break to the lexicographically smallest sorted pair of end points, so both sides agree.
+    Midpoints are (a + b) / 2, fem2d's expression; the children (a, m, c), (m, b, c) keep the parent's orientation and take its
+    place; every other triangle keeps its bits and its relative order.  An empty `marked` returns K bitwise."""
+    K = np.array(K, dtype=np.float64)
+    if K.ndim != 2 or K.shape[1] != 2 or K.shape[0] % 3 or K.shape[0] < 3:
+        raise ValueError("refine_triangles: K must be a (3m, 2) array, got %r" % (tuple(K.shape),))
+    if not np.isfinite(K).all():
+        raise ValueError("refine_triangles: K must be finite")
+    m = K.shape[0] // 3
+    marked = np.asarray(marked).reshape(-1)
+    if marked.size and not np.issubdtype(marked.dtype, np.integer):
+        raise TypeError("refine_triangles: marked must hold triangle indices")
+    marked = [int(t) for t in marked]
+    if any(not 0 <= t < m for t in marked):
+        raise ValueError("refine_triangles: marked holds an index outside [0, %d)" % m)
+    if not marked:
+        return K
+    verts = [tuple((float(K[3 * t + i, 0]), float(K[3 * t + i, 1])) for i in range(3)) for t in range(m)]
+    children = [None] * m          # per node of the refinement forest: None (a leaf) or its two children
+    edges = {}                     # sorted end points -> the leaves that have this edge
+
+    def edge_keys(v):
+        return [tuple(sorted((v[i], v[(i + 1) % 3]))) for i in range(3)]
+
+    def attach(t):
+        for key in edge_keys(verts[t]):
+            edges.setdefault(key, []).append(t)
+
+    def detach(t):
+        for key in edge_keys(verts[t]):
+            edges[key].remove(t)
+
+    def longest(t):
+        v, best = verts[t], None
+        for i, key in enumerate(edge_keys(verts[t])):
+            (ax, ay), (bx, by) = key
+            rank = (-((bx - ax) * (bx - ax) + (by - ay) * (by - ay)), key)
+            if best is None or rank < best[0]:
+                best = (rank, i, key)
+        return best[1], best[2]
+
+    def split(t, i):
+        v = verts[t]
+        a, b, c = v[i], v[(i + 1) % 3], v[(i + 2) % 3]
+        mid = ((a[0] + b[0]) / 2, (a[1] + b[1]) / 2)
+        detach(t)
+        kids = []
+        for tri in ((a, mid, c), (mid, b, c)):
+            verts.append(tri)
+            children.append(None)
+            kids.append(len(verts) - 1)
+            attach(kids[-1])
+        children[t] = kids
+
+    for t in range(m):
+        attach(t)
+    for t0 in marked:
+        if children[t0] is not None:
+            continue
+        stack = [t0]
+        while stack:
+            t = stack[-1]
+            if children[t] is not None:
+                stack.pop()
+                continue
+            i, key = longest(t)
+            others = [o for o in edges[key] if o != t]
+            if len(others) > 1:
+                raise ValueError("refine_triangles: an edge is shared by more than two triangles")
+            if not others:
+                split(t, i)
+            else:
+                o = others[0]
+                io, keyo = longest(o)
+                if keyo == key:
+                    split(t, i)
+                    split(o, io)
+                else:
+                    stack.append(o)
+    out = []
+    todo = list(range(m - 1, -1, -1))
+    while todo:
+        t = todo.pop()
+        if children[t] is None:
+            out.append(verts[t])
+        else:
+            todo.extend(reversed(children[t]))
+    return np.array(out, dtype=np.float64).reshape(-1, 2)
+
+
+def adapt(K, L, p, steps, theta=0.5, **amgb_kwargs) -> list:
+    """Solve, estimate, mark, refine the coarse mesh, solve again: `steps` refinements of the 2-D coarse mesh K (None: fem2d's
+    default square), every mesh solved by amgb on fem2d_mpi(L, K) with `amgb_kwargs`.  The indicators of a solve, summed per
+    coarse triangle (ErrorIndicators.coarse), feed mark(., theta), and refine_triangles gives the next K.  Returns the steps + 1
+    triples (K, sol, ErrorIndicators), the last one on the finest mesh.  f, dirichlet and neumann of `amgb_kwargs` also go to
+    estimate (f defaults to amgb's)."""
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("adapt: steps must be >= 0")
+    K = _DEFAULT_K.copy() if K is None else np.array(K, dtype=np.float64)
+    geo_kw = {k: amgb_kwargs[k] for k in ("Ti", "backend") if k in amgb_kwargs}
+    solve_kw = {k: v for k, v in amgb_kwargs.items() if k not in geo_kw}
+    est_kw = dict(f=solve_kw.get("f", DEFAULT_F[2]), dirichlet=solve_kw.get("dirichlet"), neumann=solve_kw.get("neumann"))
+    out = []
+    for step in range(steps + 1):
+        sol = amgb(fem2d_mpi(int(L), K, **geo_kw), p=p, **solve_kw)
+        ind = estimate(sol, p, **est_kw)
+        out.append((K, sol, ind))
+        if step < steps:
+            K = refine_triangles(K, mark(ind.coarse(int(L)), theta))
+    return out
 
 
 # --------------------------------------------------------------------------- mixed boundary conditions

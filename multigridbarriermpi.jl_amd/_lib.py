@@ -147,6 +147,11 @@ PROTOTYPES = {
     "mgb_geo_boundary_dims": [H, c_int_p, c_int_p, c_int_p],
     "mgb_geo_boundary_get": [H, c_i32_p, c_i32_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_geo_boundary_flux_host": [H, C.c_int, C.POINTER(c_dbl_p), C.c_int, C.c_int, C.c_double, c_dbl_p, c_u8_p, c_dbl_p, c_dbl_p],
+    "mgb_geo_interior_dims": [H, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p],
+    "mgb_geo_interior_get": [H, c_i32_p, c_i32_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_i32_p],
+    "mgb_estimate": [H, H, C.c_int, C.c_int, C.c_double, H, H, C.c_double, C.c_int, C.c_double, c_dbl_p, c_u8_p, H, c_dbl_p],
+    "mgb_geo_estimate_host": [H, c_dbl_p, C.c_int, C.c_int, C.c_double, c_dbl_p, c_dbl_p, C.c_double, C.c_int, C.c_double, c_dbl_p,
+                              c_u8_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_geo_dirichlet_on": [H, C.c_char_p, c_u8_p],
     "mgb_geo_boundary_incidence": [H, c_int_p, c_int_p, c_i32_p, c_i32_p, c_i32_p],
     "mgb_boundary_incidence": [H, c_int_p, c_int_p, c_i32_p, c_i32_p, c_i32_p],

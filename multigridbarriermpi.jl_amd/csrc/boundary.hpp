@@ -15,6 +15,8 @@
 //   Five contributions: omega sn | omega u_i | omega | |sn| | |t|_2   (three sums, two NaN-sticky maxima).
 //   A non-finite u_i or sigma, or an exponent that is not a finite real >= 1, makes all five NaN.  A facet left out by the mask
 //   contributes nothing; its per-facet value is 0.  The per-facet value is the sum of omega sn over j = 0..q-1 in that order.
+//   The same key sort also gives the INTERIOR facets (exactly two elements) and the element -> facet table of the error
+//   indicators (estimate.hpp): struct Interior below.
 // The arithmetic of Node::contributions is kept as written (fp contract off), as energy.hpp's is.
 #pragma once
 #include <array>
@@ -163,7 +165,63 @@ inline void local_facet(int dim, int k, int lf, std::vector<int>& rows, std::vec
   }
 }
 
-inline Facets build_facets(const GeometryHost& g) {
+// weights (q), outward unit normal (dim, zeroed by the caller), measure and centre (dim) of local facet lf of element e
+inline void facet_geometry(const GeometryHost& g, int dim, int k, int block, int e, int lf, const std::vector<int>& rows, double* w,
+                           double* n, double* c, double& measure) {
+  const double nc[3][4] = {{0.5, 0.5, 0, 0}, {1.0 / 6, 4.0 / 6, 1.0 / 6, 0}, {1.0 / 8, 3.0 / 8, 3.0 / 8, 1.0 / 8}};      // fem3d_native's
+  const double* xe = g.x.data() + (size_t)e * block * dim;
+  if (dim == 2) {
+    const double* a = xe + 2 * rows[0];
+    const double* m = xe + 2 * rows[1];
+    const double* b = xe + 2 * rows[2];
+    const double dx = b[0] - a[0], dy = b[1] - a[1], len = std::sqrt(dx * dx + dy * dy);
+    const double cx = (xe[0] + xe[2] + xe[4]) / 3.0, cy = (xe[1] + xe[3] + xe[5]) / 3.0;
+    n[0] = dy / len, n[1] = -dx / len;
+    if (n[0] * (m[0] - cx) + n[1] * (m[1] - cy) < 0.0) n[0] = -n[0], n[1] = -n[1];
+    w[0] = len * (1.0 / 6), w[1] = len * (4.0 / 6), w[2] = len * (1.0 / 6);
+    measure = len;
+    c[0] = m[0], c[1] = m[1];
+  } else {
+    const double* lo = xe;                                   // first and last row: opposite corners of the box, in either order
+    const double* hi = xe + (size_t)(block - 1) * dim;
+    const int axis = dim == 1 ? 0 : lf / 2;
+    const double* p = xe + (size_t)rows[0] * dim;            // a node of the facet: it carries the facet coordinate
+    double area = 1.0;
+    for (int d = 0; d < dim; ++d) {
+      c[d] = d == axis ? p[d] : 0.5 * (lo[d] + hi[d]);
+      if (d != axis) area *= std::fabs(hi[d] - lo[d]);
+    }
+    n[axis] = p[axis] > 0.5 * (lo[axis] + hi[axis]) ? 1.0 : -1.0;
+    measure = area;
+    if (dim == 1) {
+      w[0] = 1.0;
+    } else {
+      const int m1 = k + 1;
+      for (int b = 0; b < m1; ++b)
+        for (int a = 0; a < m1; ++a) w[a + m1 * b] = area * (nc[k - 1][a] * nc[k - 1][b]);
+    }
+  }
+}
+
+// The interior facets of one geometry, on the host: a facet whose sorted corner dofs occur in exactly
+// two elements.  The first side is the one with the smaller (element, local facet); facets come in ascending (element, local
+// facet) order of their first side.  Weights, measure, centre and normal are those of the first side (the formulas of the
+// boundary facets), the normal pointing out of it.  nodes holds the q rows of the first side in local_facet order, then the q
+// rows of the second side permuted so that node j of both sides has the same continuous dof.  elem_facet (nel x nlf): the
+// interior facet of (element, local facet), or -1 - f for boundary facet f -- every local facet is one or the other.
+struct Interior {
+  int dim = 0, k = 0, q = 0, nif = 0, nel = 0, nlf = 0;
+  std::vector<int> elements;       // nif x 2
+  std::vector<int> nodes;          // nif x 2 x q global rows
+  std::vector<double> weights;     // nif x q
+  std::vector<double> normal;      // nif x dim, out of the first side
+  std::vector<double> measure;     // nif
+  std::vector<double> centre;      // nif x dim
+  std::vector<int> elem_facet;     // nel x nlf
+};
+
+// one key sort for both lists; each output is nullable
+inline void build_facet_lists(const GeometryHost& g, Facets* Fout, Interior* Iout) {
   const interp::Locator L = interp::build_locator(g);      // validates x, dim, block and the shape of every element
   const std::vector<int> dof = continuous_dofs(g);
   const int dim = L.dim, k = L.k, block = L.block, nel = L.nel;
@@ -189,66 +247,85 @@ inline Facets build_facets(const GeometryHost& g) {
     if (a.d != b.d) return a.d < b.d;
     return a.e != b.e ? a.e < b.e : a.lf < b.lf;
   });
-  std::vector<std::pair<int, int>> bnd;      // (element, local facet)
+  std::vector<std::pair<int, int>> bnd;                          // (element, local facet)
+  std::vector<std::array<int, 4>> pairs;                         // (element, local facet) of the first side, then of the second
   for (size_t i = 0; i < keys.size();) {
     size_t j = i + 1;
     while (j < keys.size() && keys[j].d == keys[i].d) ++j;
     if (j - i > 2) throw ArgError("boundary: a facet is shared by more than two elements (non-manifold mesh)");
     if (j - i == 2 && keys[i].e == keys[i + 1].e) throw ArgError("boundary: two facets of one element share their corner dofs");
     if (j - i == 1) bnd.emplace_back(keys[i].e, keys[i].lf);
+    else pairs.push_back({keys[i].e, keys[i].lf, keys[i + 1].e, keys[i + 1].lf});      // the sort put the smaller side first
     i = j;
   }
   std::sort(bnd.begin(), bnd.end());
-  Facets F;
-  F.dim = dim, F.k = k, F.q = q, F.nf = (int)bnd.size();
-  F.element.resize(F.nf);
-  F.nodes.resize((size_t)F.nf * q);
-  F.weights.resize((size_t)F.nf * q);
-  F.normal.assign((size_t)F.nf * dim, 0.0);
-  F.measure.resize(F.nf);
-  F.centre.resize((size_t)F.nf * dim);
-  const double nc[3][4] = {{0.5, 0.5, 0, 0}, {1.0 / 6, 4.0 / 6, 1.0 / 6, 0}, {1.0 / 8, 3.0 / 8, 3.0 / 8, 1.0 / 8}};      // fem3d_native's
-  for (int f = 0; f < F.nf; ++f) {
-    const int e = bnd[f].first, lf = bnd[f].second;
-    const double* xe = g.x.data() + (size_t)e * block * dim;
-    F.element[f] = e;
-    for (int j = 0; j < q; ++j) F.nodes[(size_t)f * q + j] = e * block + rows[lf][j];
-    double* w = F.weights.data() + (size_t)f * q;
-    double* n = F.normal.data() + (size_t)f * dim;
-    double* c = F.centre.data() + (size_t)f * dim;
-    if (dim == 2) {
-      const double* a = xe + 2 * rows[lf][0];
-      const double* m = xe + 2 * rows[lf][1];
-      const double* b = xe + 2 * rows[lf][2];
-      const double dx = b[0] - a[0], dy = b[1] - a[1], len = std::sqrt(dx * dx + dy * dy);
-      const double cx = (xe[0] + xe[2] + xe[4]) / 3.0, cy = (xe[1] + xe[3] + xe[5]) / 3.0;
-      n[0] = dy / len, n[1] = -dx / len;
-      if (n[0] * (m[0] - cx) + n[1] * (m[1] - cy) < 0.0) n[0] = -n[0], n[1] = -n[1];
-      w[0] = len * (1.0 / 6), w[1] = len * (4.0 / 6), w[2] = len * (1.0 / 6);
-      F.measure[f] = len;
-      c[0] = m[0], c[1] = m[1];
-    } else {
-      const double* lo = xe;                                   // first and last row: opposite corners of the box, in either order
-      const double* hi = xe + (size_t)(block - 1) * dim;
-      const int axis = dim == 1 ? 0 : lf / 2;
-      const double* p = xe + (size_t)rows[lf][0] * dim;        // a node of the facet: it carries the facet coordinate
-      double area = 1.0;
-      for (int d = 0; d < dim; ++d) {
-        c[d] = d == axis ? p[d] : 0.5 * (lo[d] + hi[d]);
-        if (d != axis) area *= std::fabs(hi[d] - lo[d]);
-      }
-      n[axis] = p[axis] > 0.5 * (lo[axis] + hi[axis]) ? 1.0 : -1.0;
-      F.measure[f] = area;
-      if (dim == 1) {
-        w[0] = 1.0;
-      } else {
-        const int m1 = k + 1;
-        for (int b = 0; b < m1; ++b)
-          for (int a = 0; a < m1; ++a) w[a + m1 * b] = area * (nc[k - 1][a] * nc[k - 1][b]);
-      }
+  std::sort(pairs.begin(), pairs.end());
+  if (Fout) {
+    Facets& F = *Fout;
+    F = Facets();
+    F.dim = dim, F.k = k, F.q = q, F.nf = (int)bnd.size();
+    F.element.resize(F.nf);
+    F.nodes.resize((size_t)F.nf * q);
+    F.weights.resize((size_t)F.nf * q);
+    F.normal.assign((size_t)F.nf * dim, 0.0);
+    F.measure.resize(F.nf);
+    F.centre.resize((size_t)F.nf * dim);
+    for (int f = 0; f < F.nf; ++f) {
+      const int e = bnd[f].first, lf = bnd[f].second;
+      F.element[f] = e;
+      for (int j = 0; j < q; ++j) F.nodes[(size_t)f * q + j] = e * block + rows[lf][j];
+      facet_geometry(g, dim, k, block, e, lf, rows[lf], F.weights.data() + (size_t)f * q, F.normal.data() + (size_t)f * dim,
+                     F.centre.data() + (size_t)f * dim, F.measure[f]);
     }
   }
+  if (Iout) {
+    Interior& I = *Iout;
+    I = Interior();
+    I.dim = dim, I.k = k, I.q = q, I.nif = (int)pairs.size(), I.nel = nel, I.nlf = nlf;
+    I.elements.resize((size_t)I.nif * 2);
+    I.nodes.resize((size_t)I.nif * 2 * q);
+    I.weights.resize((size_t)I.nif * q);
+    I.normal.assign((size_t)I.nif * dim, 0.0);
+    I.measure.resize(I.nif);
+    I.centre.resize((size_t)I.nif * dim);
+    I.elem_facet.assign((size_t)nel * nlf, INT_MIN);
+    for (int f = 0; f < (int)bnd.size(); ++f) I.elem_facet[(size_t)bnd[f].first * nlf + bnd[f].second] = -1 - f;
+    std::vector<char> used((size_t)q);
+    for (int f = 0; f < I.nif; ++f) {
+      const int ea = pairs[f][0], la = pairs[f][1], eb = pairs[f][2], lb = pairs[f][3];
+      I.elements[2 * (size_t)f] = ea, I.elements[2 * (size_t)f + 1] = eb;
+      I.elem_facet[(size_t)ea * nlf + la] = f;
+      I.elem_facet[(size_t)eb * nlf + lb] = f;
+      int* na = I.nodes.data() + (size_t)f * 2 * q;
+      int* nb = na + q;
+      std::fill(used.begin(), used.end(), 0);
+      for (int j = 0; j < q; ++j) {
+        na[j] = ea * block + rows[la][j];
+        int hit = -1;
+        for (int t = 0; t < q && hit < 0; ++t)
+          if (!used[t] && dof[(size_t)eb * block + rows[lb][t]] == dof[na[j]]) hit = t;
+        if (hit < 0) throw ArgError("boundary: the two sides of an interior facet cannot be matched node by node");
+        used[hit] = 1;
+        nb[j] = eb * block + rows[lb][hit];
+      }
+      facet_geometry(g, dim, k, block, ea, la, rows[la], I.weights.data() + (size_t)f * q, I.normal.data() + (size_t)f * dim,
+                     I.centre.data() + (size_t)f * dim, I.measure[f]);
+    }
+    for (size_t t = 0; t < I.elem_facet.size(); ++t)
+      if (I.elem_facet[t] == INT_MIN) throw InternalError("boundary: a local facet is neither interior nor on the boundary");
+  }
+}
+
+inline Facets build_facets(const GeometryHost& g) {
+  Facets F;
+  build_facet_lists(g, &F, nullptr);
   return F;
+}
+
+inline Interior build_interior(const GeometryHost& g) {
+  Interior I;
+  build_facet_lists(g, nullptr, &I);
+  return I;
 }
 
 // facets per workgroup (a facet never straddles two workgroups), workgroups per field, doubles of scratch of the two launches

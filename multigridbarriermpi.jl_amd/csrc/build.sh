@@ -36,6 +36,7 @@ compile "$HERE/_obj/interp.o" "$HERE/interp.hip" "$HIPCC" --offload-arch=gfx950 
 compile "$HERE/_obj/norms.o" "$HERE/norms.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/energy.o" "$HERE/energy.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/boundary.o" "$HERE/boundary.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
+compile "$HERE/_obj/estimate.o" "$HERE/estimate.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/parabolic.o" "$HERE/parabolic.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/amg_mg.o" "$HERE/amg_mg.cpp" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS -x hip
 compile "$HERE/_obj/gpuchol.o" "$HERE/gpuchol.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS $PRELOAD
@@ -46,5 +47,5 @@ for pid in "${pids[@]}"; do
   wait "$pid" || { echo "build.sh: a compile job failed" >&2; exit 1; }
 done
 rm -f "$OUT/libmgb_hip.so"
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,kernels,kernels_f32,mg,interp,norms,energy,boundary,parabolic,gpuchol,amg,amg_mg,comm,capi}.o -lpthread -ldl
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,kernels,kernels_f32,mg,interp,norms,energy,boundary,estimate,parabolic,gpuchol,amg,amg_mg,comm,capi}.o -lpthread -ldl
 echo "built $OUT/libmgb_hip.so"

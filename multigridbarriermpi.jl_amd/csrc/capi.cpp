@@ -11,6 +11,7 @@
 #include "boundary.hpp"
 #include "interp.hpp"
 #include "energy.hpp"
+#include "estimate.hpp"
 #include "mixed.hpp"
 #include "norms.hpp"
 
@@ -64,6 +65,10 @@ struct mgb_boundary_s {
   boundary::Incidence inc;                         // mgb_boundary_load: the row-sorted incidence table, built with the facets
   DevBuf<int> inc_rows, inc_start, inc_idx;
   DevBuf<double> load_h;                           // ... the B x nf x q data of the call, grown on demand
+  boundary::Interior I;                            // mgb_estimate: the interior facets and the element -> facet table, built with the facets
+  DevBuf<int> inodes, elem_facet;
+  DevBuf<double> iweights, inormal;
+  DevBuf<double> est_sigma, est_J, est_N, est_scratch, est_h;      // ... flux, per-facet values, partials, Neumann data: grown on demand
 };
 struct mgb_plan_s {
   LevelPlan plan;
@@ -1421,8 +1426,10 @@ int mgb_boundary_create(mgb_locator loc, mgb_geo g, mgb_boundary* out) {
     need(loc && g && out, "boundary_create: null argument");
     const interp::Locator& L = loc->loc;
     need(L.n == g->g.n && L.dim == g->g.dim && L.block == g->g.block, "boundary_create: the locator belongs to another geometry");
-    auto* b = new mgb_boundary_s{loc, boundary::build_facets(g->g), {}, {}, {}, {}, {}, {}, {}};
+    auto* b = new mgb_boundary_s();
     try {
+      b->loc = loc;
+      boundary::build_facet_lists(g->g, &b->F, &b->I);
       hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
       b->nodes.upload(b->F.nodes.data(), b->F.nodes.size());
       b->weights.upload(b->F.weights.data(), b->F.weights.size());
@@ -1431,6 +1438,10 @@ int mgb_boundary_create(mgb_locator loc, mgb_geo g, mgb_boundary* out) {
       b->inc_rows.upload(b->inc.rows.data(), b->inc.rows.size());
       b->inc_start.upload(b->inc.start.data(), b->inc.start.size());
       b->inc_idx.upload(b->inc.idx.data(), b->inc.idx.size());
+      b->inodes.upload(b->I.nodes.data(), b->I.nodes.size());
+      b->iweights.upload(b->I.weights.data(), b->I.weights.size());
+      b->inormal.upload(b->I.normal.data(), b->I.normal.size());
+      b->elem_facet.upload(b->I.elem_facet.data(), b->I.elem_facet.size());
     } catch (...) {
       delete b;
       throw;
@@ -1547,6 +1558,158 @@ int mgb_geo_boundary_flux_host(mgb_geo g, int B, const double* const* z, int S, 
     A.mask = mask;
     A.nf = F.nf, A.q = F.q;
     boundary::boundary_flux_host(F.dim, F.k, A, out, facet_flux);
+  });
+}
+
+// ---- residual error indicators (estimate.hpp / estimate.hip)
+namespace {
+void need_estimate_shape(const char* who, int S, int u, double p, double r, int own_scale, double scale) {
+  const std::string w(who);
+  if (S < 1) throw std::invalid_argument(w + ": S must be >= 1");
+  if (!good_q(p)) throw std::invalid_argument(w + ": p must be finite and >= 1");
+  if (u < 0 || u >= S) throw std::invalid_argument(w + ": column u outside [0, S)");
+  if (!good_q(r)) throw std::invalid_argument(w + ": r must be finite and >= 1");
+  if (own_scale && !std::isfinite(scale)) throw std::invalid_argument(w + ": the scale must be finite");
+}
+}  // namespace
+int mgb_geo_interior_dims(mgb_geo g, int* nif, int* q, int* dim, int* nel, int* nlf) {
+  return guard([&] {
+    need(g, "geo_interior_dims: null geometry");
+    const boundary::Interior I = boundary::build_interior(g->g);
+    if (nif) *nif = I.nif;
+    if (q) *q = I.q;
+    if (dim) *dim = I.dim;
+    if (nel) *nel = I.nel;
+    if (nlf) *nlf = I.nlf;
+  });
+}
+int mgb_geo_interior_get(mgb_geo g, int32_t* elements, int32_t* nodes, double* weights, double* normal, double* measure,
+                         double* centre, int32_t* elem_facet) {
+  return guard([&] {
+    need(g, "geo_interior_get: null geometry");
+    const boundary::Interior I = boundary::build_interior(g->g);
+    if (elements) std::copy(I.elements.begin(), I.elements.end(), elements);
+    if (nodes) std::copy(I.nodes.begin(), I.nodes.end(), nodes);
+    if (weights) std::copy(I.weights.begin(), I.weights.end(), weights);
+    if (normal) std::copy(I.normal.begin(), I.normal.end(), normal);
+    if (measure) std::copy(I.measure.begin(), I.measure.end(), measure);
+    if (centre) std::copy(I.centre.begin(), I.centre.end(), centre);
+    if (elem_facet) std::copy(I.elem_facet.begin(), I.elem_facet.end(), elem_facet);
+  });
+}
+int mgb_estimate(mgb_boundary bd, mgb_vec z, int S, int u, double p, mgb_vec p_nodal, mgb_vec f, double r, int own_scale,
+                 double scale, const double* h_host, const unsigned char* mask_host, mgb_vec eta, double* out_host) {
+  return guard([&] {
+    need(bd && z && eta && out_host, "estimate: null argument");
+    need_estimate_shape("estimate", S, u, p, r, own_scale, scale);
+    mgb_locator_s* loc = bd->loc;
+    need(loc->ctx->ctx.world == 1, "estimate: sharded contexts are not supported");
+    const interp::Locator& L = loc->loc;
+    const boundary::Facets& F = bd->F;
+    const boundary::Interior& I = bd->I;
+    need(z->n == (long long)L.n * S, "estimate: z must hold n x S values");
+    need(eta->n == (long long)I.nel * estimate::kParts, "estimate: eta must hold nel x 3 values");
+    need(!p_nodal || p_nodal->n == L.n, "estimate: p_nodal must hold n values");
+    need(!f || f->n == L.n, "estimate: f must hold n values");
+    need(z->ctx == loc->ctx && eta->ctx == loc->ctx && (!p_nodal || p_nodal->ctx == loc->ctx) && (!f || f->ctx == loc->ctx),
+         "estimate: vectors of another context");
+    need(z != eta, "estimate: eta must not be z");
+    const bool neu = h_host != nullptr && F.nf > 0;
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const int facets = I.nif + (neu ? F.nf : 0);
+    const size_t nsig = (size_t)L.n * L.dim, nd = estimate::scratch_doubles(I.nel, L.block, facets, F.q), nh = (size_t)F.nf * F.q;
+    // an earlier call's launches may still read the buffers: wait before any of them is replaced
+    if (bd->est_sigma.n < nsig || bd->est_J.n < (size_t)I.nif || bd->est_scratch.n < nd || (neu && (bd->est_N.n < (size_t)F.nf ||
+        bd->est_h.n < nh || (mask_host && bd->mask.n < (size_t)F.nf)))) {
+      hip_check(hipStreamSynchronize(st), "sync estimate");
+      if (bd->est_sigma.n < nsig) bd->est_sigma.alloc(nsig);
+      if (bd->est_J.n < (size_t)I.nif) bd->est_J.alloc((size_t)I.nif);
+      if (bd->est_scratch.n < nd) bd->est_scratch.alloc(nd);
+      if (neu && bd->est_N.n < (size_t)F.nf) bd->est_N.alloc((size_t)F.nf);
+      if (neu && bd->est_h.n < nh) bd->est_h.alloc(nh);
+      if (neu && mask_host && bd->mask.n < (size_t)F.nf) bd->mask.alloc((size_t)F.nf);
+    }
+    if (neu) {
+      hip_check(hipMemcpyAsync(bd->est_h.p, h_host, nh * sizeof(double), hipMemcpyHostToDevice, st), "H2D h");
+      if (mask_host) hip_check(hipMemcpyAsync(bd->mask.p, mask_host, (size_t)F.nf, hipMemcpyHostToDevice, st), "H2D mask");
+    }
+    energy::Args E;
+    E.own = L.view(loc->cellptr.p, loc->cellelem.p, loc->x.p);
+    E.w = loc->w.p;
+    E.p_nodal = p_nodal ? p_nodal->buf.p : nullptr;
+    E.p = p;
+    E.n = L.n, E.S = S, E.u = u, E.B = 1;
+    energy::launch_field_flux(st, L.dim, L.k, E, z->buf.p, bd->est_sigma.p);
+    hip_check(hipGetLastError(), "estimate flux launch");
+    estimate::Args A;
+    A.own = E.own;
+    A.w = E.w, A.p_nodal = E.p_nodal, A.p = p;
+    A.sigma = bd->est_sigma.p;
+    A.f = f ? f->buf.p : nullptr;
+    A.r = r, A.scale = scale, A.own_scale = own_scale != 0;
+    A.n = L.n, A.nel = I.nel, A.nlf = I.nlf, A.q = F.q;
+    A.inodes = bd->inodes.p, A.iweights = bd->iweights.p, A.inormal = bd->inormal.p, A.nif = I.nif;
+    A.bnodes = bd->nodes.p, A.bweights = bd->weights.p, A.bnormal = bd->normal.p;
+    A.mask = neu && mask_host ? bd->mask.p : nullptr;
+    A.h = neu ? bd->est_h.p : nullptr;
+    A.nf = F.nf;
+    A.elem_facet = bd->elem_facet.p;
+    estimate::launch_estimate(st, L.dim, L.k, A, bd->est_J.p, bd->est_N.p, eta->buf.p, bd->est_scratch.p);
+    hip_check(hipGetLastError(), "estimate launch");
+    hip_check(hipStreamSynchronize(st), "sync estimate");
+    hip_check(hipMemcpy(out_host, bd->est_scratch.p + (nd - estimate::kCols), estimate::kCols * sizeof(double), hipMemcpyDeviceToHost),
+              "D2H");
+  });
+}
+int mgb_geo_estimate_host(mgb_geo g, const double* z, int S, int u, double p, const double* p_nodal, const double* f, double r,
+                          int own_scale, double scale, const double* h, const unsigned char* mask, double* eta, double* J, double* N,
+                          double* sigma_out, double* out) {
+  return guard([&] {
+    need(g && z && eta && out, "geo_estimate_host: null argument");
+    need_estimate_shape("geo_estimate_host", S, u, p, r, own_scale, scale);
+    need(g->g.w.size() == (size_t)g->g.n, "geo_estimate_host: the geometry must carry one weight per node");
+    if (p_nodal)
+      for (int i = 0; i < g->g.n; ++i) need(good_q(p_nodal[i]), "geo_estimate_host: every p_nodal must be finite and >= 1");
+    boundary::Facets F;
+    boundary::Interior I;
+    boundary::build_facet_lists(g->g, &F, &I);
+    const int n = g->g.n, dim = F.dim;
+    energy::Args E;
+    E.own.block = g->g.block;
+    E.own.nel = n / g->g.block;
+    E.own.x = g->g.x.data();
+    E.w = g->g.w.data();
+    E.p_nodal = p_nodal;
+    E.p = p;
+    E.n = n, E.S = S, E.u = u, E.B = 1;
+    std::vector<double> sigma((size_t)n * dim), Jv((size_t)I.nif), Nv((size_t)F.nf);
+    estimate::field_flux_host(dim, F.k, E, z, sigma.data());
+    const bool neu = h != nullptr && F.nf > 0;
+    estimate::Args A;
+    A.own = E.own;
+    A.w = E.w, A.p_nodal = p_nodal, A.p = p;
+    A.sigma = sigma.data();
+    A.f = f;
+    A.r = r, A.scale = scale, A.own_scale = own_scale != 0;
+    A.n = n, A.nel = I.nel, A.nlf = I.nlf, A.q = F.q;
+    A.inodes = I.nodes.data(), A.iweights = I.weights.data(), A.inormal = I.normal.data(), A.nif = I.nif;
+    A.bnodes = F.nodes.data(), A.bweights = F.weights.data(), A.bnormal = F.normal.data();
+    A.mask = neu ? mask : nullptr;
+    A.h = neu ? h : nullptr;
+    A.nf = F.nf;
+    A.elem_facet = I.elem_facet.data();
+    std::vector<double> etav((size_t)I.nel * estimate::kParts);
+    double res[estimate::kCols];
+    estimate::estimate_host(dim, F.k, A, etav.data(), Jv.data(), Nv.data(), res);
+    std::copy(etav.begin(), etav.end(), eta);
+    if (J) std::copy(Jv.begin(), Jv.end(), J);
+    if (N) {
+      if (neu) std::copy(Nv.begin(), Nv.end(), N);
+      else std::fill(N, N + F.nf, 0.0);
+    }
+    if (sigma_out) std::copy(sigma.begin(), sigma.end(), sigma_out);
+    std::copy(res, res + estimate::kCols, out);
   });
 }
 
