@@ -198,6 +198,11 @@ int mgb_amg_chol_info(mgb_amg a, int level, int* split_world, double* exchange_d
  * mgb_amg_chol_tree) and its column among that node's own columns (0 .. ns - 1).  kind / workgroups may be null. */
 int mgb_amg_chol_schedule(mgb_amg a, int level, int cap, int* nlaunch, int* kind, int* workgroups, int* unknown_node,
                           int* unknown_col);
+/* pre-mapped child contributions of that chain (MGB_CHOL_PREMAP; nullable outputs), per launch of the first
+ * min(cap, launches) in the order of mgb_amg_chol_schedule: consumer = 1 if the launch reads its fronts' contribution slabs
+ * instead of gathering through the index maps, producers = how many of its fronts store their Schur complement into their
+ * parent's slab; *slab_bytes = device memory of the slabs */
+int mgb_amg_chol_premap(mgb_amg a, int level, int cap, int* consumer, int* producers, double* slab_bytes);
 /* the elimination tree of that factorisation in postorder (children first): own size, front size and parent (-1 = root)
  * of the first min(cap, *nnodes) nodes -- mgb_plan_chol_tree for the level as the device factors it */
 int mgb_amg_chol_tree(mgb_amg a, int level, int cap, int* nnodes, int* ns, int* nf, int* parent);
@@ -642,6 +647,17 @@ int mgb_plan_chol_tree(mgb_plan p, int dim, int cap, int* nnodes, int* ns, int* 
  * of its boundary list and its first own unknown.  Each array is filled up to its capacity. */
 int mgb_plan_chol_bwd_fused(mgb_plan p, int dim, int cut, int top_nf, int threads, int* info, int cap_wg, int* wg, int cap_bdry,
                             int* bdry, int* slots, int cap_nodes, int* bofs, int* first);
+/* host-only: the tables of the pre-mapped child contributions (csrc/chol_premap.hpp) for this level's tree under the
+ * given knobs: leaf / single = MGB_CHOL_LEAF / MGB_CHOL_SINGLE, mode = MGB_CHOL_PREMAP, tiles = MGB_CHOL_PREMAP_TILES.
+ * info[5] = nodes, heights, forward-map entries, inverse-map entries, slab doubles.  Per node (cap_nodes): height,
+ * producer flag, soff (2 per node: slab offset per child slot, -1 = none), eoff (slab it stores into, -1 = its own front),
+ * fofs (start of its forward map: nb + 1 entries, boundary row -> parent front row, the last one the parent's
+ * right-hand-side row; -1 = root), iofs (start of its two (nf + 1)-long inverse maps, -1 = no children).  Per height
+ * (cap_heights): hkind (0 Leaf, 1 Single*, 2 Start + panels), hwg (workgroups of its first launch), hconsumer (that launch
+ * reads the slabs).  fwd / pinv: the maps.  Each array is nullable and filled up to its capacity. */
+int mgb_plan_chol_premap(mgb_plan p, int dim, int leaf, int single, int mode, int tiles, long long* info, int cap_nodes, int* height,
+                         int* producer, long long* soff, long long* eoff, int* fofs, int* iofs, int cap_heights, int* hkind, int* hwg,
+                         int* hconsumer, int cap_fwd, int* fwd, int cap_pinv, int* pinv);
 int mgb_chol_selftest(int nx, int ny, double* max_residual, double* flops, double* seconds);
 
 #ifdef __cplusplus

@@ -895,20 +895,25 @@ class AMG:
 
     def chol_info(self, l=None):
         """Device factorisation of level l (default finest): ranks it is split over, doubles exchanged and launches per
-        Newton system, and whether the Hessian values stay on the rank that computed them (subtrees = row blocks)."""
+        Newton system, whether the Hessian values stay on the rank that computed them (subtrees = row blocks), and the
+        device memory of the pre-mapped contribution slabs (MGB_CHOL_PREMAP)."""
         sw, ex, la = C.c_int(), C.c_double(), C.c_int()
         call("mgb_amg_chol_info", self.handle, self.L - 1 if l is None else int(l), C.byref(sw), C.byref(ex), C.byref(la))
         vl = C.c_int()
         call("mgb_amg_chol_values_local", self.handle, self.L - 1 if l is None else int(l), C.byref(vl))
-        return dict(split_world=sw.value, exchange_doubles=ex.value, launches=la.value, values_local=bool(vl.value))
+        sb = C.c_double()
+        call("mgb_amg_chol_premap", self.handle, self.L - 1 if l is None else int(l), 0, None, None, C.byref(sb))
+        return dict(split_world=sw.value, exchange_doubles=ex.value, launches=la.value, values_local=bool(vl.value),
+                    slab_bytes=sb.value)
 
     CHOL_KINDS = ("Leaf", "Single", "SingleNarrow", "SingleDense", "SingleDenseNarrow", "Start", "Step", "Step2", "Panel2",
                   "Update2", "BwdRect", "Bwd256", "Bwd1024", "BwdFused")      # kind codes of mgb_amg_chol_schedule
 
     def chol_schedule(self, l=None):
         """Launch chain of the device factorisation of level l (default finest) in launch order: kind names and workgroup
-        counts; per unknown its tree node (postorder) and own column; and per tree node its own size, front size, parent
-        and height (leaves 0).  Read-only."""
+        counts, whether the launch reads pre-mapped contribution slabs (premap_consumer) and how many of its fronts store
+        their Schur complement into one (premap_producers); per unknown its tree node (postorder) and own column; and per
+        tree node its own size, front size, parent and height (leaves 0).  Read-only."""
         l = self.L - 1 if l is None else int(l)
         N = self.level_size(l)[0]
         nl = C.c_int()
@@ -916,6 +921,8 @@ class AMG:
         kind, wg = np.empty(nl.value, dtype=np.int32), np.empty(nl.value, dtype=np.int32)
         node, col = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32)
         call("mgb_amg_chol_schedule", self.handle, l, nl.value, C.byref(nl), iptr(kind), iptr(wg), iptr(node), iptr(col))
+        cons, prod = np.zeros(nl.value, dtype=np.int32), np.zeros(nl.value, dtype=np.int32)
+        call("mgb_amg_chol_premap", self.handle, l, nl.value, iptr(cons), iptr(prod), None)
         nn = C.c_int()
         call("mgb_amg_chol_tree", self.handle, l, 0, C.byref(nn), None, None, None)
         ns, nf, par = (np.empty(nn.value, dtype=np.int32) for _ in range(3))
@@ -925,7 +932,7 @@ class AMG:
             if par[t] >= 0:
                 height[par[t]] = max(height[par[t]], height[t] + 1)
         return dict(kinds=[self.CHOL_KINDS[k] for k in kind], workgroups=wg, unknown_node=node, unknown_col=col, ns=ns, nf=nf,
-                    parent=par, height=height)
+                    parent=par, height=height, premap_consumer=cons.astype(bool), premap_producers=prod)
 
     def hessian_pattern(self, l):
         N, nz = self.level_size(l)

@@ -88,6 +88,7 @@ PROTOTYPES = {
     "mgb_amg_prepare": [H, C.c_int],
     "mgb_amg_chol_info": [H, C.c_int, c_int_p, c_dbl_p, c_int_p],
     "mgb_amg_chol_schedule": [H, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p],
+    "mgb_amg_chol_premap": [H, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p],
     "mgb_amg_chol_tree": [H, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p],
     "mgb_amg_chol_values_local": [H, C.c_int, c_int_p],
     "mgb_amg_level_size": [H, C.c_int, c_int_p, c_int_p],
@@ -188,6 +189,8 @@ PROTOTYPES = {
     "mgb_plan_chol_tree": [H, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p],
     "mgb_plan_chol_bwd_fused": [H, C.c_int, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p, C.c_int,
                                 c_int_p, c_int_p],
+    "mgb_plan_chol_premap": [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ll_p, C.c_int, c_int_p, c_int_p, c_ll_p, c_ll_p, c_int_p,
+                             c_int_p, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int, c_int_p],
     "mgb_chol_selftest": [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p],
 }
 _SPECIAL = {"mgb_last_error": ([], C.c_char_p), "mgb_version": ([], C.c_int), "mgb_device_count": ([], C.c_int)}

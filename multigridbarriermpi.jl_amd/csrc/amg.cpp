@@ -653,6 +653,13 @@ void Amg::chol_schedule(int l, int cap, int* nlaunch, int* kind, int* workgroups
   GpuChol::unknown_columns(lv.chol, unknown_node, unknown_col);
 }
 
+void Amg::chol_premap(int l, int cap, int* consumer, int* producers, double* slab_bytes) {
+  Level& lv = level(l);
+  ensure_chol(lv);
+  lv.gchol.premap_info(cap, consumer, producers);
+  if (slab_bytes) *slab_bytes = lv.gchol.slab_bytes();
+}
+
 void Amg::chol_tree(int l, int cap, int* nnodes, int* ns, int* nf, int* parent) {
   Level& lv = level(l);
   ensure_chol(lv);

@@ -304,6 +304,7 @@ class Amg {
   void chol_info(int l, int* split_world, double* exchange_doubles, int* launches);
   // ... its launch chain (kind code and workgroups per launch, launch order) and per unknown its tree node and own column
   void chol_schedule(int l, int cap, int* nlaunch, int* kind, int* workgroups, int* unknown_node, int* unknown_col);
+  void chol_premap(int l, int cap, int* consumer, int* producers, double* slab_bytes);
   // ... its elimination tree in postorder: own size, front size and parent of the first min(cap, *nnodes) nodes
   void chol_tree(int l, int cap, int* nnodes, int* ns, int* nf, int* parent);
   bool chol_values_local(int l) { return values_stay_local(level(l)); }

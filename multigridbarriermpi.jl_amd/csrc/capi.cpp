@@ -835,6 +835,12 @@ int mgb_amg_chol_info(mgb_amg a, int level, int* split_world, double* exchange_d
     a->amg->chol_info(level, split_world, exchange_doubles, launches);
   });
 }
+int mgb_amg_chol_premap(mgb_amg a, int level, int cap, int* consumer, int* producers, double* slab_bytes) {
+  return guard([&] {
+    need(a, "chol_premap: null handle");
+    a->amg->chol_premap(level, cap, consumer, producers, slab_bytes);
+  });
+}
 int mgb_amg_chol_schedule(mgb_amg a, int level, int cap, int* nlaunch, int* kind, int* workgroups, int* unknown_node,
                           int* unknown_col) {
   return guard([&] {
@@ -2110,6 +2116,39 @@ int mgb_plan_chol_bwd_fused(mgb_plan p, int dim, int cut, int top_nf, int thread
     if (slots) std::copy(P.slots.begin(), P.slots.begin() + mb, slots);
     if (bofs) std::copy(P.bofs.begin(), P.bofs.begin() + mn, bofs);
     if (first) std::copy(fi.begin(), fi.begin() + mn, first);
+  });
+}
+
+int mgb_plan_chol_premap(mgb_plan p, int dim, int leaf, int single, int mode, int tiles, long long* info, int cap_nodes, int* height,
+                         int* producer, long long* soff, long long* eoff, int* fofs, int* iofs, int cap_heights, int* hkind, int* hwg,
+                         int* hconsumer, int cap_fwd, int* fwd, int cap_pinv, int* pinv) {
+  return guard([&] {
+    need(p && info, "chol_premap: bad arguments");
+    MfChol ch;
+    ch.analyze(p->plan.Apat, p->plan.coords.data(), dim);
+    std::vector<int> ns, nf, par, c0, c1;
+    std::vector<const std::vector<int>*> ea;
+    ch.premap_tables(ns, nf, par, c0, c1, ea);
+    PremapKnobs kn = GpuChol::premap_knobs();
+    kn.leaf = leaf != 0;
+    kn.single = single != 0;
+    kn.mode = mode;
+    kn.tiles = tiles;
+    const PremapPlan P = plan_premap(ns, nf, par, c0, c1, ea, kn);
+    const long long v[5] = {(long long)ns.size(), P.nheights, (long long)P.fwd.size(), (long long)P.pinv.size(), P.slab_doubles};
+    std::copy(v, v + 5, info);
+    const size_t mn = std::min<size_t>(std::max(cap_nodes, 0), ns.size()), mh = std::min<size_t>(std::max(cap_heights, 0), P.nheights);
+    if (height) std::copy(P.height.begin(), P.height.begin() + mn, height);
+    if (producer) std::copy(P.producer.begin(), P.producer.begin() + mn, producer);
+    if (soff) std::copy(P.soff.begin(), P.soff.begin() + 2 * mn, soff);
+    if (eoff) std::copy(P.eoff.begin(), P.eoff.begin() + mn, eoff);
+    if (fofs) std::copy(P.fofs.begin(), P.fofs.begin() + mn, fofs);
+    if (iofs) std::copy(P.iofs.begin(), P.iofs.begin() + mn, iofs);
+    if (hkind) std::copy(P.hkind.begin(), P.hkind.begin() + mh, hkind);
+    if (hwg) std::copy(P.hwg.begin(), P.hwg.begin() + mh, hwg);
+    if (hconsumer) std::copy(P.hconsumer.begin(), P.hconsumer.begin() + mh, hconsumer);
+    if (fwd) std::copy(P.fwd.begin(), P.fwd.begin() + std::min<size_t>(std::max(cap_fwd, 0), P.fwd.size()), fwd);
+    if (pinv) std::copy(P.pinv.begin(), P.pinv.begin() + std::min<size_t>(std::max(cap_pinv, 0), P.pinv.size()), pinv);
   });
 }
 

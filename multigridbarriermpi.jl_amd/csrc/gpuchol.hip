@@ -260,12 +260,16 @@ __device__ __forceinline__ void factor_block_wave0(const double* D, int kw, doub
 // the loads of all 32 columns are issued (branch-free) before their stores; (2) the assembled matrix entries and the right-hand side
 // are added; (3) the workgroup of columns 0..31 factors the first pivot block.  Every parent entry belongs to
 // exactly one workgroup and the order of the additions is fixed.
+// PRE (pre-mapped consumer launch, chol_premap.hpp): the children left their contributions in the front's two slabs, in
+// the front's own index order, so every entry is slab0 + slab1 at its own position: no maps, plain coalesced loads.
+template <bool PRE>
 __global__ __launch_bounds__(TB, 3) void front_start_kernel(const GNode* __restrict__ nodes, const StartJob* __restrict__ jobs,
                                                           const int* __restrict__ pinv, const int* __restrict__ asm_src,
                                                           const int* __restrict__ asm_pos, const double* __restrict__ vals,
                                                           const int* __restrict__ perm, const double* __restrict__ b,
                                                           const double* __restrict__ fronts_ro, double* fronts, double* linv,
-                                                          int* fail, long long* prof, int dedicated_pivot) {
+                                                          int* fail, long long* prof, int dedicated_pivot,
+                                                          const double* __restrict__ slabs) {
   __shared__ double sh[2 * PB * LP];
   __shared__ int cb[2][PB];
   STAMP(0);
@@ -281,6 +285,9 @@ __global__ __launch_bounds__(TB, 3) void front_start_kernel(const GNode* __restr
   const bool has[2] = {job.cld[0] > 0, job.cld[1] > 0};
   const int* __restrict__ inv0 = pinv + (has[0] ? job.iofs : 0);
   const int* __restrict__ inv1 = pinv + (has[1] ? job.iofs + ld : 0);
+  // (PRE) the slabs, indexed like F; an absent child contributes the constant 0.0 (the sum is still formed: -0.0 + 0.0 = +0.0)
+  const double* __restrict__ E0 = slabs + (PRE ? job.soff[0] : 0);
+  const double* __restrict__ E1 = slabs + (PRE ? job.soff[1] : 0);
   if (job.rb < 0) {
     // Dedicated pivot job (one per front, first in the launch): the first pivot block is gathered straight into LDS --
     // child0 + child1, then the matrix entries, the order of the assembling workgroups -- and factored at once, instead
@@ -295,9 +302,21 @@ __global__ __launch_bounds__(TB, 3) void front_start_kernel(const GNode* __restr
       apos[u] = (k < job.a1) ? asm_pos[k] : -1;
       asrc[u] = (k < job.a1) ? asm_src[k] : 0;
     }
-    if (tid < 2 * PB) {
+    if (!PRE && tid < 2 * PB) {
       const int s = tid / PB, c = tid % PB;
       cb[s][c] = (has[s] && c < kw) ? (s ? inv1 : inv0)[c] : -1;
+    }
+    double pre[4];
+    if (PRE) {      // needs the descriptor only: requested with the assembly indices
+      const int i = tid % PB, jg = tid / PB;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int j = jg * 4 + u;
+        const bool in = (j <= i && i < kw);
+        const int pos = in ? ld * j + i : 0;      // a slab has ld * nf < 2^31 entries (build() bounds the front)
+        const double x0 = has[0] ? E0[pos] : 0.0, x1 = has[1] ? E1[pos] : 0.0;
+        pre[u] = in ? x0 + x1 : 0.0;
+      }
     }
     double aval[2];
 #pragma unroll
@@ -306,7 +325,11 @@ __global__ __launch_bounds__(TB, 3) void front_start_kernel(const GNode* __restr
     STAMP(1);
     const double* __restrict__ B0 = fronts_ro + boff[0];
     const double* __restrict__ B1 = fronts_ro + boff[1];
-    {
+    if (PRE) {
+      const int i = tid % PB, jg = tid / PB;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) D[i * LP + jg * 4 + u] = pre[u];
+    } else {
       const int i = tid % PB, jg = tid / PB;      // 32 rows x 8 groups of 4 columns
       double v[4];
 #pragma unroll
@@ -340,11 +363,11 @@ __global__ __launch_bounds__(TB, 3) void front_start_kernel(const GNode* __restr
   const int i = c0 + job.rb * TB + tid;        // one row per thread: the workgroup owns rows [c0 + 256 rb, +256)
   // everything that only needs the descriptor is requested together: the column maps, this thread's row maps, the first
   // assembly indices and the right-hand-side permutation (the chain is descriptor -> indices -> data)
-  if (tid < 2 * PB) {
+  if (!PRE && tid < 2 * PB) {
     const int s = tid / PB, c = c0 + tid % PB;
     cb[s][tid % PB] = (has[s] && c < c1) ? (s ? inv1 : inv0)[c] : -1;
   }
-  const int ra0 = (i <= nf && has[0]) ? inv0[i] : -1, ra1 = (i <= nf && has[1]) ? inv1[i] : -1;
+  const int ra0 = (!PRE && i <= nf && has[0]) ? inv0[i] : -1, ra1 = (!PRE && i <= nf && has[1]) ? inv1[i] : -1;
   const int ka = job.a0 + tid;
   const int apos0 = (ka < job.a1) ? asm_pos[ka] : -1, asrc0 = (ka < job.a1) ? asm_src[ka] : 0;
   const bool rhs_wg = (c0 + job.rb * TB <= nf && nf < c0 + (job.rb + 1) * TB);      // this workgroup owns the right-hand-side row
@@ -361,6 +384,19 @@ __global__ __launch_bounds__(TB, 3) void front_start_kernel(const GNode* __restr
 #pragma unroll
     for (int q = 0; q < PB; ++q)
       if (c0 + q < cend) F[(long long)ld * (c0 + q) + i] = 0.0;
+  } else if (PRE && i <= nf) {
+    const int cend = min(c1, i + 1);
+    double v[PB];
+#pragma unroll
+    for (int q = 0; q < PB; ++q) {
+      const bool in = c0 + q < cend;
+      const int pos = in ? ld * (c0 + q) + i : 0;
+      const double x0 = has[0] ? E0[pos] : 0.0, x1 = has[1] ? E1[pos] : 0.0;
+      v[q] = x0 + x1;
+    }
+#pragma unroll
+    for (int q = 0; q < PB; ++q)
+      if (c0 + q < cend) F[(long long)ld * (c0 + q) + i] = v[q];
   } else if (i <= nf) {
     const int cend = min(c1, i + 1);       // lower triangle: columns c <= i (row nf: every column)
     double v[PB];
@@ -1010,16 +1046,24 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 // of workgroups and are bound by how many of them a CU holds): the factor stays in its packed row-major form and the
 // substitutions read it there (as front_leaf does) instead of from a second copy in quad order: 51 instead of 63 KB of
 // LDS, three workgroups per CU instead of two.  Same operations in the same order: bitwise the same result.
-template <bool NARROW, bool DENSE>
+// Pre-mapped child contributions (chol_premap.hpp).  PRE (per launch): the children stored their Schur complements into
+// the front's two slabs in the front's own index order, so the C tile, the panel blocks and the pivot block are
+// slab0 + slab1 at the entry's own position -- no index maps, no barrier before the data loads, addresses that are a base
+// plus constants.  Producer (per workgroup, t.eoff >= 0): the updated C tile goes to the PARENT's slab through the front's
+// forward map (loaded with the first loads of the kernel) instead of the front's own corner, which nobody would read.
+template <bool NARROW, bool DENSE, bool PRE>
 __device__ __forceinline__ void front_single_body(
     const SingleTile* __restrict__ tiles, const int* __restrict__ pinv,
     const int* __restrict__ asm_src, const int* __restrict__ asm_pos, const double* __restrict__ vals,
     const int* __restrict__ perm, const double* __restrict__ b, const double* __restrict__ fronts_ro, double* fronts,
-    double* linv, int* fail, long long* prof) {
+    double* linv, int* fail, long long* prof, const double* __restrict__ slabs_ro, double* slabs, const int* __restrict__ fwd) {
   constexpr int TP = TS + 8;      // row stride of the staged panel blocks (as in front_step)
   constexpr int kFactorLds = DENSE ? PB * LP + PB * (PB + 1) / 2 : PB * PB + 2 * PB * LP;      // D | Lo (packed)  or  Lc | D | Lo
   __shared__ __attribute__((aligned(32))) double sh[2 * PB * TP + kFactorLds];
-  __shared__ int rowI[2][TS], rowJ[2][TS], piv[2][PB];
+  // gather: the inverse maps of the tile's rows / columns and of the pivot columns, per child slot.  PRE has no maps (B0, B1,
+  // inv0, inv1, cld and piv are unused there and compile away: 768 B less LDS); row 0 of rowI / rowJ is kept in both
+  // variants because the producer parks its forward-map entries there
+  __shared__ int rowI[PRE ? 1 : 2][TS], rowJ[PRE ? 1 : 2][TS], piv[PRE ? 1 : 2][PRE ? 1 : PB];
   double* ATI = sh;
   double* ATJ = sh + PB * TP;
   double* Lc = sh + 2 * PB * TP;                       // (not DENSE) the factor in quad order
@@ -1051,19 +1095,28 @@ __device__ __forceinline__ void front_single_body(
   }
   const bool rhs_tile = (nf >= r0 && nf < r0 + TS);      // this tile holds the right-hand-side row
   const int prm = (rhs_tile && tid < ns) ? perm[t.first + tid] : -1;
-  // index maps of the tile's rows, columns and of the pivot columns (parent front index -> child boundary index)
-  for (int idx = tid; idx < 2 * (2 * TS + PB); idx += TB) {
-    const int s = idx / (2 * TS + PB), q = idx % (2 * TS + PB);
-    const int* __restrict__ iv = s ? inv1 : inv0;
-    if (q < TS) rowI[s][q] = (has[s] && r0 + q <= nf) ? iv[r0 + q] : -1;
-    else if (q < 2 * TS) rowJ[s][q - TS] = (has[s] && c0 + q - TS <= nf) ? iv[c0 + q - TS] : -1;
-    else piv[s][q - 2 * TS] = (has[s] && q - 2 * TS < ns) ? iv[q - 2 * TS] : -1;
+  // producer: the forward-map entries of the tile's rows and columns (front boundary index -> parent front index),
+  // requested now and parked in rowI[0] / rowJ[0] once the gather (which owns them until then) is done
+  const bool producer = t.eoff >= 0;      // workgroup-uniform
+  int fw = 0;
+  if (producer && tid < 2 * TS) {
+    const int g = ((tid < TS) ? r0 : c0 - TS) + tid;      // front row / column
+    fw = (g <= nf) ? fwd[t.fofs + g - ns] : 0;
   }
+  // index maps of the tile's rows, columns and of the pivot columns (parent front index -> child boundary index)
+  if (!PRE)
+    for (int idx = tid; idx < 2 * (2 * TS + PB); idx += TB) {
+      const int s = idx / (2 * TS + PB), q = idx % (2 * TS + PB);
+      const int* __restrict__ iv = s ? inv1 : inv0;
+      if (q < TS) rowI[s][q] = (has[s] && r0 + q <= nf) ? iv[r0 + q] : -1;
+      else if (q < 2 * TS) rowJ[s][q - TS] = (has[s] && c0 + q - TS <= nf) ? iv[c0 + q - TS] : -1;
+      else piv[s][q - 2 * TS] = (has[s] && q - 2 * TS < ns) ? iv[q - 2 * TS] : -1;
+    }
   double aval[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) aval[u] = vals[asrc[u]];
   const double bval = (prm >= 0) ? b[prm] : 0.0;
-  __syncthreads();
+  if (!PRE) __syncthreads();
   // gather (every load issued before it is consumed, clamped to a valid address when the entry has no contribution)
   auto child = [&](int a0, int q0, int a1, int q1) {
     const bool ok0 = a0 >= 0 && q0 >= 0, ok1 = a1 >= 0 && q1 >= 0;
@@ -1071,16 +1124,53 @@ __device__ __forceinline__ void front_single_body(
     const double x1 = B1[ok1 ? (long long)cld[1] * q1 + a1 : 0];
     return (ok0 ? x0 : 0.0) + (ok1 ? x1 : 0.0);
   };
+  // (PRE) entry (i, j) of the front as slab0 + slab1; an absent child contributes the constant 0.0 (-0.0 + 0.0 = +0.0)
+  const double* __restrict__ E0 = slabs_ro + (PRE ? t.soff[0] : 0);
+  const double* __restrict__ E1 = slabs_ro + (PRE ? t.soff[1] : 0);
+  auto slab = [&](bool in, int i, int j) {
+    const int pos = in ? ld * j + i : 0;      // a slab has ld * nf < 2^31 entries (build() bounds the front): base + 32-bit offset
+    const double x0 = has[0] ? E0[pos] : 0.0, x1 = has[1] ? E1[pos] : 0.0;
+    return in ? x0 + x1 : 0.0;
+  };
   double c[4][4];
+  // (PRE && DENSE: the C tile is requested after the substitution instead -- with three workgroups per CU, 168 VGPRs, its
+  // 32 registers in flight across the factor and the substitution spilled; these launches are bound by how many
+  // workgroups a CU holds, not by one workgroup's latency)
+  if (!(PRE && DENSE)) {
 #pragma unroll
-  for (int bj = 0; bj < 4; ++bj)
+    for (int bj = 0; bj < 4; ++bj)
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int r = 16 * w + li, cc = 16 * bj + lk + 4 * reg, i = r0 + r, j = c0 + cc;
-      const bool in = (i <= nf && j < nf && i >= j);
-      c[bj][reg] = in ? child(rowI[0][r], rowJ[0][cc], rowI[1][r], rowJ[1][cc]) : 0.0;
+      for (int reg = 0; reg < 4; ++reg) {
+        const int r = 16 * w + li, cc = 16 * bj + lk + 4 * reg, i = r0 + r, j = c0 + cc;
+        const bool in = (i <= nf && j < nf && i >= j);
+        if (PRE) c[bj][reg] = slab(in, i, j);
+        else c[bj][reg] = in ? child(rowI[0][r], rowJ[0][cc], rowI[1][r], rowJ[1][cc]) : 0.0;
+      }
+  }
+  if (PRE) {
+    const int r = tid % TS, qg = tid / TS;      // 64 rows x 4 groups of 8 pivot columns
+    double vi[8], vj[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int q = qg * 8 + u;
+      vi[u] = vj[u] = 0.0;
+      if (!NARROW || qg == 0) {      // wave-uniform
+        vi[u] = slab(q < ns && r0 + r <= nf, r0 + r, q);
+        if (!diag) vj[u] = slab(q < ns && c0 + r <= nf, c0 + r, q);
+      }
     }
-  {
+    const int i = tid % PB, jg = tid / PB;      // pivot block: 32 rows x 8 groups of 4 columns
+    double vd[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) vd[u] = slab(jg * 4 + u <= i && i < ns, i, jg * 4 + u);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      ATI[(qg * 8 + u) * TP + r] = vi[u];
+      if (!diag) ATJ[(qg * 8 + u) * TP + r] = vj[u];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) D[i * LP + jg * 4 + u] = vd[u];
+  } else {
     const int r = tid % TS, qg = tid / TS;      // 64 rows x 4 groups of 8 pivot columns
     double vi[8], vj[8];
 #pragma unroll
@@ -1106,6 +1196,7 @@ __device__ __forceinline__ void front_single_body(
   }
   __syncthreads();
   STAMP(1);
+  if (producer && tid < 2 * TS) (tid < TS ? rowI[0] : rowJ[0] - TS)[tid] = fw;      // read behind several barriers
   // assembled entries (all in pivot columns) and right-hand side of the pieces this tile holds; the first batch is in
   // registers already
   auto add_entry = [&](int pos, double v) {
@@ -1152,6 +1243,15 @@ __device__ __forceinline__ void front_single_body(
     }
   }
   STAMP(3);
+  if (PRE && DENSE) {
+#pragma unroll
+    for (int bj = 0; bj < 4; ++bj)
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int i = r0 + 16 * w + li, j = c0 + 16 * bj + lk + 4 * reg;
+        c[bj][reg] = slab(i <= nf && j < nf && i >= j, i, j);
+      }
+  }
   // rank-32 (rank-8 when NARROW) update on the matrix cores, operand and result layout as in front_step
   typedef double v4f64 __attribute__((ext_vector_type(4)));
   const double* LI = ATI + 16 * w + li + lk * TP;
@@ -1166,30 +1266,40 @@ __device__ __forceinline__ void front_single_body(
     for (int bj = 0; bj < 4; ++bj)
       acc[bj] = __builtin_amdgcn_mfma_f64_16x16x4f64(LJ[4 * ks * TP + 16 * bj], bv, acc[bj], 0, 0, 0);
   }
+  double* E = slabs + (producer ? t.eoff : 0);
+  const int* fwJ = rowJ[0];
+  const int fi = producer ? rowI[0][16 * w + li] : 0;
 #pragma unroll
   for (int bj = 0; bj < 4; ++bj)
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) {
       const int i = r0 + 16 * w + li, j = c0 + 16 * bj + lk + 4 * reg;
-      if (i <= nf && j < nf && i >= j) F[(long long)ld * j + i] = acc[bj][reg];
+      if (i <= nf && j < nf && i >= j) {
+        if (producer) E[(long long)t.pld * fwJ[16 * bj + lk + 4 * reg] + fi] = acc[bj][reg];
+        else F[(long long)ld * j + i] = acc[bj][reg];
+      }
     }
   STAMP(7);
 }
 
-template <bool NARROW>
+template <bool NARROW, bool PRE>
 __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(2, 2))) void front_single_kernel(
     const SingleTile* __restrict__ tiles, const int* __restrict__ pinv, const int* __restrict__ asm_src,
     const int* __restrict__ asm_pos, const double* __restrict__ vals, const int* __restrict__ perm, const double* __restrict__ b,
-    const double* __restrict__ fronts_ro, double* fronts, double* linv, int* fail, long long* prof) {
-  front_single_body<NARROW, false>(tiles, pinv, asm_src, asm_pos, vals, perm, b, fronts_ro, fronts, linv, fail, prof);
+    const double* __restrict__ fronts_ro, double* fronts, double* linv, int* fail, long long* prof,
+    const double* __restrict__ slabs_ro, double* slabs, const int* __restrict__ fwd) {
+  front_single_body<NARROW, false, PRE>(tiles, pinv, asm_src, asm_pos, vals, perm, b, fronts_ro, fronts, linv, fail, prof, slabs_ro,
+                                        slabs, fwd);
 }
 
-template <bool NARROW>
+template <bool NARROW, bool PRE>
 __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(3, 3))) void front_single_dense_kernel(
     const SingleTile* __restrict__ tiles, const int* __restrict__ pinv, const int* __restrict__ asm_src,
     const int* __restrict__ asm_pos, const double* __restrict__ vals, const int* __restrict__ perm, const double* __restrict__ b,
-    const double* __restrict__ fronts_ro, double* fronts, double* linv, int* fail, long long* prof) {
-  front_single_body<NARROW, true>(tiles, pinv, asm_src, asm_pos, vals, perm, b, fronts_ro, fronts, linv, fail, prof);
+    const double* __restrict__ fronts_ro, double* fronts, double* linv, int* fail, long long* prof,
+    const double* __restrict__ slabs_ro, double* slabs, const int* __restrict__ fwd) {
+  front_single_body<NARROW, true, PRE>(tiles, pinv, asm_src, asm_pos, vals, perm, b, fronts_ro, fronts, linv, fail, prof, slabs_ro,
+                                       slabs, fwd);
 }
 
 // Leaf heights (no children) whose fronts fit LDS and whose trailing matrix after the first panel is one 64x64
@@ -1200,12 +1310,16 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 __global__ __launch_bounds__(TB, 4) void front_leaf_kernel(
     const GNode* __restrict__ nodes, const int* __restrict__ list, const int* __restrict__ asm_src,
     const int* __restrict__ asm_pos, const double* __restrict__ vals, const int* __restrict__ perm,
-    const double* __restrict__ b, double* fronts, double* linv, int* fail, long long* prof) {
+    const double* __restrict__ b, double* fronts, double* linv, int* fail, long long* prof, double* slabs,
+    const int* __restrict__ fwd) {
   extern __shared__ __attribute__((aligned(32))) double sm[];
+  __shared__ int fw[TS];      // producer: the front's forward map (at most 63 boundary rows and the right-hand-side row)
   STAMP(0);
   const GNode nd = nodes[blockIdx.x];      // per-launch copy in launch order: one descriptor round trip, not two
   (void)list;
   const int nf = nd.nf, ld = nf + 1, ns = nd.ns, tid = threadIdx.x;
+  const bool producer = nd.eoff >= 0;      // workgroup-uniform: the Schur complement goes to the parent's slab, in its order
+  if (producer && tid <= nf - ns && tid < TS) fw[tid] = fwd[nd.fofs + tid];      // read behind the panels' barriers
   constexpr int TP = TS + 8;      // row stride of the staged panel rows (as in front_step)
   __shared__ __attribute__((aligned(32))) double fixed[TP * PB + PB * (PB + 1) / 2];      // AT (also D) | Lo (packed)
   double* Fs = sm;                               // the front, (nf+1)-leading-dimension layout as in HBM
@@ -1277,9 +1391,17 @@ __global__ __launch_bounds__(TB, 4) void front_leaf_kernel(
   STAMP(2);
   // Schur complement + reduced right-hand side for the parent: boundary columns, rows down to nf
   const int nb = nf - ns;
-  for (int idx = tid; idx < (nb + 1) * nb; idx += TB) {
-    const int i = ns + idx % (nb + 1), j = ns + idx / (nb + 1);
-    if (i >= j) F[(long long)ld * j + i] = Fs[P(i, j)];
+  if (producer) {
+    double* E = slabs + nd.eoff;
+    for (int idx = tid; idx < (nb + 1) * nb; idx += TB) {
+      const int a = idx % (nb + 1), q = idx / (nb + 1);
+      if (a >= q) E[(long long)nd.pld * fw[q] + fw[a]] = Fs[P(ns + a, ns + q)];
+    }
+  } else {
+    for (int idx = tid; idx < (nb + 1) * nb; idx += TB) {
+      const int i = ns + idx % (nb + 1), j = ns + idx / (nb + 1);
+      if (i >= j) F[(long long)ld * j + i] = Fs[P(i, j)];
+    }
   }
   STAMP(7);
 }
@@ -1748,9 +1870,22 @@ const CholKnobs& GpuChol::knobs() {
     c.bwd_cut = num("MGB_CHOL_BWD_CUT", 2);
     c.bwd_fused_nf = num("MGB_CHOL_BWD_FUSED_NF", 384);
     c.bwd_fused_threads = num("MGB_CHOL_BWD_FUSED_THREADS", 512);
+    c.premap = num("MGB_CHOL_PREMAP", 1);      // front_start consumers measured no gain inside a Newton step
+    c.premap_tiles = num("MGB_CHOL_PREMAP_TILES", 400);      // fem2d L=7: the 512-tile launch gains 0.4 us for a fifth of the slabs
     return c;
   }();
   return k;
+}
+
+PremapKnobs GpuChol::premap_knobs() {
+  const CholKnobs& kn = knobs();
+  PremapKnobs pk;
+  pk.leaf = kn.leaf;
+  pk.single = kn.single;
+  pk.start_pivot = kn.start_pivot;
+  pk.mode = kn.premap;
+  pk.tiles = kn.premap_tiles;
+  return pk;
 }
 
 namespace {
@@ -1790,9 +1925,13 @@ int append_tiles(std::vector<StepTile>& out, const GNode& g, int t, int p, int k
   return (int)(out.size() - n0);
 }
 
-SingleTile single_tile(const std::vector<GNode>& nodes, const StepTile& s) {
+SingleTile single_tile(const std::vector<GNode>& nodes, const StepTile& s, const PremapPlan& pm) {
   const GNode& g = nodes[s.pad];
   SingleTile u{};
+  u.pld = g.pld;
+  u.fofs = g.fofs;
+  u.eoff = g.eoff;
+  for (int sI = 0; sI < 2; ++sI) u.soff[sI] = std::max(0LL, pm.soff[2 * (size_t)s.pad + sI]);
   u.off = g.off;
   u.loff = g.loff;
   u.nf = g.nf;
@@ -1851,15 +1990,30 @@ int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::v
         start_bytes += 0.5 * cnb * cnb * 8.0;     // child entry read (the parent entry write is counted above)
       }
     }
-    // leaf heights with small fronts: the whole front in one workgroup (front_leaf_kernel).  nf <= 95 alone is not enough:
-    // a narrow leaf with a wide boundary (3-D trees under a small MGB_LEAF: ns = 16, nf = 88) has more trailing rows than
-    // the kernel's one tile, and the rows past it were never updated
-    const bool leaf = kn.leaf && max_nf <= 95 && max_ns <= 2 * PB && childless && all_pivots && one_tile;
-    // single-panel heights with children: one dependency-free launch (front_single_kernel)
-    const bool single = kn.single && max_ns <= PB && !childless && all_pivots;
+    // front_leaf (the whole front in one workgroup), front_single (single-panel heights with children: one dependency-free
+    // launch) or front_start + panel launches: HeightShape::kind, shared with the pre-mapping rule
+    HeightShape shape;
+    shape.max_ns = max_ns;
+    shape.max_nf = max_nf;
+    shape.childless = childless;
+    shape.all_pivots = all_pivots;
+    shape.one_tile = one_tile;
+    const int hkind = shape.kind(premap_knobs());
+    const bool leaf = hkind == PH_LEAF, single = hkind == PH_SINGLE;
+    // pre-mapped child contributions (unsplit factorisations; the plan covers the whole tree, height by height)
+    const bool planned = &heights == premap_heights_ && premap_.any();      // (no slabs: nothing to cross-check or flag)
+    if (planned && (premap_.hkind[hh] != hkind)) throw InternalError("gpuchol: pre-map plan disagrees with the schedule");
+    const bool consumer = planned && premap_.hconsumer[hh];
+    int nprod = 0;
+    if (planned)
+      for (int t : mine) nprod += premap_.producer[t];
+    auto check_wg = [&](int cnt) {
+      if (planned && premap_.hwg[hh] != cnt) throw InternalError("gpuchol: pre-map plan disagrees with the launch size");
+    };
     if (leaf) {
       const size_t lds = ((size_t)(max_nf + 1) * max_nf - (size_t)max_nf * (max_nf - 1) / 2) * sizeof(double);
-      chain_.push_back({Kind::Leaf, nofs, ncnt, TB, lds, 0, 0, false, KC_CHOL_SINGLE, start_bytes});
+      check_wg(ncnt);
+      chain_.push_back({Kind::Leaf, nofs, ncnt, TB, lds, 0, 0, false, KC_CHOL_SINGLE, start_bytes, false, nprod});
     } else if (!single) {
       const int ofs = (int)jobs.starts.size();
       if (kn.start_pivot)      // dedicated pivot jobs first: they are what the first panel launch waits for
@@ -1870,7 +2024,9 @@ int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::v
             jobs.starts.push_back(pj);
           }
       for (int t : mine) jobs.starts.insert(jobs.starts.end(), sjobs[t].begin(), sjobs[t].end());
-      chain_.push_back({Kind::Start, ofs, (int)jobs.starts.size() - ofs, TB, 0, 0, 0, false, KC_CHOL_START, start_bytes});
+      check_wg((int)jobs.starts.size() - ofs);
+      if (nprod) throw InternalError("gpuchol: a multi-panel front cannot store pre-mapped");
+      chain_.push_back({Kind::Start, ofs, (int)jobs.starts.size() - ofs, TB, 0, 0, 0, false, KC_CHOL_START, start_bytes, consumer, 0});
     }
     // panel launches, pivot-owning workgroups first: they are the critical path of the next launch
     const int npanel = leaf ? 0 : (max_ns + PB - 1) / PB;
@@ -1935,10 +2091,11 @@ int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::v
       const int cnt = (int)jobs.tiles.size() - ofs;
       if (single) {      // same tiles, self-contained descriptors
         const int sofs = (int)jobs.singles.size();
-        for (int q = ofs; q < ofs + cnt; ++q) jobs.singles.push_back(single_tile(nodes, jobs.tiles[q]));
+        for (int q = ofs; q < ofs + cnt; ++q) jobs.singles.push_back(single_tile(nodes, jobs.tiles[q], premap_));
+        check_wg(cnt);
         const bool narrow = max_ns <= 8, dense = cnt > kn.dense_tiles;
         const Kind k = dense ? (narrow ? Kind::SingleDenseNarrow : Kind::SingleDense) : (narrow ? Kind::SingleNarrow : Kind::Single);
-        chain_.push_back({k, sofs, cnt, TB, 0, 0, 0, false, KC_CHOL_SINGLE, start_bytes + bytes});
+        chain_.push_back({k, sofs, cnt, TB, 0, 0, 0, false, KC_CHOL_SINGLE, start_bytes + bytes, consumer, nprod});
       } else {
         chain_.push_back({pair ? Kind::Step2 : Kind::Step, ofs, cnt, TB, pair ? (size_t)kStep2Lds : 0, p, npiv, false, KC_CHOL_STEP, bytes});
       }
@@ -1984,6 +2141,14 @@ void GpuChol::schedule_info(int cap, int* nlaunch, int* kind, int* workgroups) c
   }
 }
 
+void GpuChol::premap_info(int cap, int* consumer, int* producers) const {
+  const int m = std::min(std::max(cap, 0), (int)chain_.size());
+  for (int i = 0; i < m; ++i) {
+    if (consumer) consumer[i] = chain_[i].premap ? 1 : 0;
+    if (producers) producers[i] = chain_[i].nproducers;
+  }
+}
+
 void GpuChol::unknown_columns(const MfChol& sym, int* node, int* col) {
   for (int t = 0; t < (int)sym.nodes_.size(); ++t)
     for (int k = 0; k < sym.nodes_[t].ns; ++k) {
@@ -2002,12 +2167,33 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
   nnodes_ = (int)sym.nodes_.size();
   flops_ = sym.flops_;
   std::vector<GNode> nodes(nnodes_);
-  std::vector<int> bdry_all, ea_all, pinv, height(nnodes_, 0);
+  std::vector<int> bdry_all, height(nnodes_, 0);
+  {      // pre-mapped child contributions: the tables first, every descriptor below carries its part of them
+    std::vector<int> ns(nnodes_), nf(nnodes_), parent(nnodes_), c0(nnodes_, -1), c1(nnodes_, -1);
+    std::vector<const std::vector<int>*> ea(nnodes_);
+    for (int t = 0; t < nnodes_; ++t) {
+      const auto& nd = sym.nodes_[t];
+      if (nd.children.size() > 2) throw InternalError("gpuchol: elimination tree is not binary");
+      ns[t] = nd.ns;
+      nf[t] = nd.nf();
+      parent[t] = nd.parent;
+      if (nd.children.size() > 0) c0[t] = nd.children[0];
+      if (nd.children.size() > 1) c1[t] = nd.children[1];
+      ea[t] = &nd.ea;
+    }
+    PremapKnobs pk = premap_knobs();
+    if (part_.split()) pk.mode = 0;      // schur_pack_kernel reads the subtree roots' Schur complements from the fronts
+    premap_ = plan_premap(ns, nf, parent, c0, c1, ea, pk);
+  }
+  const std::vector<int>& pinv = premap_.pinv;
   long long off = 0, loff = 0;
   max_nf_ = 0;
   for (int t = 0; t < nnodes_; ++t) {
     const auto& nd = sym.nodes_[t];
     GNode& g = nodes[t];
+    g.pld = premap_.pld[t];
+    g.fofs = premap_.fofs[t];
+    g.eoff = premap_.eoff[t];
     g.off = off;
     g.loff = loff;
     loff += (long long)((nd.ns + PB - 1) / PB) * 2 * PB * PB;
@@ -2018,38 +2204,18 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
     g.bofs = (int)bdry_all.size();
     g.child[0] = nd.children.size() > 0 ? nd.children[0] : -1;
     g.child[1] = nd.children.size() > 1 ? nd.children[1] : -1;
-    g.iofs = -1;
-    if (nd.children.size() > 2) throw InternalError("gpuchol: elimination tree is not binary");
+    g.iofs = premap_.iofs[t];
     bdry_all.insert(bdry_all.end(), nd.bdry.begin(), nd.bdry.end());
-    ea_all.insert(ea_all.end(), nd.ea.begin(), nd.ea.end());
     if (nd.parent >= 0 && nd.ea.size() != nd.bdry.size()) throw InternalError("gpuchol: ea/bdry size mismatch");
     if (nd.parent >= 0 && !std::is_sorted(nd.ea.begin(), nd.ea.end())) throw InternalError("gpuchol: ea not ascending");
-    if (nd.parent < 0) ea_all.resize(bdry_all.size(), 0);
     if ((long long)(g.nf + 1) * (g.nf + 1) > 2000000000LL) throw ArgError("gpuchol: front too large");
     off += (long long)(g.nf + 1) * (g.nf + 1);
     max_nf_ = std::max(max_nf_, g.nf);
     for (int c : nd.children) height[t] = std::max(height[t], height[c] + 1);   // postorder: children first
   }
   total_front_ = off;
-  // per parent and child slot: parent front row -> child boundary row (the child's right-hand-side row for nf)
-  for (int t = 0; t < nnodes_; ++t) {
-    GNode& g = nodes[t];
-    if (g.child[0] < 0 && g.child[1] < 0) continue;
-    g.iofs = (int)pinv.size();
-    pinv.resize(pinv.size() + 2 * (size_t)(g.nf + 1), -1);
-    for (int s = 0; s < 2; ++s) {
-      const int c = g.child[s];
-      if (c < 0) continue;
-      int* iv = pinv.data() + g.iofs + (size_t)s * (g.nf + 1);
-      const int cnb = nodes[c].nf - nodes[c].ns;
-      const int* ea = ea_all.data() + nodes[c].bofs;
-      for (int a = 0; a < cnb; ++a) {
-        if (ea[a] < 0 || ea[a] >= g.nf || iv[ea[a]] != -1) throw InternalError("gpuchol: bad extend-add map");
-        iv[ea[a]] = a;
-      }
-      iv[g.nf] = cnb;
-    }
-  }
+  // (the inverse maps -- per parent and child slot: parent front row -> child boundary row, the child's right-hand-side
+  // row for nf -- come with the plan: premap_.pinv / iofs)
   nheights_ = nnodes_ ? *std::max_element(height.begin(), height.end()) + 1 : 0;
   // assembly map, per node sorted by the front_start job (32-column chunk, 256-row block counted from the chunk's
   // first row) that owns the destination; positions in the (nf+1)-leading-dimension layout
@@ -2090,6 +2256,7 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
             j.boff[sI] = c.off + (long long)j.cld[sI] * c.ns + c.ns;
           }
         }
+        for (int sI = 0; sI < 2; ++sI) j.soff[sI] = std::max(0LL, premap_.soff[2 * (size_t)t + sI]);
         j.a0 = (int)asrc.size();
         while (q < m && key(ord[q]) == (long long)ch * 65536 + rb) {
           const int pos = sym.a_pos_[t][ord[q]], col = pos / nf, row = pos % nf;
@@ -2139,8 +2306,12 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
         if (fused_.bofs[t] != nodes[t].bofs || fused_.height[t] != height[t]) throw InternalError("gpuchol: fused plan disagrees with the front layout");
     }
   }
+  for (int t = 0; t < nnodes_; ++t)
+    if (premap_.height[t] != height[t]) throw InternalError("gpuchol: pre-map plan disagrees with the tree heights");
+  premap_heights_ = part_.split() ? nullptr : &own;
   own_bwd_ = schedule(own, nodes, sjobs, sym, jobs);
   fused_heights_ = nullptr;
+  premap_heights_ = nullptr;
   top_fwd_ = (int)chain_.size();
   if (part_.split()) schedule(top, nodes, sjobs, sym, jobs);
   if ((size_t)(max_nf_ + RT + PB) * 8 > 150 * 1024) throw ArgError("gpuchol: front exceeds the LDS budget of the sweeps");
@@ -2148,6 +2319,7 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
   d_perm_ = upload(sym.perm_);
   d_bdry_ = upload(bdry_all);
   d_pinv_ = upload(pinv);
+  d_fwd_ = upload(premap_.fwd);
   d_asm_src_ = upload(asrc);
   d_asm_pos_ = upload(apos);
   d_lists_ = upload(jobs.lists);
@@ -2214,6 +2386,11 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
   allocs_.push_back(d_fronts_);
   // the mirrored-L half of every front is written before it is read, but never leave it uninitialised
   ck(hipMemset(d_fronts_, 0, std::max<long long>(total_front_, 1) * sizeof(double)), "memset fronts");
+  // the contribution slabs are zeroed ONCE, here, outside any stream capture: afterwards only the producers write them,
+  // always at the same positions, so every uncovered entry stays +0.0 for the life of the object
+  ck(hipMalloc((void**)&d_slabs_, std::max<long long>(premap_.slab_doubles, 1) * sizeof(double)), "hipMalloc slabs");
+  allocs_.push_back(d_slabs_);
+  ck(hipMemset(d_slabs_, 0, std::max<long long>(premap_.slab_doubles, 1) * sizeof(double)), "memset slabs");
   ck(hipMalloc((void**)&d_linv_, std::max<long long>(loff, 1) * sizeof(double)), "hipMalloc linv");
   allocs_.push_back(d_linv_);
   ck(hipMalloc((void**)&d_rect_, std::max(n_, 1) * sizeof(double)), "hipMalloc rect");
@@ -2302,20 +2479,23 @@ void GpuChol::run(hipStream_t st, int begin, int end, const double* d_vals, cons
     switch (L.kind) {
       case Kind::Leaf:
         hipLaunchKernelGGL(front_leaf_kernel, grid, block, L.lds, st, d_hnodes_ + L.ofs, d_lists_ + L.ofs, d_asm_src_, d_asm_pos_,
-                           d_vals, d_perm_, d_b, d_fronts_, d_linv_, d_fail_, prof);
+                           d_vals, d_perm_, d_b, d_fronts_, d_linv_, d_fail_, prof, d_slabs_, d_fwd_);
         break;
       case Kind::Single:
       case Kind::SingleNarrow:
       case Kind::SingleDense:
       case Kind::SingleDenseNarrow:
-        hipLaunchKernelGGL(dense ? (narrow ? front_single_dense_kernel<true> : front_single_dense_kernel<false>)
-                                 : (narrow ? front_single_kernel<true> : front_single_kernel<false>),
+        hipLaunchKernelGGL(L.premap ? (dense ? (narrow ? front_single_dense_kernel<true, true> : front_single_dense_kernel<false, true>)
+                                             : (narrow ? front_single_kernel<true, true> : front_single_kernel<false, true>))
+                                    : (dense ? (narrow ? front_single_dense_kernel<true, false> : front_single_dense_kernel<false, false>)
+                                             : (narrow ? front_single_kernel<true, false> : front_single_kernel<false, false>)),
                            grid, block, L.lds, st, d_singles_ + L.ofs, d_pinv_, d_asm_src_, d_asm_pos_, d_vals, d_perm_, d_b, d_fronts_,
-                           d_fronts_, d_linv_, d_fail_, prof);
+                           d_fronts_, d_linv_, d_fail_, prof, d_slabs_, d_slabs_, d_fwd_);
         break;
       case Kind::Start:
-        hipLaunchKernelGGL(front_start_kernel, grid, block, L.lds, st, d_nodes_, d_start_ + L.ofs, d_pinv_, d_asm_src_, d_asm_pos_,
-                           d_vals, d_perm_, d_b, d_fronts_, d_fronts_, d_linv_, d_fail_, prof, knobs().start_pivot ? 1 : 0);
+        hipLaunchKernelGGL(L.premap ? front_start_kernel<true> : front_start_kernel<false>, grid, block, L.lds, st, d_nodes_,
+                           d_start_ + L.ofs, d_pinv_, d_asm_src_, d_asm_pos_, d_vals, d_perm_, d_b, d_fronts_, d_fronts_, d_linv_,
+                           d_fail_, prof, knobs().start_pivot ? 1 : 0, d_slabs_);
         break;
       case Kind::Step:
       case Kind::Step2:

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "bwd_fused.hpp"
+#include "chol_premap.hpp"
 #include "mfchol.hpp"
 
 namespace mgb {
@@ -51,6 +52,9 @@ struct GNode {
   int child[2];       // -1 if absent
   int iofs;           // offset of the two (nf+1)-long inverse extend-add maps (-1: leaf)
   int a0, a1;         // range of this node's entries in the assembly list
+  int pld;            // pre-mapped store (chol_premap.hpp): the parent's leading dimension,
+  int fofs;           // ... where this node's forward map begins,
+  long long eoff;     // ... and the offset of its slab in the parent (-1: the Schur complement stays in the front)
 };
 
 struct StartJob {     // one workgroup of front_start: 32 columns x 256 rows (counted from the chunk's first row) of one front,
@@ -61,6 +65,7 @@ struct StartJob {     // one workgroup of front_start: 32 columns x 256 rows (co
   int nf, ns, iofs, first;
   int node, chunk, rb;
   int a0, a1;         // range of the (column-sorted) assembly list
+  long long soff[2];  // pre-mapped consumer launches: the front's contribution slab per child slot (unused slot: any valid offset)
 };
 
 struct StepTile {     // one workgroup of front_step: a 64x64 tile of the trailing matrix of one front
@@ -77,6 +82,9 @@ struct SingleTile {   // one workgroup of front_single: a tile of a single-panel
   int cld[2];               // child leading dimensions (0 = no child)
   int nf, ns, iofs, a0, a1, first;
   short ti, tj;
+  int pld, fofs;      // pre-mapped store: the parent's leading dimension, where the front's forward map begins
+  long long eoff;     // ... and the offset of its slab in the parent (-1: the Schur complement stays in the front)
+  long long soff[2];  // pre-mapped consumer launches: the front's contribution slab per child slot
 };
 
 struct RectJob {      // one workgroup of backward_rect: 64 own columns of one front
@@ -100,6 +108,9 @@ struct CholKnobs {
                        // up to two heights until they are at most 256, one per CU; trees that need more keep the per-height launches)
   int bwd_fused_nf;    // MGB_CHOL_BWD_FUSED_NF (384): heights with a larger front keep their own backward launches; 0: no limit
   int bwd_fused_threads;  // MGB_CHOL_BWD_FUSED_THREADS (512): workgroup size of the fused backward launch (a power of two, 64 .. 512)
+  int premap;          // MGB_CHOL_PREMAP (1): children store their Schur complements in parent order (chol_premap.hpp) for
+                       // 1: front_single consumers, 2: front_start consumers too; 0: every launch gathers through the index maps
+  int premap_tiles;    // MGB_CHOL_PREMAP_TILES (400): largest launch, in workgroups, that reads pre-mapped slabs
 };
 
 class GpuChol {
@@ -146,6 +157,11 @@ class GpuChol {
   // the chain in launch order (nullable outputs): *nlaunch launches, the Kind code (enum order) and the workgroup count of
   // the first min(cap, *nlaunch) of them.  Read-only.
   void schedule_info(int cap, int* nlaunch, int* kind, int* workgroups) const;
+  // pre-mapped child contributions, per launch of the first min(cap, launches) (nullable outputs): 1 if the launch reads
+  // its fronts' contribution slabs instead of gathering, and how many of its fronts store their Schur complement into one
+  void premap_info(int cap, int* consumer, int* producers) const;
+  double slab_bytes() const { return (double)premap_.slab_doubles * 8; }
+  static PremapKnobs premap_knobs();      // the rule's knobs as this process reads them
   // per unknown (original ordering, nullable outputs): its tree node (postorder) and its column among that node's own columns
   static void unknown_columns(const MfChol& sym, int* node, int* col);
 
@@ -189,6 +205,10 @@ class GpuChol {
   double* d_fronts_ = nullptr;
   double* d_rect_ = nullptr;      // L21' x_bdry of the split backward sweep (n entries, new ordering)
   double* d_linv_ = nullptr;      // 32x32 diagonal (pivot) blocks of L
+  double* d_slabs_ = nullptr;     // pre-mapped child contributions: zeroed once by build(), written by the producers only
+  int* d_fwd_ = nullptr;          // ... the forward maps (child boundary row -> parent front row)
+  PremapPlan premap_;             // ... their host tables (all flags off for split factorisations)
+  const std::vector<std::vector<int>>* premap_heights_ = nullptr;     // (during build) the height lists that plan covers
   double* d_y_ = nullptr;         // solution in the new ordering
   int* d_fail_ = nullptr;
   long long* d_prof_ = nullptr;   // MGB_CHOL_PROF=1: phase stamps of workgroup 0 of every launch but backward_rect
@@ -224,6 +244,8 @@ class GpuChol {
     bool rect;          // Bwd*: the rectangular part ran in the BwdRect launch before
     int timer;          // KernelTimer class
     double bytes;       // algorithmic bytes
+    bool premap = false;     // Single*, Start: reads the contribution slabs (no gather)
+    int nproducers = 0;      // Leaf, Single*: fronts of the launch that store into a slab
   };
   // own forward | own backward | (split) top forward | top backward, in launch order; a launch's position is its profile slot.
   // Own: this rank's subtree when split, else everything; top: the replicated separators above the subtrees.

@@ -78,6 +78,19 @@ class MfChol {
     ns.clear(); first.clear(); parent.clear(); bdry.clear();
     for (const Node& nd : nodes_) { ns.push_back(nd.ns); first.push_back(nd.first); parent.push_back(nd.parent); bdry.push_back(&nd.bdry); }
   }
+  // what the pre-mapped child contributions of the device factorisation need per node: own size, front size, parent, the
+  // two child slots (-1: absent) and the extend-add list (position of boundary entry i in the parent's front; the pointers
+  // stay valid as long as this object)
+  void premap_tables(std::vector<int>& ns, std::vector<int>& nf, std::vector<int>& parent, std::vector<int>& child0,
+                     std::vector<int>& child1, std::vector<const std::vector<int>*>& ea) const {
+    tree(ns, nf, parent);
+    child0.clear(); child1.clear(); ea.clear();
+    for (const Node& nd : nodes_) {
+      child0.push_back(nd.children.size() > 0 ? nd.children[0] : -1);
+      child1.push_back(nd.children.size() > 1 ? nd.children[1] : -1);
+      ea.push_back(&nd.ea);
+    }
+  }
 
  private:
   friend class GpuChol;   // the device factorisation reuses this symbolic structure verbatim
