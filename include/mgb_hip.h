@@ -336,6 +336,12 @@ int mgb_amg_sol_pcg(mgb_amg a, long long* counts4, double* time_s);
 int mgb_amg_time_mg_kernels(mgb_amg a, int level, int reps, int nrot, double* ms6, double* bytes6, double* alg6);
 /* coarsest level of the V-cycle whose top is level `top` (the largest level with at most 128 unknowns; dense inverse there) */
 int mgb_amg_mg_info(mgb_amg a, int top, int* coarsest);
+/* read-only description of the element operator of `level` (the matrix-free H v and the element-slab assembly), built first if
+ * it is not yet.  out[13]: [0] valid (0: the operators are not element-local, or an element does not fit into LDS; the rest is
+ * zero then), [1] threads per element (8 .. 256: the kernel instantiation), [2] rows per element, [3] cmax, [4] nnz_max,
+ * [5] structure classes, [6] elements, [7] K, [8] nY, [9] 1 if the software-pipelined load path is taken, 0 for the plain one,
+ * [10] 1 if the element-slab assembly is valid, [11] workgroups of the apply launch, [12] passes of its busiest workgroup */
+int mgb_amg_elop_info(mgb_amg a, int level, int* out);
 
 /* ---- evaluation at arbitrary points (the step after mpi_to_native in the reference's workflow: README.md:42-50,
  * docs/src/guide.md:21-52 plot the solution; [UPSTREAM-UNVERIFIED] `interpolate`, the contract is this project's) --------- *

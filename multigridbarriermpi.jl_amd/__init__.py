@@ -1186,6 +1186,19 @@ class AMG:
         call("mgb_amg_mg_info", self.handle, self.L - 1 if top is None else int(top), C.byref(c0))
         return c0.value
 
+    ELOP_INFO = ("valid", "tpe", "rows_per_el", "cmax", "nnz_max", "ncls", "nel", "K", "nY", "pipelined", "elasm_valid", "grid",
+                 "passes_per_wg")
+
+    def elop_info(self, l):
+        """Read-only description of level l's element operator (mgb_amg_elop_info): the kernel instantiation `tpe`, the element
+        shape, which load path the apply kernel takes, whether the element-slab assembly is valid, and the launch shape."""
+        out = (C.c_int * len(self.ELOP_INFO))()
+        call("mgb_amg_elop_info", self.handle, int(l), out)
+        d = dict(zip(self.ELOP_INFO, (int(v) for v in out)))
+        for k in ("valid", "pipelined", "elasm_valid"):
+            d[k] = bool(d[k])
+        return d
+
     def solve(self, tol=None, t=0.1, kappa=10.0, maxit=10000, max_newton=0, verbose=0, schedule="fine",
               solver="gpu", stop_rule="fixed", centering="exact"):
         if schedule not in ("fine", "all"):

@@ -498,6 +498,10 @@ class Amg {
   void mg_prolong(int l, const double* xc_host, double* xf_host);      // level l -> l + 1
   void mg_restrict(int l, const double* rf_host, double* rc_host);     // level l + 1 -> l
   int mg_coarsest(int top);      // coarsest level of the V-cycle below `top`
+  // read-only description of level l's element operator (built through mg_ensure_elop if it is not yet), kElopInfo ints:
+  // valid, tpe, rows_per_el, cmax, nnz_max, ncls, nel, K, nY, pipelined, element assembly valid, grid, passes per workgroup
+  static constexpr int kElopInfo = 13;
+  void elop_info(int l, int* out);
   // x = H(s)^{-1} g by V-cycle-preconditioned CG at level l; returns false if it stopped without converging
   bool pcg_solve_linear(int l, const double* s_host, const double* g_host, double* x_host, int* iters, double* relres);
   const Csr& prolongation_host(int l);      // P_l as built on the host (tests)

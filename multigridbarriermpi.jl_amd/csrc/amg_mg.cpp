@@ -394,6 +394,20 @@ bool Amg::mg_ensure_elop(Level& lv) {
   return m.elop.view.valid();
 }
 
+void Amg::elop_info(int l, int* out) {
+  Level& lv = level(l);
+  hip_check(hipSetDevice(ctx_.device), "hipSetDevice");
+  std::fill(out, out + kElopInfo, 0);
+  if (!mg_ensure_elop(lv)) return;
+  const DevElOp& E = lv.mg->elop.view;
+  const int nY = P_.nY();
+  int grid = 0, passes = 0;
+  elop_launch_shape(E, &grid, &passes);
+  const int v[kElopInfo] = {1, E.tpe, E.rows_per_el, E.cmax, E.nnz_max, E.ncls, E.nel, E.K, nY,
+                            elop_pipelined(E.tpe, E.nnz_max, E.block * nY, E.cmax) ? 1 : 0, lv.elasm.view.valid() ? 1 : 0, grid, passes};
+  std::copy(v, v + kElopInfo, out);
+}
+
 void Amg::mg_ensure_assembled(Level& lv) {
   Level::Mg& m = mg_of(lv);
   if (m.assembled) return;

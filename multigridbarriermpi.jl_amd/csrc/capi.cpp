@@ -1079,6 +1079,12 @@ int mgb_amg_mg_info(mgb_amg a, int top, int* coarsest) {
     if (coarsest) *coarsest = a->amg->mg_coarsest(top);
   });
 }
+int mgb_amg_elop_info(mgb_amg a, int level, int* out) {
+  return guard([&] {
+    need(a && out && level >= 0 && level < a->amg->L(), "elop_info: bad arguments");
+    a->amg->elop_info(level, out);
+  });
+}
 int mgb_amg_set_stop_rule(mgb_amg a, int upstream) {
   return guard([&] {
     need(a, "null amg");

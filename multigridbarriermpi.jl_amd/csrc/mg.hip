@@ -38,8 +38,6 @@ struct YList {
 // diag != 0: E forms diag(B_e' Y_e B_e) instead.
 // Class table entry per nonzero (64 bit): bits 0-15 local nonzero index and 16-31 local row of the p-th entry in column-wise
 // order, bits 32-39 local column of the k-th entry in row-wise order.
-constexpr int kPre = 4;      // register prefetch depth per lane (values / table-free data of the NEXT pass); deeper elements take the plain path
-
 template <int TPE>
 __global__ __launch_bounds__(kBlock) void elop_apply_kernel(DevElOp E, int K, int nY, YList yl, const double* __restrict__ Y,
                                                              const double* __restrict__ v, const double* __restrict__ vmul,
@@ -72,7 +70,7 @@ __global__ __launch_bounds__(kBlock) void elop_apply_kernel(DevElOp E, int K, in
   // Software pipeline: the HBM-latency loads of pass n + 1 (nonzero values, Y, column ids, class, extent) are issued into
   // registers before the LDS-only phases of pass n and land in LDS at the top of pass n + 1; only the gather of vin (its column
   // ids are already in registers) and a class table that changed are fetched inside the pass.
-  const bool pipelined = (nzm + TPE - 1) / TPE <= kPre && (nYel + TPE - 1) / TPE <= kPre && (cmax + TPE - 1) / TPE <= kPre;
+  const bool pipelined = elop_pipelined(TPE, nzm, nYel, cmax);      // mg.hpp: kPre registers per lane hold an element's arrays
   double pv[kPre], py[kPre];
   int pcol[kPre], pc = 0, pk0 = 0, pnz = 1, pe = 0;      // stage B (next pass): values, Y, column ids
   int qc = 0, qk0 = 0, qnz = 1, qe = 0;                   // stage A (the pass after): class and extent, which stage B's addresses need
@@ -568,28 +566,44 @@ YList make_ylist(const BarrierParams& P) {
   return y;
 }
 
-void launch_elop_phase1(hipStream_t st, const DevElOp& E, const BarrierParams& P, const double* Y, const double* v, const double* vmul,
-                        const double* vscale, double* elbuf, int diag, const double* done) {
-  const int epb = kBlock / E.tpe;
-  const int npass = (E.nel + epb - 1) / epb;
-  const size_t lds = (size_t)epb * E.slot_doubles * sizeof(double);
-  const YList tab = make_ylist(P);
-  // persistent workgroups: as many as are resident on the device at once (occupancy query: LDS and registers), each walking
-  // its share of the passes with the next pass's loads in flight behind the current one's arithmetic
+// persistent workgroups: as many as are resident on the device at once (occupancy query: LDS and registers), each walking
+// its share of the passes with the next pass's loads in flight behind the current one's arithmetic
+template <int TPE>
+int elop_grid(const DevElOp& E) {
   static const int ncu = [] {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n > 0 ? n : 256;
   }();
-#define MGB_ELOP(T)                                                                                                            \
-  {                                                                                                                            \
-    int per_cu = 0;                                                                                                            \
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, elop_apply_kernel<T>, kBlock, lds) != hipSuccess || per_cu < 1)  \
-      per_cu = 2;                                                                                                              \
-    const int grid = std::max(1, std::min(npass, ncu * per_cu));                                                               \
-    hipLaunchKernelGGL(elop_apply_kernel<T>, dim3(grid), dim3(kBlock), lds, st, E, P.K, P.nY(), tab, Y, v, vmul, vscale, elbuf,  \
-                       diag, done);                                                                                            \
+  constexpr int epb = kBlock / TPE;
+  const int npass = (E.nel + epb - 1) / epb;
+  const size_t lds = (size_t)epb * E.slot_doubles * sizeof(double);
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, elop_apply_kernel<TPE>, kBlock, lds) != hipSuccess || per_cu < 1)
+    per_cu = 2;
+  return std::max(1, std::min(npass, ncu * per_cu));
+}
+
+int elop_grid_of(const DevElOp& E) {
+  switch (E.tpe) {
+    case 8: return elop_grid<8>(E);
+    case 16: return elop_grid<16>(E);
+    case 32: return elop_grid<32>(E);
+    case 64: return elop_grid<64>(E);
+    case 128: return elop_grid<128>(E);
+    default: return elop_grid<256>(E);
   }
+}
+
+void launch_elop_phase1(hipStream_t st, const DevElOp& E, const BarrierParams& P, const double* Y, const double* v, const double* vmul,
+                        const double* vscale, double* elbuf, int diag, const double* done) {
+  const int epb = kBlock / E.tpe;
+  const size_t lds = (size_t)epb * E.slot_doubles * sizeof(double);
+  const YList tab = make_ylist(P);
+  const int grid = elop_grid_of(E);
+#define MGB_ELOP(T)                                                                                                            \
+  hipLaunchKernelGGL(elop_apply_kernel<T>, dim3(grid), dim3(kBlock), lds, st, E, P.K, P.nY(), tab, Y, v, vmul, vscale, elbuf,    \
+                     diag, done)
   switch (E.tpe) {
     case 8: MGB_ELOP(8); break;
     case 16: MGB_ELOP(16); break;
@@ -602,6 +616,14 @@ void launch_elop_phase1(hipStream_t st, const DevElOp& E, const BarrierParams& P
 }
 
 }  // namespace
+
+void elop_launch_shape(const DevElOp& E, int* grid, int* passes_per_wg) {
+  const int epb = kBlock / E.tpe;
+  const int npass = (E.nel + epb - 1) / epb;
+  const int g = E.valid() ? elop_grid_of(E) : 0;
+  if (grid) *grid = g;
+  if (passes_per_wg) *passes_per_wg = g > 0 ? (npass + g - 1) / g : 0;
+}
 
 void launch_elop_assemble(hipStream_t st, const DevElOp& E, const DevElAsm& A, BarrierParams P, const double* Y, double* elmat,
                           double* avals) {

@@ -38,6 +38,14 @@ struct DevElOp {
   bool valid() const { return nel > 0; }
 };
 
+// Register prefetch depth per lane of elop_apply_kernel (values, Y and column ids of the NEXT pass), and the one predicate that
+// decides between its two load paths: the software-pipelined one needs every staged array of an element to fit into kPre
+// registers per lane; deeper elements take the plain path.  ny_el = block * nY, the Y doubles of an element.
+constexpr int kPre = 4;
+__host__ __device__ __forceinline__ bool elop_pipelined(int tpe, int nnz_max, int ny_el, int cmax) {
+  return (nnz_max + tpe - 1) / tpe <= kPre && (ny_el + tpe - 1) / tpe <= kPre && (cmax + tpe - 1) / tpe <= kPre;
+}
+
 // Element-slab assembly of the Newton matrix (replaces the plan T of amg.hpp where the rows of B come in element
 // blocks): per element the structurally nonzero lower-triangle pairs (i >= j) of its columns -- listed once per structure class
 // -- are formed as  sum_q b_qi' Y_q b_qj  into `elmat` (nel x npm), and every lower-triangle entry of A then sums its element
@@ -102,6 +110,8 @@ struct MgEpi {
 
 // matrix-free level: elbuf = per element B_e' (Y_e o (B_e vin_e)), then the dof gather + epilogue.  elbuf: nel x cmax doubles.
 void launch_elop_apply(hipStream_t st, const DevElOp& E, BarrierParams P, const double* Y, double* elbuf, const MgEpi& epi);
+// the launch shape of elop_apply_kernel for E (read-only; what launch_elop_apply uses): workgroups and the passes of the busiest one
+void elop_launch_shape(const DevElOp& E, int* grid, int* passes_per_wg);
 // diagonal of B' Y B through the same two launches: out = 1 / diag
 void launch_elop_diaginv(hipStream_t st, const DevElOp& E, BarrierParams P, const double* Y, double* elbuf, double* dinv);
 // assembled level: the same epilogues behind a CSR product (full symmetric storage)

@@ -29,7 +29,9 @@ Row generators (seeded) put rows strictly inside every term, the chosen term at 
 (sum |coef_i y_i| + |off|)) near a target of 1e-4, 1e-8 or 1e-11, or of order one (the "1e0" regime draws it from [0.25, 1):
 at exactly 1 the row has q = 0 and its gradient and mixed Hessian entries vanish), at scales s in 1e-3 .. 1e3 and, for the
 single terms, 1e-30 .. 1e30; in an intersection every term in turn is the near-active one.  `level_reference()` carries rows, bounds and all to a level: f0, f1 = B' (w (F1 + t c)),
-f2 = B' diag(w F2) B for the CSR B = D R (row q K + k) of the library's own host matrices."""
+f2 = B' diag(w F2) B for the CSR B = D R (row q K + k) of the library's own host matrices; `diag_reference()` and
+`hessian_apply_reference()` read diag(H) and H v off it, and `hessian_apply_matrix_free()` gives H v with the same bound without
+forming H, for the levels of test_gpu_elop_kinds.py that are too large for a dense long-double matrix."""
 import numpy as np
 import scipy.sparse as sp
 
@@ -502,6 +504,55 @@ def level_reference(B, K, w, c, t, Dz, terms, a_node=None, mu_node=None, mask=No
 def hessian_apply_reference(Lv, v):
     vl = np.asarray(v, dtype=LD)
     return Lv.H @ vl, Lv.b_H @ np.abs(v) + (Lv.H_rowlen + 2) * (Lv.H_abs @ np.abs(v))
+
+
+def diag_reference(Lv):
+    """(diag(H) in long double, its bound diag(b_H)): every diagonal entry is one of the sums that make up H."""
+    return np.diagonal(Lv.H).copy(), np.diagonal(Lv.b_H).copy()
+
+
+def hessian_apply_matrix_free(B, K, w, R, v, rows_per_el=None):
+    """H v = B' ((w F2) (B v)) without forming H, for levels too large for a dense N x N long-double H: three keyed long-double
+    sums (B v by row, (w F2) d by node and D-row, B' u by column) from the rows R = reference(terms, Dz).  The bound is
+    hessian_apply_reference's, term by term, with every product by |H| or b_H replaced by three fp64 sparse products:
+
+        |B|' (w bF2) (|B| |v|)  +  (m K + 2 + r + 2) |B|' (|w F2| (|B| |v|)),     m = longest column of B, r = longest row of H
+
+    r comes from the sparsity pattern of |B|' |w F2| |B|, held as a sparse matrix; where that product is itself too large, give
+    rows_per_el (the rows of B come in element blocks of that many): r is then the largest number of unknowns that share an
+    element with one unknown, which is never smaller."""
+    B = sp.csr_matrix(B)
+    n, N = R.F2.shape[0], B.shape[1]
+    assert B.shape[0] == n * K and R.F2.shape[1:] == (K, K)
+    wl, vl = np.asarray(w, dtype=LD), np.asarray(v, dtype=LD)
+    rows = np.repeat(np.arange(B.shape[0], dtype=np.int64), np.diff(B.indptr))
+    cols = B.indices.astype(np.int64)
+    Bl = B.data.astype(LD)
+    d = _sum_by_key(rows, Bl * vl[cols], n * K).reshape(n, K)
+    wH = wl[:, None, None] * R.F2
+    nk = np.arange(n * K, dtype=np.int64).reshape(n, K)
+    key = np.broadcast_to(nk[:, :, None], (n, K, K))
+    u = _sum_by_key(key.reshape(-1), (wH * d[:, None, :]).reshape(-1), n * K)
+    hv = _sum_by_key(cols, Bl * u[rows], N)
+    # the bound, in fp64: node-block-diagonal matrices of |w F2| and w bF2 between |B|' and |B|
+    q = np.repeat(np.arange(n), K * K)
+    kk = np.tile(np.repeat(np.arange(K), K), n)
+    ll = np.tile(np.arange(K), n * K)
+    blk = lambda X: sp.csr_matrix((np.asarray(X, dtype=np.float64).reshape(-1), (q * K + kk, q * K + ll)), shape=(n * K, n * K))
+    Babs = abs(B)
+    Habs_blk, bH_blk = blk(np.abs(wH)), blk(wl[:, None, None] * R.bF2)
+    m = int(np.bincount(B.indices, minlength=N).max()) if B.nnz else 0
+    if rows_per_el is None:
+        pat = sp.csr_matrix(Babs.T @ Habs_blk @ Babs)
+        pat.eliminate_zeros()
+    else:
+        el = np.unique((rows // rows_per_el) * N + cols)
+        E = sp.csr_matrix((np.ones(len(el)), (el // N, el % N)), shape=(B.shape[0] // rows_per_el, N))
+        pat = sp.csr_matrix(E.T @ E)
+    r = int(np.diff(pat.indptr).max()) if pat.nnz else 0
+    bv = Babs @ np.abs(np.asarray(v, dtype=np.float64))
+    bound = Babs.T @ (bH_blk @ bv) + (m * K + 2 + r + 2) * (Babs.T @ (Habs_blk @ bv))
+    return hv, bound
 
 
 def interleave(Dk):

@@ -6,7 +6,10 @@
     yardstick the device kernels are held to in test_gpu_barrier_rows.py.  A correctly rounded fp64 evaluation has ratio
     <= 1 to first order; numpy's pow / log are within an ulp, so rho_base <= 4 pins the bound model (measured: 0.0 .. 1.2);
   * the case table covers what the issue of the check lists;
-  * the level propagation on the committed goldens: oracle f0 / f1 / f2 in fp64 at the golden z against the exact values."""
+  * the level propagation on the committed goldens: oracle f0 / f1 / f2 in fp64 at the golden z against the exact values;
+  * the matrix-free H v reference (three keyed sums, for levels too large for a dense H) against the dense one on small levels:
+    both are long-double sums of the same products in another order, so they differ by long-double roundings of terms the
+    bound already counts at fp64's u = 2^11 long-double ulps: held to 4 long-double ulps of the bound, a ratio of 2^-9."""
 import os
 
 import numpy as np
@@ -211,3 +214,49 @@ def test_level_baseline_on_the_goldens(kind, L, p):
             print("%s L=%d p=%g t=%.0e level %d: kappa_max %.1e  baseline ratio f0 %.2f f1 %.2f f2 %.2f" % (kind, L, p, t, l, kap, r0, r1, r2))
             assert Lv.rows.feasible.all()
             assert max(r0, r1, r2) <= RHO_BASE_MAX
+
+
+MATRIX_FREE_ULPS = 4.0 * 2.0 ** -11      # 4 long-double ulps (2^-64) in units of u = 2^-53, relative to the bound
+
+
+@pytest.mark.parametrize("kind,L,p", [("fem1d", 4, 2.0), ("fem2d", 2, 1.5), ("fem3d", 2, 1.0)])
+def test_matrix_free_hessian_apply_matches_the_dense_reference(kind, L, p):
+    """hessian_apply_matrix_free against hessian_apply_reference at a golden state, every level, for a random vector and a unit
+    vector: values to 4 long-double ulps of the bound, and the two bounds equal up to the fp64 rounding of their own sums."""
+    import scipy.sparse as sp
+    gold = np.load(os.path.join(HERE, "golden", BR.golden_name(kind, L, p)))
+    go = getattr(O, kind)(L)
+    Mo = O.amg(go)
+    dim = go.discretization["dim"]
+    K = len(Mo.D)
+    c = O.map_rows(lambda xi: O.DEFAULT_F[dim](xi), Mo.x)
+    terms = BR.default_terms(dim, p)
+    t = float(gold["ts"][len(gold["ts"]) // 2])
+    rng = np.random.default_rng(3)
+    worst = 0.0
+    for l in range(L):
+        _, _, _, Lv = BR.oracle_level_baseline(Mo, l, gold["z"], c, t, terms)
+        B = BR.interleave([sp.csr_matrix(Dk @ Mo.R[l]) for Dk in Mo.D])
+        N = B.shape[1]
+        e = np.zeros(N)
+        e[N // 2] = 1.0
+        for v in (rng.standard_normal(N), e):
+            hv, bhv = BR.hessian_apply_reference(Lv, v)
+            hm, bhm = BR.hessian_apply_matrix_free(B, K, Mo.w, Lv.rows, v)
+            assert hm.dtype == BR.LD and np.all(bhv[hv != 0] > 0)
+            worst = max(worst, BR.ratio(hm, hv, bhv))
+            assert np.allclose(bhm, bhv, rtol=1e-12, atol=0.0)
+            he, bhe = BR.hessian_apply_matrix_free(B, K, Mo.w, Lv.rows, v, rows_per_el=K * go.discretization["block"])
+            assert BR.ratio(he, hv, bhv) <= MATRIX_FREE_ULPS and np.all(bhe >= bhm)      # r from the elements: never smaller
+        # teeth: one nonzero of B dropped (a lost element entry, a wrong slot) is far outside the bound, pessimistic as it is
+        Bd = B.copy()
+        in_cone = np.repeat(np.arange(B.shape[0]) % K == K - 1, np.diff(B.indptr))      # the slack row of D: in every default cone
+        Bd.data[int(np.argmax(np.abs(Bd.data) * in_cone))] = 0.0
+        hd, _ = BR.hessian_apply_matrix_free(Bd, K, Mo.w, Lv.rows, np.ones(N))
+        teeth = BR.ratio(hd, *BR.hessian_apply_reference(Lv, np.ones(N)))
+        print("level %d: one dropped nonzero of B: ratio %.1e" % (l, teeth))
+        assert teeth > 1e3 * BR.MARGIN * RHO_BASE_MAX
+        d, bd = BR.diag_reference(Lv)
+        assert np.array_equal(d, np.diagonal(Lv.H)) and np.all(d > 0) and np.all(bd >= (K + 2) * d)
+    print("%s L=%d: matrix-free against dense H v, worst ratio %.2e (allowed %.2e)" % (kind, L, worst, MATRIX_FREE_ULPS))
+    assert worst <= MATRIX_FREE_ULPS
