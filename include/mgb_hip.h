@@ -665,6 +665,9 @@ int mgb_plan_chol_premap(mgb_plan p, int dim, int leaf, int single, int mode, in
                          int* producer, long long* soff, long long* eoff, int* fofs, int* iofs, int cap_heights, int* hkind, int* hwg,
                          int* hconsumer, int cap_fwd, int* fwd, int cap_pinv, int* pinv);
 int mgb_chol_selftest(int nx, int ny, double* max_residual, double* flops, double* seconds);
+/* test hook: the finish launch of the two-stage field reductions (csrc/reduce.hpp) alone, on the context's stream.
+ * partials_host: rows x nwg x 5 (three sums, two NaN-sticky maxima per partial); out_host: rows x 5. */
+int mgb_reduce_selftest(mgb_ctx ctx, int rows, int nwg, const double* partials_host, double* out_host);
 
 #ifdef __cplusplus
 }

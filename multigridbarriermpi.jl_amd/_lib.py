@@ -193,6 +193,7 @@ PROTOTYPES = {
     "mgb_plan_chol_premap": [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ll_p, C.c_int, c_int_p, c_int_p, c_ll_p, c_ll_p, c_int_p,
                              c_int_p, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int, c_int_p],
     "mgb_chol_selftest": [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p],
+    "mgb_reduce_selftest": [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p],
 }
 _SPECIAL = {"mgb_last_error": ([], C.c_char_p), "mgb_version": ([], C.c_int), "mgb_device_count": ([], C.c_int)}
 

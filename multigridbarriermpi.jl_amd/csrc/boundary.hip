@@ -1,45 +1,19 @@
 // Boundary integrals of nodal fields on gfx950.  B fields on one geometry are reduced over its boundary
-// facets by ONE pair of plain launches on one stream, the way energy.hip reduces over the nodes:
+// facets by ONE pair of plain launches on one stream, the two stages of reduce.hpp, the way energy.hip reduces over the nodes:
 //   boundary_kernel<DIM, K>: grid (workgroups(nf, q), B); a workgroup takes 256 / q whole facets, one thread per (facet, facet
 //     node) -- thread t is node t % q of the workgroup's facet t / q, so the facet tables are read contiguously and a facet never
 //     straddles two workgroups; threads past the last whole facet, and those of facets the mask leaves out, contribute the
 //     identity.  Each thread runs boundary.hpp's Node (sigma through energy.hpp's Node, sigma . n, the tangential part); the
-//     workgroup reduces the five columns -- wave shuffles, then LDS across the four waves -- and writes ONE partial row per
-//     (field, workgroup).  With a per-facet output the threads leave omega sigma . n in LDS and node 0 of every facet sums its
+//     workgroup reduces the five columns and writes ONE partial row per (field, workgroup).  With a per-facet output the threads leave omega sigma . n in LDS and node 0 of every facet sums its
 //     facet's q values in ascending order.
-//   boundary_finish: grid (B); the workgroup of a field combines that field's partials in ascending workgroup order.
+//   reduce::launch_finish: grid (B); the workgroup of a field finishes that field's partials.
 //   boundary_load_kernel / boundary_load_add_kernel: the Neumann load of DESIGN.md section 4i, see below.
-// What a field's result is made of depends on the facet list alone, never on B or on the field's place in the batch.  No atomics
-// and no hand-off between workgroups inside a launch; every word is written by one thread with a vector store.
+// What a field's result is made of depends on the facet list alone, never on B or on the field's place in the batch.
 #include "boundary.hpp"
 
 namespace mgb {
 namespace boundary {
 namespace {
-
-static_assert(kThreads == 256, "four waves of 64");
-constexpr int kWaves = kThreads / 64;
-
-// Reduce c[0..4] over the workgroup; the result is valid in thread 0.
-__device__ inline void block_combine(double* c, double (*red)[kCols]) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    double t[kCols];
-#pragma unroll
-    for (int k = 0; k < kCols; ++k) t[k] = __shfl_down(c[k], o, 64);
-    combine(c, t);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kCols; ++k) red[wave][k] = c[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int v = 1; v < kWaves; ++v) combine(c, red[v]);
-  }
-}
 
 template <int DIM, int K>
 __global__ void __launch_bounds__(kThreads) boundary_kernel(Args A, double* __restrict__ partials, double* __restrict__ facet_flux) {
@@ -62,27 +36,11 @@ __global__ void __launch_bounds__(kThreads) boundary_kernel(Args A, double* __re
       facet_flux[(size_t)b * A.nf + f] = s;
     }
   }
-  block_combine(c, red);
+  block_reduce<kCols>(c, Combine{}, red);
   if (threadIdx.x == 0) {
     double* row = partials + ((size_t)b * gridDim.x + blockIdx.x) * kCols;
 #pragma unroll
     for (int k = 0; k < kCols; ++k) row[k] = c[k];
-  }
-}
-
-__global__ void __launch_bounds__(kThreads) boundary_finish(const double* __restrict__ partials, int nwg, double* __restrict__ out) {
-  __shared__ double red[kWaves][kCols];
-  const int b = blockIdx.x;
-  const int chunk = (nwg + kThreads - 1) / kThreads;
-  const long long b0 = (long long)threadIdx.x * chunk;
-  const long long b1 = b0 + chunk < nwg ? b0 + chunk : nwg;
-  double c[kCols];
-  identity(c);
-  for (long long g = b0; g < b1; ++g) combine(c, partials + ((size_t)b * nwg + g) * kCols);
-  block_combine(c, red);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 0; k < kCols; ++k) out[(size_t)b * kCols + k] = c[k];
   }
 }
 
@@ -96,8 +54,9 @@ struct LaunchFlux {
     const long long nwg = workgroups(A.nf, A.q);
     hipLaunchKernelGGL((boundary_kernel<DIM, K>), dim3((unsigned)nwg, (unsigned)A.E.B), dim3(kThreads), 0, stream, A, scratch,
                        facet_flux);
-    hipLaunchKernelGGL(boundary_finish, dim3((unsigned)A.E.B), dim3(kThreads), 0, stream, scratch, (int)nwg,
-                       scratch + (size_t)nwg * A.E.B * kCols);
+    // the partials hold boundary.hpp's zeros where reduce::identity has -inf: columns 3 and 4 are absolute values and thread 0
+    // always holds a partial, so the finish gives the bits of a zero seed
+    launch_finish(stream, A.E.B, scratch, (int)nwg, (size_t)nwg * kCols, kCols, scratch + results_offset(A.nf, A.q, A.E.B));
   }
 };
 
@@ -126,7 +85,7 @@ __global__ void __launch_bounds__(kThreads) boundary_load_add_kernel(int nb, con
 void launch_boundary_load(hipStream_t stream, const LoadArgs& A, int B, const double* h, double* out) {
   if (A.nb < 0 || A.nf < 0 || A.q < 1 || B < 1 || B > 65535) throw ArgError("boundary_load: bad incidence table, or B outside [1, 65535]");
   if (A.nb == 0) return;
-  const unsigned nwg = (unsigned)(((long long)A.nb + kThreads - 1) / kThreads);
+  const unsigned nwg = (unsigned)reduce::workgroups(A.nb);
   hipLaunchKernelGGL(boundary_load_kernel, dim3(nwg, (unsigned)B), dim3(kThreads), 0, stream, A, h, out);
 }
 
@@ -134,7 +93,7 @@ void launch_boundary_load_add(hipStream_t stream, int nb, const int* rows, const
                               long long offset, double* y) {
   if (nb < 0 || stride < 1 || offset < 0 || offset >= stride) throw ArgError("boundary_load_add: bad stride or offset");
   if (nb == 0) return;
-  const unsigned nwg = (unsigned)(((long long)nb + kThreads - 1) / kThreads);
+  const unsigned nwg = (unsigned)reduce::workgroups(nb);
   hipLaunchKernelGGL(boundary_load_add_kernel, dim3(nwg), dim3(kThreads), 0, stream, nb, rows, load, alpha, stride, offset, y);
 }
 

@@ -1,6 +1,6 @@
 // Boundary facets of a geometry and boundary integrals of p-Laplace solutions: the facet list, built
 // ONCE per geometry on the host, and what ONE facet node contributes, written ONCE.  The gfx950 kernels (boundary.hip) and the
-// host restatement (mgb_geo_boundary_flux_host) both run Node below; sigma is energy.hpp's Node::flux, combine is norms.hpp's.
+// host restatement (mgb_geo_boundary_flux_host) both run Node below; sigma is energy.hpp's Node::flux, combine is reduce.hpp's.
 //   The elements are broken and their quadrature is nodal: every node of a boundary facet is a row of x and z already, so a
 //   boundary rule is a list of (row, weight) pairs per facet plus the facet's outward unit normal.
 //   A facet of an element is a BOUNDARY facet when the sorted tuple of the continuous dofs (subspaces["full"][L-1], one entry 1
@@ -26,9 +26,7 @@
 namespace mgb {
 namespace boundary {
 
-constexpr int kCols = 5;      // MGB_BOUNDARY_COLS
-static_assert(kCols == norms::kCols, "norms::combine takes three sums, then two NaN-sticky maxima: the columns of this module");
-using norms::combine;
+using namespace reduce;      // kCols (MGB_BOUNDARY_COLS), kThreads, combine
 
 // the facet list of one geometry, on the host
 struct Facets {
@@ -51,7 +49,8 @@ struct Args {
   int nf = 0, q = 0;
 };
 
-// all five columns are sums of, or maxima over, non-negative or signed terms whose empty value is 0
+// all five columns are sums of, or maxima over, non-negative or signed terms whose empty value is 0: an empty or wholly masked
+// facet list gives zeros, not reduce::identity's -inf, which this hides
 MGB_HD void identity(double* c) { c[0] = c[1] = c[2] = c[3] = c[4] = 0.0; }
 
 template <int DIM, int K>
@@ -329,13 +328,14 @@ inline Interior build_interior(const GeometryHost& g) {
 }
 
 // facets per workgroup (a facet never straddles two workgroups), workgroups per field, doubles of scratch of the two launches
-constexpr int kThreads = 256;
+// and where the finish leaves its results in them
 inline int facets_per_workgroup(int q) { return kThreads / q; }
 inline long long workgroups(int nf, int q) {
   const int fpw = facets_per_workgroup(q);
   return nf > 0 ? ((long long)nf + fpw - 1) / fpw : 1;
 }
 inline size_t scratch_doubles(int nf, int q, int B) { return (size_t)(workgroups(nf, q) + 1) * B * kCols; }      // partials, then B x kCols results
+inline size_t results_offset(int nf, int q, int B) { return (size_t)workgroups(nf, q) * B * kCols; }
 
 // ---------------------------------------------------------------------------------------------------- Neumann load
 //   The objective is sum_i w_i c_i . (Dz)_i, so  int_Gamma h u ds  adds
@@ -412,9 +412,9 @@ void launch_boundary_load(hipStream_t stream, const LoadArgs& A, int B, const do
 // y[rows[j] * stride + offset] += alpha * load[j], one thread per j < nb (rows are distinct: no conflicts)
 void launch_boundary_load_add(hipStream_t stream, int nb, const int* rows, const double* load, double alpha, long long stride,
                               long long offset, double* y);
-// boundary.hip: two launches on `stream` -- partials on grid (workgroups, B), one thread per (facet, facet node), then one
-// workgroup per field that combines that field's partials in ascending workgroup order; all pointers of A are device pointers
-// (A.E.z a device table of B device pointers); the B x kCols results are at scratch + workgroups * B * kCols; facet_flux
+// boundary.hip: two launches on `stream` -- partials on grid (workgroups, B), one thread per (facet, facet node), then the
+// finish of reduce.hpp, one workgroup per field; all pointers of A are device pointers (A.E.z a device table of B device
+// pointers); the B x kCols results are at scratch + results_offset; facet_flux
 // (nullable): B x nf device doubles
 void launch_boundary_flux(hipStream_t stream, int dim, int k, const Args& A, double* scratch, double* facet_flux);
 #endif

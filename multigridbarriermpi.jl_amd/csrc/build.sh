@@ -34,6 +34,7 @@ compile "$HERE/_obj/kernels.o" "$HERE/kernels.hip" "$HIPCC" --offload-arch=gfx95
 compile "$HERE/_obj/kernels_f32.o" "$HERE/kernels_f32.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/mg.o" "$HERE/mg.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/interp.o" "$HERE/interp.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
+compile "$HERE/_obj/reduce.o" "$HERE/reduce.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/norms.o" "$HERE/norms.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/energy.o" "$HERE/energy.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/boundary.o" "$HERE/boundary.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
@@ -48,5 +49,5 @@ for pid in "${pids[@]}"; do
   wait "$pid" || { echo "build.sh: a compile job failed" >&2; exit 1; }
 done
 rm -f "$OUT/libmgb_hip.so"
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,chol_premap,kernels,kernels_f32,mg,interp,norms,energy,boundary,estimate,parabolic,gpuchol,amg,amg_mg,comm,capi}.o -lpthread -ldl
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,chol_premap,kernels,kernels_f32,mg,interp,reduce,norms,energy,boundary,estimate,parabolic,gpuchol,amg,amg_mg,comm,capi}.o -lpthread -ldl
 echo "built $OUT/libmgb_hip.so"

@@ -1272,10 +1272,10 @@ int mgb_field_norms(mgb_locator loc, int S, mgb_vec z, double q, mgb_vec ref_val
     norms::launch_field_norms(st, L.dim, L.k, A, loc->norm_scratch.p, loc->norm_counts.p);
     hip_check(hipGetLastError(), "field_norms launch");
     hip_check(hipStreamSynchronize(st), "sync field_norms");
-    const size_t nwg = (size_t)norms::workgroups(L.n);
-    hip_check(hipMemcpy(out_host, loc->norm_scratch.p + nwg * S * norms::kCols, (size_t)S * norms::kCols * sizeof(double),
+    hip_check(hipMemcpy(out_host, loc->norm_scratch.p + norms::results_offset(L.n, S), (size_t)S * reduce::kCols * sizeof(double),
                         hipMemcpyDeviceToHost), "D2H");
-    if (outside_host) hip_check(hipMemcpy(outside_host, loc->norm_counts.p + nwg, sizeof(long long), hipMemcpyDeviceToHost), "D2H");
+    if (outside_host)
+      hip_check(hipMemcpy(outside_host, loc->norm_counts.p + norms::count_offset(L.n), sizeof(long long), hipMemcpyDeviceToHost), "D2H");
   });
 }
 int mgb_geo_field_norms_host(mgb_geo g, int S, const double* z, double q, const double* ref_vals, const double* ref_grads,
@@ -1314,13 +1314,27 @@ int mgb_geo_field_norms_host(mgb_geo g, int S, const double* z, double q, const 
 
 // ---- energy, flux and cone margin of p-Laplace solutions (energy.hpp / energy.hip)
 namespace {
-// what the three entry points check alike; s < 0: no slack column (flux)
-void need_energy_shape(const char* who, int B, int S, int u, int s, double p, int f_rows, bool has_f) {
-  const std::string w(who);
+// what the entry points of energy, boundary flux and estimate check alike: B fields of S columns, column u, exponent p
+void need_field_shape(const std::string& w, int B, int S, int u, double p) {
   if (B < 1) throw std::invalid_argument(w + ": B must be >= 1");
   if (S < 1) throw std::invalid_argument(w + ": S must be >= 1");
   if (!good_q(p)) throw std::invalid_argument(w + ": p must be finite and >= 1");
   if (u < 0 || u >= S) throw std::invalid_argument(w + ": column u outside [0, S)");
+}
+// checks every z[b] and collects the table of the B fields of n x S values on the context of `loc`
+void field_table(const std::string& w, const mgb_locator_s* loc, int B, const mgb_vec* z, int S, std::vector<const double*>& table) {
+  table.resize((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    if (z[b] == nullptr) throw std::invalid_argument(w + ": null field");
+    if (z[b]->n != (long long)loc->loc.n * S) throw std::invalid_argument(w + ": every z must hold n x S values");
+    if (z[b]->ctx != loc->ctx) throw std::invalid_argument(w + ": vectors of another context");
+    table[b] = z[b]->buf.p;
+  }
+}
+// the slack column and the forcing on top; s < 0: no slack column (flux)
+void need_energy_shape(const char* who, int B, int S, int u, int s, double p, int f_rows, bool has_f) {
+  const std::string w(who);
+  need_field_shape(w, B, S, u, p);
   if (s >= S) throw std::invalid_argument(w + ": column s outside [0, S)");
   if (u == s) throw std::invalid_argument(w + ": u and s are the same column");
   if (has_f && f_rows != 1 && f_rows != B) throw std::invalid_argument(w + ": f must have 1 or B rows");
@@ -1334,13 +1348,8 @@ int mgb_geo_field_energy(mgb_locator loc, int B, const mgb_vec* z, int S, int u,
     need(s >= 0, "geo_field_energy: column s outside [0, S)");
     need(loc->ctx->ctx.world == 1, "geo_field_energy: sharded contexts are not supported");
     const interp::Locator& L = loc->loc;
-    std::vector<const double*> table((size_t)B);
-    for (int b = 0; b < B; ++b) {
-      need(z[b] != nullptr, "geo_field_energy: null field");
-      need(z[b]->n == (long long)L.n * S, "geo_field_energy: every z must hold n x S values");
-      need(z[b]->ctx == loc->ctx, "geo_field_energy: vectors of another context");
-      table[b] = z[b]->buf.p;
-    }
+    std::vector<const double*> table;
+    field_table("geo_field_energy", loc, B, z, S, table);
     need(!p_nodal || p_nodal->n == L.n, "geo_field_energy: p_nodal must hold n values");
     need(!f || f->n == (long long)f_rows * L.n, "geo_field_energy: f must hold f_rows x n values");
     need((!p_nodal || p_nodal->ctx == loc->ctx) && (!f || f->ctx == loc->ctx), "geo_field_energy: vectors of another context");
@@ -1362,8 +1371,7 @@ int mgb_geo_field_energy(mgb_locator loc, int B, const mgb_vec* z, int S, int u,
     energy::launch_field_energy(st, L.dim, L.k, A, loc->energy_scratch.p);
     hip_check(hipGetLastError(), "geo_field_energy launch");
     hip_check(hipStreamSynchronize(st), "sync geo_field_energy");
-    const size_t nwg = (size_t)energy::workgroups(L.n);
-    hip_check(hipMemcpy(out_host, loc->energy_scratch.p + nwg * B * energy::kCols, (size_t)B * energy::kCols * sizeof(double),
+    hip_check(hipMemcpy(out_host, loc->energy_scratch.p + energy::results_offset(L.n, B), (size_t)B * reduce::kCols * sizeof(double),
                         hipMemcpyDeviceToHost), "D2H");
   });
 }
@@ -1416,13 +1424,6 @@ int mgb_geo_field_flux(mgb_locator loc, mgb_vec z, int S, int u, double p, mgb_v
 
 // ---- boundary facets and boundary integrals of p-Laplace solutions (boundary.hpp / boundary.hip)
 namespace {
-void need_boundary_shape(const char* who, int B, int S, int u, double p) {
-  const std::string w(who);
-  if (B < 1) throw std::invalid_argument(w + ": B must be >= 1");
-  if (S < 1) throw std::invalid_argument(w + ": S must be >= 1");
-  if (!good_q(p)) throw std::invalid_argument(w + ": p must be finite and >= 1");
-  if (u < 0 || u >= S) throw std::invalid_argument(w + ": column u outside [0, S)");
-}
 void copy_facets(const boundary::Facets& F, int32_t* element, int32_t* nodes, double* weights, double* normal, double* measure,
                  double* centre) {
   if (element) std::copy(F.element.begin(), F.element.end(), element);
@@ -1483,18 +1484,13 @@ int mgb_boundary_flux(mgb_boundary bd, int B, const mgb_vec* z, int S, int u, do
                       const unsigned char* mask_host, double* facet_flux_host, double* out_host) {
   return guard([&] {
     need(bd && z && out_host, "boundary_flux: null argument");
-    need_boundary_shape("boundary_flux", B, S, u, p);
+    need_field_shape("boundary_flux", B, S, u, p);
     mgb_locator_s* loc = bd->loc;
     need(loc->ctx->ctx.world == 1, "boundary_flux: sharded contexts are not supported");
     const interp::Locator& L = loc->loc;
     const boundary::Facets& F = bd->F;
-    std::vector<const double*> table((size_t)B);
-    for (int b = 0; b < B; ++b) {
-      need(z[b] != nullptr, "boundary_flux: null field");
-      need(z[b]->n == (long long)L.n * S, "boundary_flux: every z must hold n x S values");
-      need(z[b]->ctx == loc->ctx, "boundary_flux: vectors of another context");
-      table[b] = z[b]->buf.p;
-    }
+    std::vector<const double*> table;
+    field_table("boundary_flux", loc, B, z, S, table);
     need(!p_nodal || p_nodal->n == L.n, "boundary_flux: p_nodal must hold n values");
     need(!p_nodal || p_nodal->ctx == loc->ctx, "boundary_flux: vectors of another context");
     need(B <= 65535, "boundary_flux: at most 65535 fields per call");
@@ -1524,8 +1520,7 @@ int mgb_boundary_flux(mgb_boundary bd, int B, const mgb_vec* z, int S, int u, do
     boundary::launch_boundary_flux(st, L.dim, L.k, A, bd->scratch.p, facet_flux_host && nfac ? bd->facet_scratch.p : nullptr);
     hip_check(hipGetLastError(), "boundary_flux launch");
     hip_check(hipStreamSynchronize(st), "sync boundary_flux");
-    const size_t nwg = (size_t)boundary::workgroups(F.nf, F.q);
-    hip_check(hipMemcpy(out_host, bd->scratch.p + nwg * B * boundary::kCols, (size_t)B * boundary::kCols * sizeof(double),
+    hip_check(hipMemcpy(out_host, bd->scratch.p + boundary::results_offset(F.nf, F.q, B), (size_t)B * reduce::kCols * sizeof(double),
                         hipMemcpyDeviceToHost), "D2H");
     if (facet_flux_host && nfac)
       hip_check(hipMemcpy(facet_flux_host, bd->facet_scratch.p, nfac * sizeof(double), hipMemcpyDeviceToHost), "D2H");
@@ -1551,7 +1546,7 @@ int mgb_geo_boundary_flux_host(mgb_geo g, int B, const double* const* z, int S, 
                                const unsigned char* mask, double* facet_flux, double* out) {
   return guard([&] {
     need(g && z && out, "geo_boundary_flux_host: null argument");
-    need_boundary_shape("geo_boundary_flux_host", B, S, u, p);
+    need_field_shape("geo_boundary_flux_host", B, S, u, p);
     for (int b = 0; b < B; ++b) need(z[b] != nullptr, "geo_boundary_flux_host: null field");
     need(g->g.w.size() == (size_t)g->g.n, "geo_boundary_flux_host: the geometry must carry one weight per node");
     const boundary::Facets F = boundary::build_facets(g->g);
@@ -1575,11 +1570,10 @@ int mgb_geo_boundary_flux_host(mgb_geo g, int B, const double* const* z, int S, 
 
 // ---- residual error indicators (estimate.hpp / estimate.hip)
 namespace {
+// the power and the scale on top of one field
 void need_estimate_shape(const char* who, int S, int u, double p, double r, int own_scale, double scale) {
   const std::string w(who);
-  if (S < 1) throw std::invalid_argument(w + ": S must be >= 1");
-  if (!good_q(p)) throw std::invalid_argument(w + ": p must be finite and >= 1");
-  if (u < 0 || u >= S) throw std::invalid_argument(w + ": column u outside [0, S)");
+  need_field_shape(w, 1, S, u, p);
   if (!good_q(r)) throw std::invalid_argument(w + ": r must be finite and >= 1");
   if (own_scale && !std::isfinite(scale)) throw std::invalid_argument(w + ": the scale must be finite");
 }
@@ -1670,8 +1664,8 @@ int mgb_estimate(mgb_boundary bd, mgb_vec z, int S, int u, double p, mgb_vec p_n
     estimate::launch_estimate(st, L.dim, L.k, A, bd->est_J.p, bd->est_N.p, eta->buf.p, bd->est_scratch.p);
     hip_check(hipGetLastError(), "estimate launch");
     hip_check(hipStreamSynchronize(st), "sync estimate");
-    hip_check(hipMemcpy(out_host, bd->est_scratch.p + (nd - estimate::kCols), estimate::kCols * sizeof(double), hipMemcpyDeviceToHost),
-              "D2H");
+    hip_check(hipMemcpy(out_host, bd->est_scratch.p + estimate::results_offset(I.nel, L.block, facets, F.q),
+                        reduce::kCols * sizeof(double), hipMemcpyDeviceToHost), "D2H");
   });
 }
 int mgb_geo_estimate_host(mgb_geo g, const double* z, int S, int u, double p, const double* p_nodal, const double* f, double r,
@@ -1712,7 +1706,7 @@ int mgb_geo_estimate_host(mgb_geo g, const double* z, int S, int u, double p, co
     A.nf = F.nf;
     A.elem_facet = I.elem_facet.data();
     std::vector<double> etav((size_t)I.nel * estimate::kParts);
-    double res[estimate::kCols];
+    double res[reduce::kCols];
     estimate::estimate_host(dim, F.k, A, etav.data(), Jv.data(), Nv.data(), res);
     std::copy(etav.begin(), etav.end(), eta);
     if (J) std::copy(Jv.begin(), Jv.end(), J);
@@ -1721,7 +1715,7 @@ int mgb_geo_estimate_host(mgb_geo g, const double* z, int S, int u, double p, co
       else std::fill(N, N + F.nf, 0.0);
     }
     if (sigma_out) std::copy(sigma.begin(), sigma.end(), sigma_out);
-    std::copy(res, res + estimate::kCols, out);
+    std::copy(res, res + reduce::kCols, out);
   });
 }
 
@@ -2194,6 +2188,23 @@ int mgb_chol_selftest(int nx, int ny, double* max_residual, double* flops, doubl
     if (max_residual) *max_residual = mx;
     if (flops) *flops = ch.factor_flops();
     if (seconds) *seconds = sec;
+  });
+}
+
+int mgb_reduce_selftest(mgb_ctx ctx, int rows, int nwg, const double* partials_host, double* out_host) {
+  return guard([&] {
+    need(ctx && partials_host && out_host, "reduce_selftest: null argument");
+    need(rows >= 1 && nwg >= 1, "reduce_selftest: rows and nwg must be >= 1");
+    hipStream_t st = ctx->ctx.stream;
+    hip_check(hipSetDevice(ctx->ctx.device), "hipSetDevice");
+    const size_t np = (size_t)rows * nwg * reduce::kCols, no = (size_t)rows * reduce::kCols;
+    DevBuf<double> buf;
+    buf.alloc(np + no);
+    buf.upload(partials_host, np);
+    reduce::launch_finish(st, rows, buf.p, nwg, (size_t)nwg * reduce::kCols, reduce::kCols, buf.p + np);
+    hip_check(hipGetLastError(), "reduce_selftest launch");
+    hip_check(hipStreamSynchronize(st), "sync reduce_selftest");
+    hip_check(hipMemcpy(out_host, buf.p + np, no * sizeof(double), hipMemcpyDeviceToHost), "D2H");
   });
 }
 

@@ -1,6 +1,6 @@
 // Energy, flux and cone margin of p-Laplace solutions by the nodal quadrature rule: what ONE node
 // contributes, written ONCE.  The gfx950 kernels (energy.hip) and the host restatement (mgb_geo_field_energy_host) both run
-// Node below; the element maths is interp.hpp's, powq and combine (with its NaN-sticky nanmax) are norms.hpp's.
+// Node below; the element maths is interp.hpp's, powq is norms.hpp's, combine and identity are reduce.hpp's.
 //   At node i of a field z (n x S row-major), in i's own element e = i / block:
 //     g = physical gradient of column u at x_i (what the dx / dy / dz operator rows give), a = |g|_2, p = the exponent at i,
 //     P = a^p (no pow for p = 2 and p = 1, zero for a = 0), s_i = column s, f_i = nodal forcing (null: 0), w_i the weight.
@@ -15,9 +15,7 @@
 namespace mgb {
 namespace energy {
 
-constexpr int kCols = 5;      // MGB_ENERGY_COLS
-static_assert(kCols == norms::kCols, "norms::combine takes three sums, then two NaN-sticky maxima: the columns of this module");
-using norms::combine;
+using namespace reduce;      // kCols (MGB_ENERGY_COLS), kThreads, combine, identity, workgroups
 using norms::powq;
 
 // what all fields of one call share: geometry, exponent, columns
@@ -31,12 +29,6 @@ struct Args {
   long long f_stride = 0;
   int n = 0, S = 0, u = 0, s = 0, B = 0;
 };
-
-// the identity of combine for the five columns: the second maximum may be negative
-MGB_HD void identity(double* c) {
-  c[0] = c[1] = c[2] = c[3] = 0.0;
-  c[4] = -std::numeric_limits<double>::infinity();
-}
 
 // a^(p-1) for a >= 0: 1 at p = 1 where a > 0, 0 at a = 0
 MGB_HD double powm1(double a, double p) {
@@ -152,15 +144,14 @@ inline void field_energy_host(int dim, int k, const Args& A, double* out, double
   interp::dispatch(dim, k, h);
 }
 
-// workgroups of the partials launch per field, and the doubles of scratch the two launches need
-constexpr int kThreads = 256;
-inline long long workgroups(int n) { return ((long long)n + kThreads - 1) / kThreads; }
+// the doubles of scratch the two launches need, and where the finish leaves its results in them
 inline size_t scratch_doubles(int n, int B) { return (size_t)(workgroups(n) + 1) * B * kCols; }      // partials, then B x kCols results
+inline size_t results_offset(int n, int B) { return (size_t)workgroups(n) * B * kCols; }
 
 #if defined(__HIPCC__)
-// energy.hip: two launches on `stream` -- partials on grid (workgroups, B), then one workgroup per field that combines that
-// field's partials in ascending workgroup order; all pointers of A are device pointers (A.z a device table of B device
-// pointers); the B x kCols results are at scratch + workgroups * B * kCols
+// energy.hip: two launches on `stream` -- partials on grid (workgroups, B), then the finish of reduce.hpp, one workgroup per
+// field; all pointers of A are device pointers (A.z a device table of B device pointers); the B x kCols results are at
+// scratch + results_offset
 void launch_field_energy(hipStream_t stream, int dim, int k, const Args& A, double* scratch);
 // one launch, one thread per node: flux (n x dim) of the field z; of A the geometry, exponent, S and u are read
 void launch_field_flux(hipStream_t stream, int dim, int k, const Args& A, const double* z, double* flux);

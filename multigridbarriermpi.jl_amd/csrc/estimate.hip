@@ -1,70 +1,31 @@
 // Residual error indicators on gfx950.  Behind the flux launch that wrote Sigma (energy.hip's
-// flux_kernel), plain launches on one stream, 256 threads each, fp64:
+// flux_kernel), plain launches on one stream, 256 threads each, fp64, reduced by the two stages of reduce.hpp:
 //   facet_terms_kernel<DIM, K>: one thread per (facet, facet node); the interior facets come first, then the boundary facets
 //     when there are Neumann data.  A workgroup takes 256 / q whole facets -- thread t is node t % q of the workgroup's facet
 //     t / q, so the facet tables are read contiguously and a facet never straddles two workgroups.  Every thread runs
 //     estimate.hpp's Terms::jump or Terms::neumann and leaves its term in LDS; node 0 of a facet adds its q terms in ascending
 //     order and writes J[F] or N[F] (0 for a facet the mask leaves out).  The workgroup reduces |J_Fj| with the NaN-sticky
-//     maximum -- wave shuffles, then LDS across the four waves -- and writes ONE partial maximum.  Left out when there is no
-//     facet at all.
+//     maximum and writes ONE partial maximum.  Left out when there is no facet at all.
 //   element_indicator_kernel<DIM, K>: one thread per node, 256 / block whole elements per workgroup.  Every thread runs
 //     Terms::node and leaves w_i |rho_i|^r and w_i in LDS; the first lane of an element adds both in ascending local order,
 //     gathers J / N through the element -> facet table and leaves the element's three numbers in LDS; the workgroup's threads
 //     write them (nel x 3, contiguous in the thread index) and thread 0 combines the elements' columns in ascending element
 //     order into ONE partial row.
-//   estimate_finish: one workgroup combines the element partials and the facet maxima in ascending workgroup order (thread t
-//     takes the t-th contiguous run, then the tree of energy.hip).
-// No atomics and no hand-off between workgroups inside a launch; no thread returns in front of a barrier -- threads past the
-// end idle through them; every word is written by one thread with a vector store.
+//   estimate_finish: one workgroup finishes the element partials; every thread folds its run of the facet maxima into column
+//     4 in front of the tree.
 #include "estimate.hpp"
 
 namespace mgb {
 namespace estimate {
 namespace {
 
-static_assert(kThreads == 256, "four waves of 64");
-constexpr int kWaves = kThreads / 64;
 constexpr int kMaxElems = kThreads / 2;      // elements per workgroup at the smallest block
-
-// NaN-sticky maximum of v over the workgroup; the result is valid in thread 0
-__device__ inline double block_nanmax(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = nanmax(v, __shfl_down(v, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int k = 1; k < kWaves; ++k) v = nanmax(v, red[k]);
-  }
-  return v;
-}
-
-// Reduce c[0..4] over the workgroup; the result is valid in thread 0.
-__device__ inline void block_combine(double* c, double (*red)[kCols]) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    double t[kCols];
-#pragma unroll
-    for (int k = 0; k < kCols; ++k) t[k] = __shfl_down(c[k], o, 64);
-    combine(c, t);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kCols; ++k) red[wave][k] = c[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int v = 1; v < kWaves; ++v) combine(c, red[v]);
-  }
-}
 
 template <int DIM, int K>
 __global__ void __launch_bounds__(kThreads) facet_terms_kernel(Args A, double* __restrict__ J, double* __restrict__ N,
                                                                double* __restrict__ partial_max) {
   __shared__ double per_node[kThreads];
-  __shared__ double red[kWaves];
+  __shared__ double red[kWaves][1];
   const int q = A.q, fpw = kThreads / q;
   const int lf = threadIdx.x / q, j = threadIdx.x - lf * q;
   const long long F = (long long)blockIdx.x * fpw + lf;
@@ -88,8 +49,8 @@ __global__ void __launch_bounds__(kThreads) facet_terms_kernel(Args A, double* _
     if (interior) J[F] = s;
     else N[F - A.nif] = s;
   }
-  const double m = block_nanmax(aj, red);
-  if (threadIdx.x == 0) partial_max[blockIdx.x] = m;
+  block_reduce<1>(&aj, NanMax<1>{}, red);
+  if (threadIdx.x == 0) partial_max[blockIdx.x] = aj;
 }
 
 template <int DIM, int K>
@@ -141,21 +102,13 @@ __global__ void __launch_bounds__(kThreads) element_indicator_kernel(Args A, con
 __global__ void __launch_bounds__(kThreads) estimate_finish(const double* __restrict__ partials, int nwg,
                                                             const double* __restrict__ partial_max, int nwgf, double* __restrict__ out) {
   __shared__ double red[kWaves][kCols];
+  // empty runs carry reduce::identity, -inf in column 4, where the partials hold zeros: the maxima are absolute values and
+  // thread 0 always holds an element partial, so either seed gives the same bits
   double c[kCols];
-  identity(c);
-  {
-    const int chunk = (nwg + kThreads - 1) / kThreads;
-    const long long b0 = (long long)threadIdx.x * chunk;
-    const long long b1 = b0 + chunk < nwg ? b0 + chunk : nwg;
-    for (long long g = b0; g < b1; ++g) combine(c, partials + (size_t)g * kCols);
-  }
-  {
-    const int chunk = (nwgf + kThreads - 1) / kThreads;
-    const long long b0 = (long long)threadIdx.x * chunk;
-    const long long b1 = b0 + chunk < nwgf ? b0 + chunk : nwgf;
-    for (long long g = b0; g < b1; ++g) c[4] = nanmax(c[4], partial_max[g]);
-  }
-  block_combine(c, red);
+  run_combine(partials, kCols, nwg, c);
+  const Run r = run_of(threadIdx.x, nwgf);
+  for (long long g = r.b0; g < r.b1; ++g) c[4] = nanmax(c[4], partial_max[g]);
+  block_reduce<kCols>(c, Combine{}, red);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < kCols; ++k) out[k] = c[k];
@@ -171,7 +124,7 @@ struct Launch {
     const long long nwge = element_workgroups(A.nel, A.own.block), nwgf = facet_workgroups(facets_launched(A), A.q);
     double* partials = scratch;
     double* partial_max = scratch + (size_t)nwge * kCols;
-    double* out = partial_max + nwgf;
+    double* out = scratch + results_offset(A.nel, A.own.block, facets_launched(A), A.q);
     if (nwgf > 0)
       hipLaunchKernelGGL((facet_terms_kernel<DIM, K>), dim3((unsigned)nwgf), dim3(kThreads), 0, stream, A, J, N, partial_max);
     hipLaunchKernelGGL((element_indicator_kernel<DIM, K>), dim3((unsigned)nwge), dim3(kThreads), 0, stream, A, J, A.h ? N : nullptr,

@@ -1,7 +1,7 @@
 // Residual error indicators of p-Laplace solutions: what ONE node, ONE facet node and ONE element
 // contribute, written ONCE.  The gfx950 kernels (estimate.hip) and the host restatement (mgb_geo_estimate_host) both run the
 // routines below; sigma is energy.hpp's Node::flux (the launch of mgb_geo_field_flux, the same bits), the element maths is
-// interp.hpp's, powq and combine (with its NaN-sticky nanmax) are norms.hpp's, the facet lists are boundary.hpp's.
+// interp.hpp's, powq is norms.hpp's, combine and nanmax are reduce.hpp's, the facet lists are boundary.hpp's.
 //   Sigma (n x dim) is the nodal flux |grad u|^(p-2) grad u, every node in its own element.  lambda_i is the scale: a scalar,
 //   or p_i (the problem  min int f u + s,  s >= |grad u|^p  has the strong form  f - p div sigma = 0  and the natural condition
 //   p sigma . n + h = 0; lambda = 1 is energy()'s convention).  r >= 1 is the power.
@@ -15,7 +15,7 @@
 //   Element e:  h_e = (sum_{i in e} w_i)^(1/dim);  vol = h_e^r sum_i w_i |rho_i|^r (local i ascending);  jump = (h_e / 2) sum J_F
 //               over its interior facets and  neu = h_e sum N_F over its boundary facets (local facet ascending, through the
 //               element -> facet table);  eta_e^r = (vol + jump) + neu.
-//   Totals, through norms::combine: sum vol | sum jump | sum neu | max_e eta_e^r | max |J_Fj|.
+//   Totals, through reduce::combine: sum vol | sum jump | sum neu | max_e eta_e^r | max |J_Fj|.
 //   A non-finite Sigma, f or h, or an exponent that is not a finite real >= 1, makes the term it feeds NaN, and with it the
 //   numbers of the element and the totals; the maxima are NaN-sticky.
 // The arithmetic is kept as written (fp contract off), as energy.hpp's is.
@@ -25,11 +25,8 @@
 namespace mgb {
 namespace estimate {
 
-constexpr int kCols = 5;      // MGB_ESTIMATE_COLS
+using namespace reduce;       // kCols (MGB_ESTIMATE_COLS), kThreads, combine, nanmax
 constexpr int kParts = 3;     // vol, jump, neu
-static_assert(kCols == norms::kCols, "norms::combine takes three sums, then two NaN-sticky maxima: the columns of this module");
-using norms::combine;
-using norms::nanmax;
 using norms::powq;
 
 struct Args {
@@ -58,6 +55,7 @@ struct Args {
   const int* elem_facet = nullptr;         // nel x nlf: interior facet, or -1 - boundary facet
 };
 
+// every column is a sum or a maximum of non-negative values: zeros, which hides reduce::identity and its -inf
 MGB_HD void identity(double* c) { c[0] = c[1] = c[2] = c[3] = c[4] = 0.0; }
 
 MGB_HD double exponent(const Args& A, int i) { return A.p_nodal ? A.p_nodal[i] : A.p; }
@@ -251,7 +249,6 @@ inline void field_flux_host(int dim, int k, const energy::Args& E, const double*
 }
 
 // grouping of the two launches: whole facets and whole elements per workgroup
-constexpr int kThreads = 256;
 inline int facets_launched(const Args& A) { return A.nif + (A.h ? A.nf : 0); }
 inline long long facet_workgroups(int facets, int q) {
   const int fpw = kThreads / q;
@@ -265,11 +262,14 @@ inline long long element_workgroups(int nel, int block) {
 inline size_t scratch_doubles(int nel, int block, int facets, int q) {
   return (size_t)element_workgroups(nel, block) * kCols + (size_t)facet_workgroups(facets, q) + kCols;
 }
+inline size_t results_offset(int nel, int block, int facets, int q) {
+  return (size_t)element_workgroups(nel, block) * kCols + (size_t)facet_workgroups(facets, q);
+}
 
 #if defined(__HIPCC__)
 // estimate.hip: up to three launches on `stream` behind the flux launch that wrote A.sigma -- facet_terms_kernel (left out when
 // there is no facet), element_indicator_kernel, estimate_finish.  All pointers are device pointers; J: nif, N: nf (read only
-// where A.h is set), eta: nel x kParts; the kCols results are the last kCols doubles of scratch (scratch_doubles)
+// where A.h is set), eta: nel x kParts; the kCols results are at scratch + results_offset
 void launch_estimate(hipStream_t stream, int dim, int k, const Args& A, double* J, double* N, double* eta, double* scratch);
 #endif
 

@@ -10,11 +10,12 @@
 // Per column five contributions: w d | w |d|^q | w |grad d|_2^q | |d| | |grad d|_2 (three sums, two maxima).
 #pragma once
 #include "interp.hpp"
+#include "reduce.hpp"
 
 namespace mgb {
 namespace norms {
 
-constexpr int kCols = 5;                      // MGB_NORM_COLS
+using namespace reduce;                       // kCols (MGB_NORM_COLS), kThreads, combine, workgroups
 constexpr double kTheta = 1.0 / 1048576.0;    // 2^-20
 
 struct Args {
@@ -30,22 +31,11 @@ struct Args {
   double q = 2.0;
 };
 
-// the larger of m and v where a NaN, once seen, stays
-MGB_HD double nanmax(double m, double v) { return ((v > m) | (v != v)) ? v : m; }
-
 // a^q for a >= 0 (or NaN, which it returns): no pow for q = 2 and q = 1, zero for a = 0
 MGB_HD double powq(double a, double q) {
   if (q == 2.0) return a * a;
   if (q == 1.0) return a;
   return a == 0.0 ? 0.0 : pow(a, q);
-}
-
-MGB_HD void combine(double* acc, const double* c) {
-  acc[0] += c[0];
-  acc[1] += c[1];
-  acc[2] += c[2];
-  acc[3] = nanmax(acc[3], c[3]);
-  acc[4] = nanmax(acc[4], c[4]);
 }
 
 template <int DIM, int K>
@@ -156,16 +146,16 @@ inline void field_norms_host(int dim, int k, const Args& A, double* out, long lo
   interp::dispatch(dim, k, h);
 }
 
-// number of workgroups of the partials launch and the doubles / counters of scratch the two launches need
-constexpr int kThreads = 256;
-inline long long workgroups(int n) { return ((long long)n + kThreads - 1) / kThreads; }
+// the doubles / counters of scratch the two launches need, and where the finish leaves its results in them
 inline size_t scratch_doubles(int n, int S) { return (size_t)(workgroups(n) + 1) * S * kCols; }      // partials, then S x kCols results
+inline size_t results_offset(int n, int S) { return (size_t)workgroups(n) * S * kCols; }
 inline size_t scratch_counts(int n) { return (size_t)workgroups(n) + 1; }                            // partials, then the total
+inline size_t count_offset(int n) { return (size_t)workgroups(n); }
 
 #if defined(__HIPCC__)
-// norms.hip: two launches on `stream` (partials per workgroup and column, then one workgroup that combines them in ascending
-// workgroup order); all pointers are device pointers; the S x kCols results are at scratch + workgroups * S * kCols, the
-// count of outside nodes at counts + workgroups
+// norms.hip: two launches on `stream` (partials per workgroup and column, then the finish of reduce.hpp, one workgroup per
+// column); all pointers are device pointers; the S x kCols results are at scratch + results_offset, the count of outside
+// nodes at counts + count_offset
 void launch_field_norms(hipStream_t stream, int dim, int k, const Args& A, double* scratch, long long* counts);
 #endif
 

@@ -4,16 +4,13 @@
 // written: `#pragma clang fp contract(off)` keeps a product and the sum behind it from fusing into one fma.
 #include "parabolic.hpp"
 
+#include <cmath>
+
 #include "errors.hpp"
-#include "norms.hpp"
 
 namespace mgb {
 namespace parabolic {
 namespace {
-
-static_assert(kThreads == 256, "four waves of 64");
-constexpr int kWaves = kThreads / 64;
-using norms::nanmax;
 
 __global__ void __launch_bounds__(kThreads) cost_kernel(int n, int K, double h, double c_s1, double c_s2, const double* __restrict__ f,
                                                         const double* __restrict__ z, double* __restrict__ c) {
@@ -33,28 +30,6 @@ __global__ void __launch_bounds__(kThreads) boundary_kernel(int nb, const int* _
   if (j < nb) z[bidx[j]] = gb[j];
 }
 
-// the two maxima over the workgroup (NaN-sticky); valid in thread 0
-__device__ inline void block_max2(double& a, double& b, double (*red)[2]) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a = nanmax(a, __shfl_down(a, o, 64));
-    b = nanmax(b, __shfl_down(b, o, 64));
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    red[wave][0] = a;
-    red[wave][1] = b;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int v = 1; v < kWaves; ++v) {
-      a = nanmax(a, red[v][0]);
-      b = nanmax(b, red[v][1]);
-    }
-  }
-}
-
 __device__ inline bool finite(double v) { return (v - v) == 0.0; }
 
 __global__ void __launch_bounds__(kThreads) violations_kernel(int n, int K, double half_p, const double* __restrict__ z,
@@ -63,46 +38,41 @@ __global__ void __launch_bounds__(kThreads) violations_kernel(int n, int K, doub
   __shared__ double red[kWaves][2];
   const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
   // idle threads of the last workgroup stay for the reduction and contribute the identity of max
-  double v1 = -HUGE_VAL, v2 = -HUGE_VAL;
+  double v[2] = {-HUGE_VAL, -HUGE_VAL};
   if (i < n) {
     const double u = z[i], s1 = z[(size_t)n + i], s2 = z[(size_t)2 * n + i];
     const double* row = Dz0 + (size_t)i * K;
     double gs = 0.0;
     for (int d = 1; d < K - 2; ++d) gs = gs + row[d] * row[d];
     if (finite(u) && finite(s1) && finite(s2) && finite(gs)) {
-      v1 = u * u - s1;
+      v[0] = u * u - s1;
       const double gp = half_p == 1.0 ? gs : (half_p == 0.5 ? sqrt(gs) : (gs == 0.0 ? 0.0 : pow(gs, half_p)));
-      v2 = gp - s2;
+      v[1] = gp - s2;
     } else {
-      v1 = v2 = NAN;
+      v[0] = v[1] = NAN;
     }
   }
-  block_max2(v1, v2, red);
+  block_reduce<2>(v, NanMax<2>{}, red);
   if (threadIdx.x == 0) {
-    partials[(size_t)blockIdx.x * 2] = v1;
-    partials[(size_t)blockIdx.x * 2 + 1] = v2;
+    partials[(size_t)blockIdx.x * 2] = v[0];
+    partials[(size_t)blockIdx.x * 2 + 1] = v[1];
   }
 }
 
 __device__ inline double lift_of(double v) { return v != v ? v : (v >= 0.0 ? 1.0 + v : 0.0); }
 
-// one workgroup: thread t combines the t-th contiguous run of partial pairs, then the same tree; out = v1, v2, lift_1, lift_2
+// one workgroup finishes the partial pairs (reduce.hpp); out = v1, v2, lift_1, lift_2
 __global__ void __launch_bounds__(kThreads) violations_finish(const double* __restrict__ partials, int nwg, double* __restrict__ out) {
   __shared__ double red[kWaves][2];
-  const int chunk = (nwg + kThreads - 1) / kThreads;
-  const long long b0 = (long long)threadIdx.x * chunk;
-  const long long b1 = b0 + chunk < nwg ? b0 + chunk : nwg;
-  double v1 = -HUGE_VAL, v2 = -HUGE_VAL;
-  for (long long b = b0; b < b1; ++b) {
-    v1 = nanmax(v1, partials[(size_t)b * 2]);
-    v2 = nanmax(v2, partials[(size_t)b * 2 + 1]);
-  }
-  block_max2(v1, v2, red);
+  const Run r = run_of(threadIdx.x, nwg);
+  double v[2] = {-HUGE_VAL, -HUGE_VAL};
+  for (long long b = r.b0; b < r.b1; ++b) NanMax<2>{}(v, partials + (size_t)b * 2);
+  block_reduce<2>(v, NanMax<2>{}, red);
   if (threadIdx.x == 0) {
-    out[0] = v1;
-    out[1] = v2;
-    out[2] = lift_of(v1);
-    out[3] = lift_of(v2);
+    out[0] = v[0];
+    out[1] = v[1];
+    out[2] = lift_of(v[0]);
+    out[3] = lift_of(v[1]);
   }
 }
 

@@ -6,25 +6,20 @@
 //               c[i, K-1] = 1 / p, zero elsewhere;
 //   boundary    u[bidx[j]] = gb[j] (a launch of its own BEHIND the cost, which reads the old boundary values);
 //   violations  after Dz0 = D z:  v1 = max_i (u_i^2 - s1_i),  v2 = max_i ((sum_d g_id^2)^(p/2) - s2_i),  g = columns 1..dim of Dz0;
-//               a node with a non-finite u, g, s1 or s2 contributes NaN and a NaN, once seen, stays (norms.hpp: nanmax);
+//               a node with a non-finite u, g, s1 or s2 contributes NaN and a NaN, once seen, stays (reduce.hpp: nanmax);
 //   lifts       lift_j = 1 + v_j if v_j >= 0, exactly 0 if v_j < 0, NaN if v_j is NaN;  s_j += lift_j at every node (a constant
 //               shift: the slacks stay in the `full` space); a column whose lift is 0 is not written at all;
 //   snapshot    out[i * S + s] = z[s * n + i] (row-major n x S).
-// The maxima are reduced as norms.hip reduces its own: wave shuffles, LDS across the four waves, one partial pair per
-// workgroup, then ONE workgroup that combines the partials in ascending order -- no atomics, no hand-off inside a launch.
+// The maxima are reduced by the two-stage scheme of reduce.hpp: one partial pair per workgroup, then ONE workgroup that combines
+// the partials in ascending order and computes the lifts.
 #pragma once
-#include <cstddef>
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#endif
+#include "reduce.hpp"
 
 namespace mgb {
 namespace parabolic {
 
-constexpr int kThreads = 256;
+using namespace reduce;          // kThreads, workgroups, nanmax
 constexpr int kResults = 4;      // v1, v2, lift_1, lift_2
-inline long long workgroups(int n) { return ((long long)n + kThreads - 1) / kThreads; }
 // one (v1, v2) pair per workgroup, then the kResults results
 inline size_t scratch_doubles(int n) { return (size_t)workgroups(n) * 2 + kResults; }
 inline size_t results_offset(int n) { return (size_t)workgroups(n) * 2; }
