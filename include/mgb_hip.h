@@ -664,6 +664,20 @@ int mgb_plan_chol_bwd_fused(mgb_plan p, int dim, int cut, int top_nf, int thread
 int mgb_plan_chol_premap(mgb_plan p, int dim, int leaf, int single, int mode, int tiles, long long* info, int cap_nodes, int* height,
                          int* producer, long long* soff, long long* eoff, int* fofs, int* iofs, int cap_heights, int* hkind, int* hwg,
                          int* hconsumer, int cap_fwd, int* fwd, int cap_pinv, int* pinv);
+/* host-only: the whole plan of the device chain (csrc/chol_plan.hpp, plan_chain) for this level's tree: every launch and
+ * every job, as GpuChol::build would upload them.  knobs (nullable: the values this process reads from the environment):
+ * 16 ints in CholKnobs order -- graph, prof, leaf, single, step2, wide, start_pivot, step2_tiles, dense_tiles,
+ * bwd_split_nf, bwd_fused, bwd_cut, bwd_fused_nf, bwd_fused_threads, premap, premap_tiles.  world / rank: the subtree
+ * split (1, 0: the unsplit chain).  info[10] = launches, first own backward launch, first top launch, list entries,
+ * start jobs, tiles, single tiles, rect jobs, assembly entries, world the tree was split over (1: not splittable).
+ * launch: 10 ints per launch -- kind (codes of mgb_amg_chol_schedule), job offset, job count (= workgroups), block size,
+ * LDS bytes, first panel p, leading pivot jobs npiv, rect, pre-map consumer flag, pre-map producers.  lists: the node
+ * lists (Leaf, Bwd*); starts: node, chunk, rb (-1: pivot job), a0, a1 per job; tiles / singles: node, ti, tj per job;
+ * rects: node, chunk per job; apos / asrc (cap_asm each): the assembly lists.  Each array is nullable and filled up to
+ * its capacity. */
+int mgb_plan_chol_schedule(mgb_plan p, int dim, const int* knobs, int world, int rank, int* info, int cap_launch, int* launch,
+                           int cap_lists, int* lists, int cap_starts, int* starts, int cap_tiles, int* tiles, int cap_singles,
+                           int* singles, int cap_rects, int* rects, int cap_asm, int* apos, int* asrc);
 int mgb_chol_selftest(int nx, int ny, double* max_residual, double* flops, double* seconds);
 /* test hook: the finish launch of the two-stage field reductions (csrc/reduce.hpp) alone, on the context's stream.
  * partials_host: rows x nwg x 5 (three sums, two NaN-sticky maxima per partial); out_host: rows x 5. */

@@ -192,6 +192,8 @@ PROTOTYPES = {
                                 c_int_p, c_int_p],
     "mgb_plan_chol_premap": [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ll_p, C.c_int, c_int_p, c_int_p, c_ll_p, c_ll_p, c_int_p,
                              c_int_p, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int, c_int_p, C.c_int, c_int_p],
+    "mgb_plan_chol_schedule": [H, C.c_int, c_int_p, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p, C.c_int, c_int_p, C.c_int, c_int_p,
+                               C.c_int, c_int_p, C.c_int, c_int_p, C.c_int, c_int_p, C.c_int, c_int_p, c_int_p],
     "mgb_chol_selftest": [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_reduce_selftest": [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p],
 }

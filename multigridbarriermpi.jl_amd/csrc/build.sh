@@ -30,6 +30,7 @@ compile "$HERE/_obj/geometry.o" "$HERE/geometry.cpp" g++ $CXXFLAGS
 compile "$HERE/_obj/mfchol.o" "$HERE/mfchol.cpp" g++ $CXXFLAGS
 compile "$HERE/_obj/bwd_fused.o" "$HERE/bwd_fused.cpp" g++ $CXXFLAGS
 compile "$HERE/_obj/chol_premap.o" "$HERE/chol_premap.cpp" g++ $CXXFLAGS
+compile "$HERE/_obj/chol_plan.o" "$HERE/chol_plan.cpp" g++ $CXXFLAGS
 compile "$HERE/_obj/kernels.o" "$HERE/kernels.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/kernels_f32.o" "$HERE/kernels_f32.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/mg.o" "$HERE/mg.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
@@ -49,5 +50,5 @@ for pid in "${pids[@]}"; do
   wait "$pid" || { echo "build.sh: a compile job failed" >&2; exit 1; }
 done
 rm -f "$OUT/libmgb_hip.so"
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,chol_premap,kernels,kernels_f32,mg,interp,reduce,norms,energy,boundary,estimate,parabolic,gpuchol,amg,amg_mg,comm,capi}.o -lpthread -ldl
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,chol_premap,chol_plan,kernels,kernels_f32,mg,interp,reduce,norms,energy,boundary,estimate,parabolic,gpuchol,amg,amg_mg,comm,capi}.o -lpthread -ldl
 echo "built $OUT/libmgb_hip.so"

@@ -1,51 +1,31 @@
+// Host tables of the fused backward sweep (see bwd_fused.hpp).  Host-compilable: no HIP.
 #include "bwd_fused.hpp"
 
 #include <algorithm>
 
+#include "chol_plan.hpp"
 #include "errors.hpp"
 
 namespace mgb {
 
 namespace {
-constexpr int PB = 32;
 int round64(int v) { return (v + 63) & ~63; }
 }  // namespace
 
-FusedPlan plan_bwd_fused(const std::vector<int>& ns, const std::vector<int>& first, const std::vector<int>& parent,
-                         const std::vector<const std::vector<int>*>& bdry, const FusedKnobs& kn) {
+FusedPlan plan_bwd_fused(const CholTree& T, const FusedKnobs& kn) {
   FusedPlan P;
-  const int n = (int)ns.size();
+  const int n = T.size(), nheights = T.nheights;
+  const std::vector<int>&ns = T.ns, &nf = T.nf, &first = T.first, &parent = T.parent, &height = T.height, &bofs = T.bofs;
+  const std::vector<long long>&off = T.off, &loff = T.loff;
   if (kn.threads < 64 || kn.threads > 512 || (kn.threads & (kn.threads - 1))) throw ArgError("gpuchol: fused backward sweep: bad thread count");
   P.threads = kn.threads;
-  P.height.assign(n, 0);
-  P.bofs.assign(n, 0);
-  std::vector<long long> off(n), loff(n);
-  std::vector<int> nf(n);
-  {
-    long long o = 0, lo = 0;
-    int b = 0;
-    for (int t = 0; t < n; ++t) {      // the layout of GpuChol::build
-      nf[t] = ns[t] + (int)bdry[t]->size();
-      off[t] = o;
-      loff[t] = lo;
-      P.bofs[t] = b;
-      o += (long long)(nf[t] + 1) * (nf[t] + 1);
-      lo += (long long)((ns[t] + PB - 1) / PB) * 2 * PB * PB;
-      b += (int)bdry[t]->size();
-      if (parent[t] >= 0) {
-        if (parent[t] <= t) throw InternalError("gpuchol: elimination tree is not in postorder");
-        P.height[parent[t]] = std::max(P.height[parent[t]], P.height[t] + 1);
-      }
-    }
-    P.slots.assign(b, -1);
-  }
+  P.slots.assign(T.bdry_total, -1);
   if (n == 0) return P;
-  P.nheights = *std::max_element(P.height.begin(), P.height.end()) + 1;
-  std::vector<int> hmax(P.nheights, 0);
-  for (int t = 0; t < n; ++t) hmax[P.height[t]] = std::max(hmax[P.height[t]], nf[t]);
+  std::vector<int> hmax(nheights, 0);
+  for (int t = 0; t < n; ++t) hmax[height[t]] = std::max(hmax[height[t]], nf[t]);
   // h_top: the heights below the first one that holds a front too large to repeat
   int h_top = -1;
-  while (h_top + 1 < P.nheights && (kn.top_nf <= 0 || hmax[h_top + 1] <= kn.top_nf)) ++h_top;
+  while (h_top + 1 < nheights && (kn.top_nf <= 0 || hmax[h_top + 1] <= kn.top_nf)) ++h_top;
   if (h_top < 0) return P;
   // h_cut: the knob, raised until the subtrees are no more than the workgroups the chip runs at once (a workgroup of
   // this kernel fills a CU: a second round would repeat every path) -- by at most max_raise heights.  A tree that needs
@@ -54,7 +34,7 @@ FusedPlan plan_bwd_fused(const std::vector<int>& ns, const std::vector<int>& fir
   int h_cut = std::min(std::max(kn.cut, 0), h_top);
   auto count_roots = [&](int c) {
     int k = 0;
-    for (int t = 0; t < n; ++t) k += P.height[t] <= c && (parent[t] < 0 || P.height[parent[t]] > c);
+    for (int t = 0; t < n; ++t) k += height[t] <= c && (parent[t] < 0 || height[parent[t]] > c);
     return k;
   };
   if (kn.max_wg > 0) {
@@ -66,8 +46,8 @@ FusedPlan plan_bwd_fused(const std::vector<int>& ns, const std::vector<int>& fir
   for (int t = 0; t < n; ++t)
     if (parent[t] >= 0) minfirst[parent[t]] = std::min(minfirst[parent[t]], minfirst[t]);
   for (int t = n - 1; t >= 0; --t) {      // parents first
-    if (P.height[t] > h_cut) continue;
-    if (parent[t] >= 0 && P.height[parent[t]] <= h_cut) root_of[t] = root_of[parent[t]];
+    if (height[t] > h_cut) continue;
+    if (parent[t] >= 0 && height[parent[t]] <= h_cut) root_of[t] = root_of[parent[t]];
     else root_of[t] = t;
   }
   for (int t = 0; t < n; ++t)
@@ -88,8 +68,8 @@ FusedPlan plan_bwd_fused(const std::vector<int>& ns, const std::vector<int>& fir
     base[t] = above[r] + first[t] - minfirst[r];
   }
   for (int t = 0; t < n; ++t) {
-    if (P.height[t] > h_top) continue;
-    const std::vector<int>& bd = *bdry[t];
+    if (height[t] > h_top) continue;
+    const std::vector<int>& bd = *T.bdry[t];
     int a = parent[t];
     for (size_t i = 0; i < bd.size(); ++i) {      // ascending: walk up the ancestors once
       while (a >= 0 && !(bd[i] >= first[a] && bd[i] < first[a] + ns[a])) a = parent[a];
@@ -99,12 +79,12 @@ FusedPlan plan_bwd_fused(const std::vector<int>& ns, const std::vector<int>& fir
         if (a < 0) throw InternalError("gpuchol: boundary entry outside the ancestors");
       }
       const int ab = (root_of[a] >= 0) ? base[a] : above[a];
-      P.slots[P.bofs[t] + i] = ab + bd[i] - first[a];
+      P.slots[bofs[t] + i] = ab + bd[i] - first[a];
     }
   }
   // the order of additions of the per-height launches: thread count and rectangular split of each height
   auto nsl_rect = [&](int t) {
-    const int h = P.height[t], nb = nf[t] - ns[t];
+    const int h = height[t], nb = nf[t] - ns[t];
     if (nb == 0 || ns[t] == 0) return 0;
     if (hmax[h] > kn.split_nf) return 1024 / 64;      // backward_rect_kernel: 1 024 threads, 64-column chunks
     const int nt = hmax[h] > 384 ? 1024 : 256;
@@ -130,13 +110,13 @@ FusedPlan plan_bwd_fused(const std::vector<int>& ns, const std::vector<int>& fir
     std::reverse(anc.begin(), anc.end());
     std::vector<int> ab;
     for (int a : anc)
-      if (P.height[a] > h_top) ab.push_back(a);
+      if (height[a] > h_top) ab.push_back(a);
     if (!ab.empty()) {
       R.levels.push_back(ab);
       R.first_solve = 1;
     }
     for (int a : anc)
-      if (P.height[a] <= h_top) R.levels.push_back({a});
+      if (height[a] <= h_top) R.levels.push_back({a});
     R.sub_level = (int)R.levels.size();
     std::vector<int> cur{r};
     while (!cur.empty()) {
@@ -184,11 +164,11 @@ FusedPlan plan_bwd_fused(const std::vector<int>& ns, const std::vector<int>& fir
         j[FJ_FIRST] = first[t];
         j[FJ_NF] = nf[t];
         j[FJ_NS] = ns[t];
-        j[FJ_SOFS] = P.bofs[t];
+        j[FJ_SOFS] = bofs[t];
         j[FJ_BASE] = base[t];
         j[FJ_LSOFS] = sl;
         j[FJ_NSL] = nsl;
-        j[FJ_NT] = hmax[P.height[t]] > 384 ? 1024 : 256;
+        j[FJ_NT] = hmax[height[t]] > 384 ? 1024 : 256;
         j[FJ_FLAGS] = flags;
         j[FJ_NODE] = t;
         if (solve) {

@@ -1,4 +1,5 @@
-// Host tables of the fused backward sweep of the device Cholesky (backward_fused_kernel, gpuchol.hip).
+// Host tables of the fused backward sweep of the device Cholesky (backward_fused_kernel, gpuchol.hip): plan_bwd_fused, called
+// by plan_chain (chol_plan.hpp) and by the host-only mgb_plan_chol_bwd_fused, on the tree view and front layout they share.
 //
 // A front of the backward sweep L'x = u needs only the solution entries of its ancestors.  So the elimination tree is
 // cut at a height h_cut: every maximal subtree of height <= h_cut gets ONE workgroup, which first solves the fronts on
@@ -16,6 +17,8 @@
 #include <vector>
 
 namespace mgb {
+
+struct CholTree;
 
 struct FusedKnobs {
   int cut = 2;         // h_cut: subtree height (heights above the leaves) ...
@@ -46,7 +49,7 @@ enum FusedJobField {                // ints of a job
 };
 
 struct FusedPlan {
-  int h_top = -1, h_cut = -1, nwg = 0, nheights = 0;
+  int h_top = -1, h_cut = -1, nwg = 0;
   int wstride = 0;      // ints per workgroup record (even)
   int max_levels = 0;
   int xs_cap = 0, sl_cap = 0, red_cap = 0;      // LDS: solution vector / reduction scratch (doubles), staged slot lists (ints)
@@ -54,13 +57,10 @@ struct FusedPlan {
   size_t lds_bytes = 0;
   std::vector<int> wg;       // nwg records
   std::vector<int> slots;    // parallel to the concatenated boundary lists
-  std::vector<int> bofs;     // per node: offset of its boundary list
-  std::vector<int> height;   // per node
   bool enabled() const { return nwg > 0; }
 };
 
-// ns / first / parent per node (postorder), bdry: the nodes' boundary lists (new indices)
-FusedPlan plan_bwd_fused(const std::vector<int>& ns, const std::vector<int>& first, const std::vector<int>& parent,
-                         const std::vector<const std::vector<int>*>& bdry, const FusedKnobs& kn);
+// T: the tree view with the front layout the job records quote (chol_plan.hpp)
+FusedPlan plan_bwd_fused(const CholTree& T, const FusedKnobs& kn);
 
 }  // namespace mgb

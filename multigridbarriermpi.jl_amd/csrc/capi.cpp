@@ -2097,25 +2097,23 @@ int mgb_plan_chol_bwd_fused(mgb_plan p, int dim, int cut, int top_nf, int thread
     need(p && info, "chol_bwd_fused: bad arguments");
     MfChol ch;
     ch.analyze(p->plan.Apat, p->plan.coords.data(), dim);
-    std::vector<int> ns, fi, par, bd;
-    std::vector<const std::vector<int>*> lists;
-    ch.bwd_tables(ns, fi, par, lists);
-    FusedKnobs kn;
+    const CholTree T = ch.view();
+    FusedKnobs kn = fused_knobs(GpuChol::knobs());
     kn.cut = cut;
     kn.top_nf = top_nf;
     kn.threads = threads;
-    kn.split_nf = GpuChol::knobs().bwd_split_nf;
-    const FusedPlan P = plan_bwd_fused(ns, fi, par, lists, kn);
-    for (const std::vector<int>* l : lists) bd.insert(bd.end(), l->begin(), l->end());
+    const FusedPlan P = plan_bwd_fused(T, kn);
+    std::vector<int> bd;
+    for (const std::vector<int>* l : T.bdry) bd.insert(bd.end(), l->begin(), l->end());
     const int v[12] = {P.h_top, P.h_cut, P.nwg, P.wstride, P.max_levels, P.xs_cap, P.red_cap, P.sl_cap, (int)P.lds_bytes,
-                       (int)bd.size(), (int)ns.size(), P.nheights};
+                       (int)bd.size(), T.size(), T.nheights};
     std::copy(v, v + 12, info);
     if (wg) std::copy(P.wg.begin(), P.wg.begin() + std::min<size_t>(cap_wg, P.wg.size()), wg);
-    const size_t mb = std::min<size_t>(cap_bdry, bd.size()), mn = std::min<size_t>(cap_nodes, ns.size());
+    const size_t mb = std::min<size_t>(cap_bdry, bd.size()), mn = std::min<size_t>(cap_nodes, T.size());
     if (bdry) std::copy(bd.begin(), bd.begin() + mb, bdry);
     if (slots) std::copy(P.slots.begin(), P.slots.begin() + mb, slots);
-    if (bofs) std::copy(P.bofs.begin(), P.bofs.begin() + mn, bofs);
-    if (first) std::copy(fi.begin(), fi.begin() + mn, first);
+    if (bofs) std::copy(T.bofs.begin(), T.bofs.begin() + mn, bofs);
+    if (first) std::copy(T.first.begin(), T.first.begin() + mn, first);
   });
 }
 
@@ -2126,19 +2124,17 @@ int mgb_plan_chol_premap(mgb_plan p, int dim, int leaf, int single, int mode, in
     need(p && info, "chol_premap: bad arguments");
     MfChol ch;
     ch.analyze(p->plan.Apat, p->plan.coords.data(), dim);
-    std::vector<int> ns, nf, par, c0, c1;
-    std::vector<const std::vector<int>*> ea;
-    ch.premap_tables(ns, nf, par, c0, c1, ea);
-    PremapKnobs kn = GpuChol::premap_knobs();
+    const CholTree T = ch.view();
+    CholKnobs kn = GpuChol::knobs();
     kn.leaf = leaf != 0;
     kn.single = single != 0;
-    kn.mode = mode;
-    kn.tiles = tiles;
-    const PremapPlan P = plan_premap(ns, nf, par, c0, c1, ea, kn);
-    const long long v[5] = {(long long)ns.size(), P.nheights, (long long)P.fwd.size(), (long long)P.pinv.size(), P.slab_doubles};
+    kn.premap = mode;
+    kn.premap_tiles = tiles;
+    const PremapPlan P = plan_premap(T, kn);
+    const long long v[5] = {(long long)T.size(), T.nheights, (long long)P.fwd.size(), (long long)P.pinv.size(), P.slab_doubles};
     std::copy(v, v + 5, info);
-    const size_t mn = std::min<size_t>(std::max(cap_nodes, 0), ns.size()), mh = std::min<size_t>(std::max(cap_heights, 0), P.nheights);
-    if (height) std::copy(P.height.begin(), P.height.begin() + mn, height);
+    const size_t mn = std::min<size_t>(std::max(cap_nodes, 0), T.size()), mh = std::min<size_t>(std::max(cap_heights, 0), T.nheights);
+    if (height) std::copy(T.height.begin(), T.height.begin() + mn, height);
     if (producer) std::copy(P.producer.begin(), P.producer.begin() + mn, producer);
     if (soff) std::copy(P.soff.begin(), P.soff.begin() + 2 * mn, soff);
     if (eoff) std::copy(P.eoff.begin(), P.eoff.begin() + mn, eoff);
@@ -2149,6 +2145,61 @@ int mgb_plan_chol_premap(mgb_plan p, int dim, int leaf, int single, int mode, in
     if (hconsumer) std::copy(P.hconsumer.begin(), P.hconsumer.begin() + mh, hconsumer);
     if (fwd) std::copy(P.fwd.begin(), P.fwd.begin() + std::min<size_t>(std::max(cap_fwd, 0), P.fwd.size()), fwd);
     if (pinv) std::copy(P.pinv.begin(), P.pinv.begin() + std::min<size_t>(std::max(cap_pinv, 0), P.pinv.size()), pinv);
+  });
+}
+
+int mgb_plan_chol_schedule(mgb_plan p, int dim, const int* knobs, int world, int rank, int* info, int cap_launch, int* launch,
+                           int cap_lists, int* lists, int cap_starts, int* starts, int cap_tiles, int* tiles, int cap_singles,
+                           int* singles, int cap_rects, int* rects, int cap_asm, int* apos, int* asrc) {
+  return guard([&] {
+    need(p && info && world >= 1 && rank >= 0 && rank < world, "chol_schedule: bad arguments");
+    MfChol ch;
+    ch.analyze(p->plan.Apat, p->plan.coords.data(), dim);
+    CholKnobs kn = GpuChol::knobs();
+    if (knobs) {
+      const int* k = knobs;
+      kn = CholKnobs{k[0] != 0, k[1] != 0, k[2] != 0, k[3] != 0, k[4] != 0, k[5] != 0, k[6] != 0, k[7], k[8], k[9], k[10] != 0, k[11],
+                     k[12], k[13], k[14], k[15]};
+    }
+    const CholPartition part = world > 1 ? ch.partition(world) : CholPartition();
+    const ChainPlan P = plan_chain(ch.view(), part, rank, kn);
+    const int v[10] = {(int)P.chain.size(), P.own_bwd, P.top_fwd, (int)P.lists.size(), (int)P.starts.size(), (int)P.tiles.size(),
+                       (int)P.singles.size(), (int)P.rects.size(), (int)P.asrc.size(), part.world};
+    std::copy(v, v + 10, info);
+    const auto upto = [](int cap, size_t n) { return std::min<size_t>(std::max(cap, 0), n); };
+    if (launch)
+      for (size_t i = 0; i < upto(cap_launch, P.chain.size()); ++i) {
+        const Launch& L = P.chain[i];
+        const int r[10] = {(int)L.kind, L.ofs, L.cnt, L.block, (int)L.lds, L.p, L.npiv, L.rect ? 1 : 0, L.premap ? 1 : 0, L.nproducers};
+        std::copy(r, r + 10, launch + 10 * i);
+      }
+    if (lists) std::copy(P.lists.begin(), P.lists.begin() + upto(cap_lists, P.lists.size()), lists);
+    if (starts)
+      for (size_t i = 0; i < upto(cap_starts, P.starts.size()); ++i) {
+        const StartJob& j = P.starts[i];
+        const int r[5] = {j.node, j.chunk, j.rb, j.a0, j.a1};
+        std::copy(r, r + 5, starts + 5 * i);
+      }
+    if (tiles)
+      for (size_t i = 0; i < upto(cap_tiles, P.tiles.size()); ++i) {
+        const int r[3] = {P.tiles[i].pad, P.tiles[i].ti, P.tiles[i].tj};
+        std::copy(r, r + 3, tiles + 3 * i);
+      }
+    if (singles)
+      for (size_t i = 0; i < upto(cap_singles, P.singles.size()); ++i) {
+        const SingleTile& u = P.singles[i];
+        // a single tile names its front by offset: fronts are laid out in node order
+        const auto g = std::lower_bound(P.nodes.begin(), P.nodes.end(), u.off, [](const GNode& a, long long o) { return a.off < o; });
+        const int r[3] = {(int)(g - P.nodes.begin()), u.ti, u.tj};
+        std::copy(r, r + 3, singles + 3 * i);
+      }
+    if (rects)
+      for (size_t i = 0; i < upto(cap_rects, P.rects.size()); ++i) {
+        rects[2 * i] = P.rects[i].node;
+        rects[2 * i + 1] = P.rects[i].chunk;
+      }
+    if (apos) std::copy(P.apos.begin(), P.apos.begin() + upto(cap_asm, P.apos.size()), apos);
+    if (asrc) std::copy(P.asrc.begin(), P.asrc.begin() + upto(cap_asm, P.asrc.size()), asrc);
   });
 }
 

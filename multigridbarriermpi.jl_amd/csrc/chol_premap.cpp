@@ -3,15 +3,20 @@
 
 #include <algorithm>
 
+#include "chol_plan.hpp"
 #include "errors.hpp"
 
 namespace mgb {
 
-namespace {
-constexpr int PB = 32, TS = 64, TB = 256;      // panel width, tile, threads per workgroup (gpuchol.hip)
+void HeightShape::add(int ns, int nf, bool has_child) {
+  max_ns = std::max(max_ns, ns);
+  max_nf = std::max(max_nf, nf);
+  childless = childless && !has_child;
+  all_pivots = all_pivots && ns >= 1;      // a pass-through front (ns = 0) needs front_start to copy it
+  one_tile = one_tile && nf + 1 - std::min(ns, PB) <= TS;      // the trailing matrix after the first panel is one 64-row tile
 }
 
-int HeightShape::kind(const PremapKnobs& kn) const {
+int HeightShape::kind(const CholKnobs& kn) const {
   // leaf heights with small fronts: the whole front in one workgroup (front_leaf_kernel).  nf <= 95 alone is not enough:
   // a narrow leaf with a wide boundary (3-D trees under a small MGB_LEAF: ns = 16, nf = 88) has more trailing rows than
   // the kernel's one tile, and the rows past it were never updated
@@ -21,16 +26,10 @@ int HeightShape::kind(const PremapKnobs& kn) const {
   return PH_START;
 }
 
-PremapPlan plan_premap(const std::vector<int>& ns, const std::vector<int>& nf, const std::vector<int>& parent,
-                       const std::vector<int>& child0, const std::vector<int>& child1, const std::vector<const std::vector<int>*>& ea,
-                       const PremapKnobs& kn) {
-  const int n = (int)ns.size();
+PremapPlan plan_premap(const CholTree& T, const CholKnobs& kn) {
+  const int n = T.size();
+  const std::vector<int>&ns = T.ns, &nf = T.nf, &parent = T.parent, &height = T.height;
   PremapPlan P;
-  P.height.assign(n, 0);
-  for (int t = 0; t < n; ++t)      // postorder: children first
-    for (int c : {child0[t], child1[t]})
-      if (c >= 0) P.height[t] = std::max(P.height[t], P.height[c] + 1);
-  P.nheights = n ? *std::max_element(P.height.begin(), P.height.end()) + 1 : 0;
   // forward maps (child boundary row -> parent front row) and their inverses
   P.fofs.assign(n, -1);
   P.pld.assign(n, 0);
@@ -38,24 +37,22 @@ PremapPlan plan_premap(const std::vector<int>& ns, const std::vector<int>& nf, c
   for (int t = 0; t < n; ++t) {
     if (parent[t] < 0) continue;
     const int nb = nf[t] - ns[t], pnf = nf[parent[t]];
-    if ((int)ea[t]->size() != nb) throw InternalError("chol_premap: ea/bdry size mismatch");
     P.fofs[t] = (int)P.fwd.size();
     P.pld[t] = pnf + 1;
     for (int a = 0; a < nb; ++a) {
-      const int e = (*ea[t])[a];
-      if (e < 0 || e >= pnf || (a > 0 && e <= (*ea[t])[a - 1])) throw InternalError("chol_premap: bad extend-add map");
+      const int e = (*T.ea[t])[a];
+      if (e < 0 || e >= pnf || (a > 0 && e <= (*T.ea[t])[a - 1])) throw InternalError("chol_premap: bad extend-add map");
       P.fwd.push_back(e);
     }
     P.fwd.push_back(pnf);      // the right-hand-side row
   }
   for (int t = 0; t < n; ++t) {
-    if (child0[t] < 0 && child1[t] < 0) continue;
+    if (T.child[0][t] < 0 && T.child[1][t] < 0) continue;
     P.iofs[t] = (int)P.pinv.size();
     P.pinv.resize(P.pinv.size() + 2 * (size_t)(nf[t] + 1), -1);
     for (int s = 0; s < 2; ++s) {
-      const int c = s ? child1[t] : child0[t];
+      const int c = T.child[s][t];
       if (c < 0) continue;
-      if (parent[c] != t) throw InternalError("chol_premap: child / parent mismatch");
       int* iv = P.pinv.data() + P.iofs[t] + (size_t)s * (nf[t] + 1);
       const int cnb = nf[c] - ns[c];
       for (int a = 0; a <= cnb; ++a) {
@@ -66,50 +63,34 @@ PremapPlan plan_premap(const std::vector<int>& ns, const std::vector<int>& nf, c
     }
   }
   // the first launch of every height: kind and workgroups
-  std::vector<HeightShape> shape(P.nheights);
-  std::vector<int> has_child(P.nheights, 0);
+  std::vector<HeightShape> shape(T.nheights);
+  for (int t = 0; t < n; ++t) shape[height[t]].add(ns[t], nf[t], T.child[0][t] >= 0 || T.child[1][t] >= 0);
+  P.hkind.assign(T.nheights, PH_START);
+  P.hwg.assign(T.nheights, 0);
+  for (int h = 0; h < T.nheights; ++h) P.hkind[h] = shape[h].kind(kn);
+  const auto count = [](int, int) {};
   for (int t = 0; t < n; ++t) {
-    HeightShape& h = shape[P.height[t]];
-    h.max_ns = std::max(h.max_ns, ns[t]);
-    h.max_nf = std::max(h.max_nf, nf[t]);
-    h.childless = h.childless && child0[t] < 0 && child1[t] < 0;
-    h.all_pivots = h.all_pivots && ns[t] >= 1;
-    h.one_tile = h.one_tile && nf[t] + 1 - std::min(ns[t], PB) <= TS;
-    if (child0[t] >= 0 || child1[t] >= 0) has_child[P.height[t]] = 1;
-  }
-  P.hkind.assign(P.nheights, PH_START);
-  P.hwg.assign(P.nheights, 0);
-  for (int h = 0; h < P.nheights; ++h) P.hkind[h] = shape[h].kind(kn);
-  for (int t = 0; t < n; ++t) {
-    const int h = P.height[t];
-    if (P.hkind[h] == PH_LEAF) {
-      P.hwg[h] += 1;
-    } else if (P.hkind[h] == PH_SINGLE) {      // the tiles of the trailing matrix behind the one panel (append_tiles)
-      const int k = ns[t], Tr = (nf[t] + 1 - k + TS - 1) / TS, Tc = std::max(1, (nf[t] - k + TS - 1) / TS);
-      for (int ti = 0; ti < Tr; ++ti) P.hwg[h] += std::min(ti, Tc - 1) + 1;
-    } else {      // front_start: 32 columns x 256 rows per job, and the pivot job
-      const int nch = (nf[t] + PB - 1) / PB;
-      if (kn.start_pivot && ns[t] > 0 && nch > 0) P.hwg[h] += 1;
-      for (int ch = 0; ch < nch; ++ch) P.hwg[h] += (nf[t] + 1 - ch * PB + TB - 1) / TB;
-    }
+    const int h = height[t];
+    if (P.hkind[h] == PH_LEAF) P.hwg[h] += 1;
+    else if (P.hkind[h] == PH_SINGLE) P.hwg[h] += for_trailing_tiles(nf[t], ns[t], count);      // behind the one panel
+    else P.hwg[h] += has_pivot_job(kn.start_pivot, ns[t]) + for_start_jobs(nf[t], count);
   }
   // the rule
-  P.hconsumer.assign(P.nheights, 0);
-  for (int h = 0; h < P.nheights; ++h) {
-    const bool kind_ok = (P.hkind[h] == PH_SINGLE && kn.mode >= 1) || (P.hkind[h] == PH_START && kn.mode >= 2);
-    P.hconsumer[h] = (kind_ok && has_child[h] && P.hwg[h] <= kn.tiles) ? 1 : 0;
+  P.hconsumer.assign(T.nheights, 0);
+  for (int h = 0; h < T.nheights; ++h) {
+    const bool kind_ok = (P.hkind[h] == PH_SINGLE && kn.premap >= 1) || (P.hkind[h] == PH_START && kn.premap >= 2);
+    P.hconsumer[h] = (kind_ok && !shape[h].childless && P.hwg[h] <= kn.premap_tiles) ? 1 : 0;
   }
   for (int t = 0; t < n; ++t)
-    for (int c : {child0[t], child1[t]})
-      if (c >= 0 && P.hkind[P.height[c]] == PH_START) P.hconsumer[P.height[t]] = 0;
+    if (parent[t] >= 0 && P.hkind[height[t]] == PH_START) P.hconsumer[height[parent[t]]] = 0;
   // slabs: one per present child of every consumer front, indexed like the front (ld x nf, lower part + row nf)
   P.producer.assign(n, 0);
   P.soff.assign(2 * (size_t)n, -1);
   P.eoff.assign(n, -1);
   for (int t = 0; t < n; ++t) {
-    if (!P.hconsumer[P.height[t]]) continue;
+    if (!P.hconsumer[height[t]]) continue;
     for (int s = 0; s < 2; ++s) {
-      const int c = s ? child1[t] : child0[t];
+      const int c = T.child[s][t];
       if (c < 0) continue;
       P.soff[2 * (size_t)t + s] = P.slab_doubles;
       P.eoff[c] = P.slab_doubles;

@@ -9,35 +9,29 @@
 // uncovered entries stay +0.0 and the parent reads child0 + child1 as E_0[p] + E_1[p] at the entry's own position: two
 // plain tile loads and one add, bitwise the gather's (x or 0.0) + (y or 0.0).
 //
-// Rule (one function, used by GpuChol::schedule and by the host-only mgb_plan_chol_premap): a height's first launch is a
-// consumer iff it is a Single* launch (mode >= 1) or a Start launch (mode >= 2), at least one of its fronts has a child,
-// every present child of every front in it is produced by a Leaf or Single* launch, and it has at most `tiles` workgroups.
-// A front is a producer iff its parent's launch is a consumer.
+// Rule (plan_premap, called by plan_chain of chol_plan.hpp and by the host-only mgb_plan_chol_premap): a height's first
+// launch is a consumer iff it is a Single* launch (MGB_CHOL_PREMAP >= 1) or a Start launch (>= 2), at least one of its fronts
+// has a child, every present child of every front in it is produced by a Leaf or Single* launch, and it has at most
+// MGB_CHOL_PREMAP_TILES workgroups.  A front is a producer iff its parent's launch is a consumer.
 #pragma once
 #include <vector>
 
 namespace mgb {
 
-struct PremapKnobs {
-  bool leaf = true;          // CholKnobs::leaf / single / start_pivot: they decide the launch kinds and workgroup counts
-  bool single = true;
-  bool start_pivot = true;
-  int mode = 0;              // MGB_CHOL_PREMAP: 0 off, 1 front_single consumers, 2 front_start consumers too
-  int tiles = 0;             // MGB_CHOL_PREMAP_TILES: largest consumer launch, in workgroups
-};
+struct CholTree;       // chol_plan.hpp: the tree view, the chain's constants and knobs
+struct CholKnobs;
 
 enum PremapHeightKind { PH_LEAF = 0, PH_SINGLE = 1, PH_START = 2 };
 
-// what schedule() decides per height before anything else: front_leaf, front_single or front_start + panel launches
+// what decides the first launch of a set of fronts of one height: front_leaf, front_single or front_start + panel launches
 struct HeightShape {
   int max_ns = 0, max_nf = 0;
   bool childless = true, all_pivots = true, one_tile = true;
-  int kind(const PremapKnobs& kn) const;      // PremapHeightKind
+  void add(int ns, int nf, bool has_child);
+  int kind(const CholKnobs& kn) const;      // PremapHeightKind
 };
 
 struct PremapPlan {
-  int nheights = 0;
-  std::vector<int> height;         // per node (leaves 0)
   std::vector<int> hkind;          // per height: PremapHeightKind
   std::vector<int> hwg;            // per height: workgroups of its first launch (Leaf: fronts, Single: tiles, Start: jobs)
   std::vector<int> hconsumer;      // per height: 1 if that launch reads the slabs
@@ -53,10 +47,7 @@ struct PremapPlan {
   bool any() const { return slab_doubles > 0; }
 };
 
-// ns / nf / parent / two child slots (-1: absent) per node in postorder; ea[t]: position of boundary entry i of node t in
-// its parent's front (ascending).  Throws InternalError on a malformed map.
-PremapPlan plan_premap(const std::vector<int>& ns, const std::vector<int>& nf, const std::vector<int>& parent,
-                       const std::vector<int>& child0, const std::vector<int>& child1, const std::vector<const std::vector<int>*>& ea,
-                       const PremapKnobs& kn);
+// Throws InternalError on a malformed extend-add map.
+PremapPlan plan_premap(const CholTree& T, const CholKnobs& kn);
 
 }  // namespace mgb

@@ -1,4 +1,5 @@
-// gfx950 kernels + host schedule of the device multifrontal Cholesky (see gpuchol.hpp).
+// gfx950 kernels, uploads and launches of the device multifrontal Cholesky (see gpuchol.hpp; which launches run over
+// which jobs is decided on the host alone, by plan_chain of chol_plan.hpp).
 //
 // Roofline: at the benchmark sizes this solver is bound by the LENGTH of its dependent launch chain (one
 // launch per 32 pivot columns along the tallest root-to-leaf path of the elimination tree), not by HBM or
@@ -18,19 +19,12 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <numeric>
 #include <stdexcept>
 #include <string>
 
 namespace mgb {
 
 namespace {
-
-constexpr int PB = 32;       // panel width
-constexpr int LP = PB + 1;   // padded LDS row length
-constexpr int TS = 64;       // trailing-update tile
-constexpr int TB = 256;      // threads per workgroup (factorisation kernels)
-constexpr int RT = 1024;     // threads per workgroup (backward_rect)
 
 void ck(hipError_t e, const char* what) {
   if (e != hipSuccess) throw HipError(std::string("HIP error in gpuchol ") + what + ": " + hipGetErrorString(e));
@@ -738,8 +732,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(1, 3))) void
 // second halves.  Then X2 = (.) L22^-T, the mirrored rows of L, and one rank-64 update of the C tile.  Tile (0,0) of every
 // front publishes L21 and the second pivot block; the pivot workgroups (first npiv) do the same for rows k2..k2+31 only
 // and factor the corner that becomes the pivot block of the NEXT launch.
-// LDS (dynamic, 115 KB): L11 and L22 in quad order, L21, the corner, the factor scratch, two 64 x 64 panel blocks.
-constexpr int kStep2Lds = (2 * PB * PB + 3 * PB * LP + 2 * 2 * PB * (TS + 8)) * (int)sizeof(double);
+// LDS (dynamic, 115 KB, kStep2Lds): L11 and L22 in quad order, L21, the corner, the factor scratch, two 64 x 64 panel blocks.
 // The same two panels as TWO launches, for the heights whose tile count is beyond what one workgroup per CU handles in a
 // round (fem2d L >= 8, the upper heights of fem3d): there the one-panel kernel was used, which re-reads and re-writes the
 // whole trailing matrix per 32 columns.
@@ -752,8 +745,6 @@ constexpr int kStep2Lds = (2 * PB * PB + 3 * PB * LP + 2 * 2 * PB * (TS + 8)) * 
 //   MODE 2, "update": the fused kernel's tiles with everything between staging and the rank-64 update removed -- the staged
 //     panel blocks ARE the solved ones.  74 KB of LDS: two per CU.
 // Operation order per entry is that of the fused kernel (and of two rank-32 steps): bitwise the same factor.
-constexpr int kPanel2Lds = (2 * PB * PB + 3 * PB * LP + 2 * PB * (TS + 8)) * (int)sizeof(double);
-constexpr int kUpdate2Lds = (2 * 2 * PB * (TS + 8)) * (int)sizeof(double);
 
 template <int MODE>
 __device__ __forceinline__ void front_step2_body(
@@ -1836,15 +1827,6 @@ GpuChol::~GpuChol() {
   for (void* p : allocs_) (void)hipFree(p);
 }
 
-// The chain's job arrays, uploaded once at the end of build(): every Launch indexes one of them
-struct GpuChol::Jobs {
-  std::vector<int> lists;      // node lists per height
-  std::vector<StartJob> starts;
-  std::vector<StepTile> tiles;
-  std::vector<SingleTile> singles;
-  std::vector<RectJob> rects;
-};
-
 const CholKnobs& GpuChol::knobs() {
   static const CholKnobs k = [] {
     auto on = [](const char* name) {      // default on; "0..." turns it off
@@ -1855,7 +1837,7 @@ const CholKnobs& GpuChol::knobs() {
       const char* e = std::getenv(name);
       return e ? std::atoi(e) : dflt;
     };
-    CholKnobs c;
+    CholKnobs c;      // the defaults: chol_plan.hpp
     c.graph = on("MGB_CHOL_GRAPH");
     c.prof = std::getenv("MGB_CHOL_PROF") != nullptr;
     c.leaf = on("MGB_CHOL_LEAF");
@@ -1863,273 +1845,18 @@ const CholKnobs& GpuChol::knobs() {
     c.step2 = on("MGB_CHOL_STEP2");
     c.wide = on("MGB_CHOL_WIDE");
     c.start_pivot = on("MGB_CHOL_START_PIVOT");
-    c.step2_tiles = num("MGB_CHOL_STEP2_TILES", 224);
-    c.dense_tiles = num("MGB_CHOL_DENSE_TILES", 512);      // what two tiles per CU hold at once
-    c.bwd_split_nf = num("MGB_BWD_SPLIT_NF", 192);
+    c.step2_tiles = num("MGB_CHOL_STEP2_TILES", c.step2_tiles);
+    c.dense_tiles = num("MGB_CHOL_DENSE_TILES", c.dense_tiles);
+    c.bwd_split_nf = num("MGB_BWD_SPLIT_NF", c.bwd_split_nf);
     c.bwd_fused = on("MGB_CHOL_BWD_FUSED");
-    c.bwd_cut = num("MGB_CHOL_BWD_CUT", 2);
-    c.bwd_fused_nf = num("MGB_CHOL_BWD_FUSED_NF", 384);
-    c.bwd_fused_threads = num("MGB_CHOL_BWD_FUSED_THREADS", 512);
-    c.premap = num("MGB_CHOL_PREMAP", 1);      // front_start consumers measured no gain inside a Newton step
-    c.premap_tiles = num("MGB_CHOL_PREMAP_TILES", 400);      // fem2d L=7: the 512-tile launch gains 0.4 us for a fifth of the slabs
+    c.bwd_cut = num("MGB_CHOL_BWD_CUT", c.bwd_cut);
+    c.bwd_fused_nf = num("MGB_CHOL_BWD_FUSED_NF", c.bwd_fused_nf);
+    c.bwd_fused_threads = num("MGB_CHOL_BWD_FUSED_THREADS", c.bwd_fused_threads);
+    c.premap = num("MGB_CHOL_PREMAP", c.premap);
+    c.premap_tiles = num("MGB_CHOL_PREMAP_TILES", c.premap_tiles);
     return c;
   }();
   return k;
-}
-
-PremapKnobs GpuChol::premap_knobs() {
-  const CholKnobs& kn = knobs();
-  PremapKnobs pk;
-  pk.leaf = kn.leaf;
-  pk.single = kn.single;
-  pk.start_pivot = kn.start_pivot;
-  pk.mode = kn.premap;
-  pk.tiles = kn.premap_tiles;
-  return pk;
-}
-
-namespace {
-
-// the workgroup of front g (node t) that factors the pivot block after panel p
-StepTile pivot_tile(const GNode& g, int t, int p) {
-  StepTile st{};
-  st.off = g.off;
-  st.loff = g.loff + (long long)p * 2 * PB * PB;
-  st.nf = g.nf;
-  st.ns = g.ns;
-  st.pad = t;      // node index (front_single_kernel)
-  return st;
-}
-
-// Appends the 64x64 tiles of front g's trailing matrix from row k on, after panel p: the lower triangle or (column) one
-// tile per 64-row block below the next pivot block -- the workgroups of a panel launch.  Returns how many.
-int append_tiles(std::vector<StepTile>& out, const GNode& g, int t, int p, int k, bool column) {
-  StepTile st = pivot_tile(g, t, p);
-  const size_t n0 = out.size();
-  if (column) {
-    const int Tr = std::max(0, (g.nf + 1 - k - PB + TS - 1) / TS);
-    for (int ti = 0; ti < Tr; ++ti) {
-      st.ti = st.tj = (short)ti;
-      out.push_back(st);
-    }
-  } else {
-    const int Tr = (g.nf + 1 - k + TS - 1) / TS, Tc = std::max(1, (g.nf - k + TS - 1) / TS);
-    if (Tr > 30000) throw ArgError("gpuchol: front too large for tile index");
-    for (int ti = 0; ti < Tr; ++ti)
-      for (int tj = 0; tj <= std::min(ti, Tc - 1); ++tj) {
-        st.ti = (short)ti;
-        st.tj = (short)tj;
-        out.push_back(st);
-      }
-  }
-  return (int)(out.size() - n0);
-}
-
-SingleTile single_tile(const std::vector<GNode>& nodes, const StepTile& s, const PremapPlan& pm) {
-  const GNode& g = nodes[s.pad];
-  SingleTile u{};
-  u.pld = g.pld;
-  u.fofs = g.fofs;
-  u.eoff = g.eoff;
-  for (int sI = 0; sI < 2; ++sI) u.soff[sI] = std::max(0LL, pm.soff[2 * (size_t)s.pad + sI]);
-  u.off = g.off;
-  u.loff = g.loff;
-  u.nf = g.nf;
-  u.ns = g.ns;
-  u.iofs = g.iofs;
-  u.a0 = g.a0;
-  u.a1 = g.a1;
-  u.first = g.first;
-  u.ti = s.ti;
-  u.tj = s.tj;
-  for (int sI = 0; sI < 2; ++sI) {
-    u.boff[sI] = g.off;
-    u.cld[sI] = 0;
-    if (g.child[sI] >= 0) {
-      const GNode& c = nodes[g.child[sI]];
-      u.cld[sI] = c.nf + 1;
-      u.boff[sI] = c.off + (long long)u.cld[sI] * c.ns + c.ns;
-    }
-  }
-  return u;
-}
-
-}  // namespace
-
-// Appends the launches of one node set to chain_ -- the forward ones height by height from the leaves, then the backward
-// ones from the root -- and their jobs to `jobs`; returns where the backward ones begin.  heights[h]: the set's nodes of
-// tree height h.
-int GpuChol::schedule(const std::vector<std::vector<int>>& heights, const std::vector<GNode>& nodes,
-                      const std::vector<std::vector<StartJob>>& sjobs, const MfChol& sym, Jobs& jobs) {
-  const CholKnobs& kn = knobs();
-  std::vector<Launch> bwd;
-  std::vector<StepTile> scratch;
-  // the fused backward launch (unsplit factorisations) takes every height up to h_top
-  const bool fused = fused_.enabled() && &heights == fused_heights_;
-  double fused_bytes = 0;
-  for (size_t hh = 0; hh < heights.size(); ++hh) {
-    const std::vector<int>& mine = heights[hh];
-    if (mine.empty()) continue;
-    const int nofs = (int)jobs.lists.size(), ncnt = (int)mine.size();
-    jobs.lists.insert(jobs.lists.end(), mine.begin(), mine.end());
-    int max_ns = 0, max_nf = 0;
-    bool childless = true, all_pivots = true;      // a pass-through front (ns = 0) needs front_start to copy it
-    bool one_tile = true;      // front_leaf: the trailing matrix after the first panel, rows min(ns, 32) .. nf, is one 64-row tile
-    double start_bytes = 0;
-    for (int t : mine) {
-      const GNode& g = nodes[t];
-      max_ns = std::max(max_ns, g.ns);
-      max_nf = std::max(max_nf, g.nf);
-      childless = childless && g.child[0] < 0 && g.child[1] < 0;
-      all_pivots = all_pivots && g.ns >= 1;
-      one_tile = one_tile && g.nf + 1 - std::min(g.ns, PB) <= TS;
-      start_bytes += 0.5 * g.nf * g.nf * 8.0 + (double)sym.a_idx_[t].size() * 20.0;
-      for (int c : g.child) {
-        if (c < 0) continue;
-        const double cnb = nodes[c].nf - nodes[c].ns;
-        start_bytes += 0.5 * cnb * cnb * 8.0;     // child entry read (the parent entry write is counted above)
-      }
-    }
-    // front_leaf (the whole front in one workgroup), front_single (single-panel heights with children: one dependency-free
-    // launch) or front_start + panel launches: HeightShape::kind, shared with the pre-mapping rule
-    HeightShape shape;
-    shape.max_ns = max_ns;
-    shape.max_nf = max_nf;
-    shape.childless = childless;
-    shape.all_pivots = all_pivots;
-    shape.one_tile = one_tile;
-    const int hkind = shape.kind(premap_knobs());
-    const bool leaf = hkind == PH_LEAF, single = hkind == PH_SINGLE;
-    // pre-mapped child contributions (unsplit factorisations; the plan covers the whole tree, height by height)
-    const bool planned = &heights == premap_heights_ && premap_.any();      // (no slabs: nothing to cross-check or flag)
-    if (planned && (premap_.hkind[hh] != hkind)) throw InternalError("gpuchol: pre-map plan disagrees with the schedule");
-    const bool consumer = planned && premap_.hconsumer[hh];
-    int nprod = 0;
-    if (planned)
-      for (int t : mine) nprod += premap_.producer[t];
-    auto check_wg = [&](int cnt) {
-      if (planned && premap_.hwg[hh] != cnt) throw InternalError("gpuchol: pre-map plan disagrees with the launch size");
-    };
-    if (leaf) {
-      const size_t lds = ((size_t)(max_nf + 1) * max_nf - (size_t)max_nf * (max_nf - 1) / 2) * sizeof(double);
-      check_wg(ncnt);
-      chain_.push_back({Kind::Leaf, nofs, ncnt, TB, lds, 0, 0, false, KC_CHOL_SINGLE, start_bytes, false, nprod});
-    } else if (!single) {
-      const int ofs = (int)jobs.starts.size();
-      if (kn.start_pivot)      // dedicated pivot jobs first: they are what the first panel launch waits for
-        for (int t : mine)
-          if (nodes[t].ns > 0 && !sjobs[t].empty()) {
-            StartJob pj = sjobs[t].front();      // chunk 0, row block 0: its assembly range covers the pivot block
-            pj.rb = -1;
-            jobs.starts.push_back(pj);
-          }
-      for (int t : mine) jobs.starts.insert(jobs.starts.end(), sjobs[t].begin(), sjobs[t].end());
-      check_wg((int)jobs.starts.size() - ofs);
-      if (nprod) throw InternalError("gpuchol: a multi-panel front cannot store pre-mapped");
-      chain_.push_back({Kind::Start, ofs, (int)jobs.starts.size() - ofs, TB, 0, 0, 0, false, KC_CHOL_START, start_bytes, consumer, 0});
-    }
-    // panel launches, pivot-owning workgroups first: they are the critical path of the next launch
-    const int npanel = leaf ? 0 : (max_ns + PB - 1) / PB;
-    for (int p = 0; p < npanel; ++p) {
-      // two panels per launch (front_step2) while the height has at least two left; the odd last one runs front_step
-      // ... and only where the launch is latency-bound (its tiles fit the chip in one round): front_step2 holds 115 KB of
-      // LDS, one workgroup per CU, and loses against two rank-32 launches at 2-3 workgroups per CU on the big 3-D heights
-      const bool two = kn.step2 && !single && p + 1 < npanel;
-      int ntile2 = 0;
-      if (two) {
-        scratch.clear();
-        for (int t : mine)
-          if (nodes[t].ns > p * PB) ntile2 += append_tiles(scratch, nodes[t], t, p, std::min(nodes[t].ns, (p + 2) * PB), false);
-      }
-      const bool pair = two && ntile2 <= kn.step2_tiles;
-      const int ofs = (int)jobs.tiles.size();
-      int npiv = 0;
-      double bytes = 0;
-      if (two && !pair && kn.wide) {
-        // beyond that tile count: the same two panels as a panel launch (one workgroup per 64-row block, row block 0 also
-        // factors the next pivot block) and an update launch (the tiles, rank-64, nothing else) -- see front_step2_body
-        for (int t : mine) {
-          const GNode& g = nodes[t];
-          if (g.ns <= p * PB) continue;
-          jobs.tiles.push_back(pivot_tile(g, t, p));      // the front's pivot workgroup: trailing rows k2 .. k2 + 31
-          npiv++;
-          const int k2 = std::min(g.ns, (p + 2) * PB);
-          const double tr = g.nf + 1 - k2;
-          bytes += tr * (k2 - p * PB) * 32.0;      // panel read, mirrored + in-place write
-        }
-        for (int t : mine)
-          if (nodes[t].ns > p * PB) append_tiles(jobs.tiles, nodes[t], t, p, std::min(nodes[t].ns, (p + 2) * PB), true);
-        chain_.push_back({Kind::Panel2, ofs, (int)jobs.tiles.size() - ofs, TB, kPanel2Lds, p, npiv, false, KC_CHOL_STEP, bytes});
-        const int uofs = (int)jobs.tiles.size();
-        double ubytes = 0;
-        for (int t : mine) {
-          const GNode& g = nodes[t];
-          if (g.ns <= p * PB) continue;
-          const int k2 = std::min(g.ns, (p + 2) * PB);
-          append_tiles(jobs.tiles, g, t, p, k2, false);
-          const double tr = g.nf + 1 - k2;
-          ubytes += tr * (k2 - p * PB) * 8.0 + 0.5 * tr * tr * 16.0;      // solved panel read, trailing read + write
-        }
-        chain_.push_back({Kind::Update2, uofs, (int)jobs.tiles.size() - uofs, TB, kUpdate2Lds, p, 0, false, KC_CHOL_STEP, ubytes});
-        ++p;
-        continue;
-      }
-      const int np = pair ? 2 : 1;
-      for (int t : mine) {
-        const GNode& g = nodes[t];
-        if (g.ns <= p * PB) continue;
-        const int k1 = std::min(g.ns, (p + np) * PB), kw = k1 - p * PB;      // first trailing row, pivots of this launch
-        if (k1 < g.ns) {
-          jobs.tiles.push_back(pivot_tile(g, t, p));
-          npiv++;
-        }
-        const double tr = g.nf + 1 - k1;
-        bytes += tr * kw * 16.0 + 0.5 * tr * tr * 16.0;      // panel read + mirrored write, trailing read + write
-      }
-      for (int t : mine)
-        if (nodes[t].ns > p * PB) append_tiles(jobs.tiles, nodes[t], t, p, std::min(nodes[t].ns, (p + np) * PB), false);
-      const int cnt = (int)jobs.tiles.size() - ofs;
-      if (single) {      // same tiles, self-contained descriptors
-        const int sofs = (int)jobs.singles.size();
-        for (int q = ofs; q < ofs + cnt; ++q) jobs.singles.push_back(single_tile(nodes, jobs.tiles[q], premap_));
-        check_wg(cnt);
-        const bool narrow = max_ns <= 8, dense = cnt > kn.dense_tiles;
-        const Kind k = dense ? (narrow ? Kind::SingleDenseNarrow : Kind::SingleDense) : (narrow ? Kind::SingleNarrow : Kind::Single);
-        chain_.push_back({k, sofs, cnt, TB, 0, 0, 0, false, KC_CHOL_SINGLE, start_bytes + bytes, consumer, nprod});
-      } else {
-        chain_.push_back({pair ? Kind::Step2 : Kind::Step, ofs, cnt, TB, pair ? (size_t)kStep2Lds : 0, p, npiv, false, KC_CHOL_STEP, bytes});
-      }
-      if (pair) ++p;
-    }
-    // backward: above bwd_split_nf the rectangular part runs in its own multi-workgroup launch first
-    const bool split = max_nf > kn.bwd_split_nf;
-    const int rofs = (int)jobs.rects.size();
-    double rect_bytes = 0, tri_bytes = 0;
-    for (int t : mine) {
-      const GNode& g = nodes[t];
-      const double nb = g.nf - g.ns;
-      rect_bytes += nb * g.ns * 8.0 + nb * 12.0;
-      tri_bytes += 0.5 * g.ns * g.ns * 8.0 + g.ns * 28.0;
-      if (split && nb > 0)
-        for (int ch = 0; ch * 64 < g.ns; ++ch) jobs.rects.push_back({t, ch});
-    }
-    const int nrect = (int)jobs.rects.size() - rofs, nt = max_nf > 384 ? 1024 : 256;
-    if (fused && (int)hh <= fused_.h_top) {
-      jobs.rects.resize(rofs);
-      fused_bytes += rect_bytes + tri_bytes;
-      continue;
-    }
-    std::vector<Launch> h;
-    if (nrect) h.push_back({Kind::BwdRect, rofs, nrect, RT, (size_t)(max_nf + RT) * sizeof(double), 0, 0, false, KC_CHOL_BWD_RECT, rect_bytes});
-    h.push_back({nt == 1024 ? Kind::Bwd1024 : Kind::Bwd256, nofs, ncnt, nt, (size_t)(max_nf + nt + PB) * sizeof(double), 0, 0, nrect > 0,
-                 KC_CHOL_BWD, tri_bytes + (nrect ? 0.0 : rect_bytes)});
-    bwd.insert(bwd.begin(), h.begin(), h.end());      // the backward sweep runs from the root
-  }
-  const int first_bwd = (int)chain_.size();
-  chain_.insert(chain_.end(), bwd.begin(), bwd.end());
-  if (fused)
-    chain_.push_back({Kind::BwdFused, 0, fused_.nwg, fused_.threads, fused_.lds_bytes, 0, 0, false, KC_CHOL_BWD, fused_bytes});
-  return first_bwd;
 }
 
 void GpuChol::schedule_info(int cap, int* nlaunch, int* kind, int* workgroups) const {
@@ -2150,9 +1877,10 @@ void GpuChol::premap_info(int cap, int* consumer, int* producers) const {
 }
 
 void GpuChol::unknown_columns(const MfChol& sym, int* node, int* col) {
-  for (int t = 0; t < (int)sym.nodes_.size(); ++t)
-    for (int k = 0; k < sym.nodes_[t].ns; ++k) {
-      const int i = sym.perm_[sym.nodes_[t].first + k];
+  const CholTree T = sym.view();
+  for (int t = 0; t < T.size(); ++t)
+    for (int k = 0; k < T.ns[t]; ++k) {
+      const int i = (*T.perm)[T.first[t] + k];
       if (node) node[i] = t;
       if (col) col[i] = k;
     }
@@ -2161,179 +1889,39 @@ void GpuChol::unknown_columns(const MfChol& sym, int* node, int* col) {
 void GpuChol::build(const MfChol& sym, Ctx* ctx) {
   ctx_ = ctx;
   part_ = (ctx && ctx->world > 1) ? sym.partition(ctx->world) : CholPartition();
-  if (!part_.split()) part_.owner.assign(sym.nodes_.size(), -1);
   const int my_rank = ctx ? ctx->rank : 0;
-  n_ = sym.n_;
-  nnodes_ = (int)sym.nodes_.size();
-  flops_ = sym.flops_;
-  std::vector<GNode> nodes(nnodes_);
-  std::vector<int> bdry_all, height(nnodes_, 0);
-  {      // pre-mapped child contributions: the tables first, every descriptor below carries its part of them
-    std::vector<int> ns(nnodes_), nf(nnodes_), parent(nnodes_), c0(nnodes_, -1), c1(nnodes_, -1);
-    std::vector<const std::vector<int>*> ea(nnodes_);
-    for (int t = 0; t < nnodes_; ++t) {
-      const auto& nd = sym.nodes_[t];
-      if (nd.children.size() > 2) throw InternalError("gpuchol: elimination tree is not binary");
-      ns[t] = nd.ns;
-      nf[t] = nd.nf();
-      parent[t] = nd.parent;
-      if (nd.children.size() > 0) c0[t] = nd.children[0];
-      if (nd.children.size() > 1) c1[t] = nd.children[1];
-      ea[t] = &nd.ea;
-    }
-    PremapKnobs pk = premap_knobs();
-    if (part_.split()) pk.mode = 0;      // schur_pack_kernel reads the subtree roots' Schur complements from the fronts
-    premap_ = plan_premap(ns, nf, parent, c0, c1, ea, pk);
-  }
-  const std::vector<int>& pinv = premap_.pinv;
-  long long off = 0, loff = 0;
-  max_nf_ = 0;
-  for (int t = 0; t < nnodes_; ++t) {
-    const auto& nd = sym.nodes_[t];
-    GNode& g = nodes[t];
-    g.pld = premap_.pld[t];
-    g.fofs = premap_.fofs[t];
-    g.eoff = premap_.eoff[t];
-    g.off = off;
-    g.loff = loff;
-    loff += (long long)((nd.ns + PB - 1) / PB) * 2 * PB * PB;
-    g.nf = nd.nf();
-    g.ns = nd.ns;
-    g.first = nd.first;
-    g.parent = nd.parent;
-    g.bofs = (int)bdry_all.size();
-    g.child[0] = nd.children.size() > 0 ? nd.children[0] : -1;
-    g.child[1] = nd.children.size() > 1 ? nd.children[1] : -1;
-    g.iofs = premap_.iofs[t];
-    bdry_all.insert(bdry_all.end(), nd.bdry.begin(), nd.bdry.end());
-    if (nd.parent >= 0 && nd.ea.size() != nd.bdry.size()) throw InternalError("gpuchol: ea/bdry size mismatch");
-    if (nd.parent >= 0 && !std::is_sorted(nd.ea.begin(), nd.ea.end())) throw InternalError("gpuchol: ea not ascending");
-    if ((long long)(g.nf + 1) * (g.nf + 1) > 2000000000LL) throw ArgError("gpuchol: front too large");
-    off += (long long)(g.nf + 1) * (g.nf + 1);
-    max_nf_ = std::max(max_nf_, g.nf);
-    for (int c : nd.children) height[t] = std::max(height[t], height[c] + 1);   // postorder: children first
-  }
-  total_front_ = off;
-  // (the inverse maps -- per parent and child slot: parent front row -> child boundary row, the child's right-hand-side
-  // row for nf -- come with the plan: premap_.pinv / iofs)
-  nheights_ = nnodes_ ? *std::max_element(height.begin(), height.end()) + 1 : 0;
-  // assembly map, per node sorted by the front_start job (32-column chunk, 256-row block counted from the chunk's
-  // first row) that owns the destination; positions in the (nf+1)-leading-dimension layout
-  std::vector<int> asrc, apos;
-  std::vector<std::vector<StartJob>> sjobs(nnodes_);
-  for (int t = 0; t < nnodes_; ++t) {
-    const int nf = nodes[t].nf, ld = nf + 1;
-    const size_t m = sym.a_idx_[t].size();
-    const int nch = (nf + PB - 1) / PB;
-    auto key = [&](int e) {
-      const int pos = sym.a_pos_[t][e], col = pos / nf, row = pos % nf, ch = col / PB;
-      return (long long)ch * 65536 + (row - ch * PB) / TB;
-    };
-    std::vector<int> ord(m);
-    std::iota(ord.begin(), ord.end(), 0);
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return key(a) < key(b); });
-    size_t q = 0;
-    for (int ch = 0; ch < nch; ++ch) {
-      const int nrb = (nf + 1 - ch * PB + TB - 1) / TB;      // rows ch*32 .. nf inclusive
-      if (nrb > 65535) throw ArgError("gpuchol: front too large for the start-job key");
-      for (int rb = 0; rb < nrb; ++rb) {
-        StartJob j{};
-        j.node = t;
-        j.chunk = ch;
-        j.rb = rb;
-        j.off = nodes[t].off;
-        j.loff = nodes[t].loff;
-        j.nf = nodes[t].nf;
-        j.ns = nodes[t].ns;
-        j.iofs = nodes[t].iofs;
-        j.first = nodes[t].first;
-        for (int sI = 0; sI < 2; ++sI) {
-          j.boff[sI] = nodes[t].off;
-          j.cld[sI] = 0;
-          if (nodes[t].child[sI] >= 0) {
-            const GNode& c = nodes[nodes[t].child[sI]];
-            j.cld[sI] = c.nf + 1;
-            j.boff[sI] = c.off + (long long)j.cld[sI] * c.ns + c.ns;
-          }
-        }
-        for (int sI = 0; sI < 2; ++sI) j.soff[sI] = std::max(0LL, premap_.soff[2 * (size_t)t + sI]);
-        j.a0 = (int)asrc.size();
-        while (q < m && key(ord[q]) == (long long)ch * 65536 + rb) {
-          const int pos = sym.a_pos_[t][ord[q]], col = pos / nf, row = pos % nf;
-          if (row < col) throw InternalError("gpuchol: assembly entry above the diagonal");
-          asrc.push_back(sym.a_idx_[t][ord[q]]);
-          apos.push_back(ld * col + row);
-          ++q;
-        }
-        j.a1 = (int)asrc.size();
-        sjobs[t].push_back(j);
-      }
-    }
-    if (q != m) throw InternalError("gpuchol: assembly entry outside the front");
-    nodes[t].a0 = sjobs[t].empty() ? 0 : sjobs[t].front().a0;
-    nodes[t].a1 = sjobs[t].empty() ? 0 : sjobs[t].back().a1;
-  }
-  // schedule: the nodes of every height, own (split: this rank's subtree; else everything) and the replicated top
-  std::vector<std::vector<int>> own(nheights_), top(nheights_);
-  for (int t = 0; t < nnodes_; ++t) {
-    if (!part_.split() || part_.owner[t] == my_rank) own[height[t]].push_back(t);
-    else if (part_.owner[t] < 0) top[height[t]].push_back(t);
-  }
-  Jobs jobs;
-  chain_.clear();
-  fused_ = FusedPlan();
-  fused_heights_ = nullptr;
-  if (!part_.split() && knobs().bwd_fused) {
-    std::vector<int> ns(nnodes_), first(nnodes_), parent(nnodes_);
-    std::vector<const std::vector<int>*> bd(nnodes_);
-    for (int t = 0; t < nnodes_; ++t) {
-      ns[t] = nodes[t].ns;
-      first[t] = nodes[t].first;
-      parent[t] = nodes[t].parent;
-      bd[t] = &sym.nodes_[t].bdry;
-    }
-    const CholKnobs& kn = knobs();
-    FusedKnobs fk;
-    fk.cut = kn.bwd_cut;
-    fk.top_nf = kn.bwd_fused_nf;
-    fk.threads = kn.bwd_fused_threads;
-    fk.split_nf = kn.bwd_split_nf;
-    fused_ = plan_bwd_fused(ns, first, parent, bd, fk);
-    if (fused_.lds_bytes > 150 * 1024) fused_ = FusedPlan();      // does not fit: the per-height launches
-    if (fused_.enabled()) {
-      fused_heights_ = &own;
-      for (int t = 0; t < nnodes_; ++t)
-        if (fused_.bofs[t] != nodes[t].bofs || fused_.height[t] != height[t]) throw InternalError("gpuchol: fused plan disagrees with the front layout");
-    }
-  }
-  for (int t = 0; t < nnodes_; ++t)
-    if (premap_.height[t] != height[t]) throw InternalError("gpuchol: pre-map plan disagrees with the tree heights");
-  premap_heights_ = part_.split() ? nullptr : &own;
-  own_bwd_ = schedule(own, nodes, sjobs, sym, jobs);
-  fused_heights_ = nullptr;
-  premap_heights_ = nullptr;
-  top_fwd_ = (int)chain_.size();
-  if (part_.split()) schedule(top, nodes, sjobs, sym, jobs);
-  if ((size_t)(max_nf_ + RT + PB) * 8 > 150 * 1024) throw ArgError("gpuchol: front exceeds the LDS budget of the sweeps");
+  const CholTree T = sym.view();
+  ChainPlan P = plan_chain(T, part_, my_rank, knobs());
+  const std::vector<GNode>& nodes = P.nodes;
+  const std::vector<int>& perm = *T.perm;
+  const int nnodes = T.size();
+  n_ = T.n;
+  flops_ = T.flops;
+  total_front_ = T.front_doubles;
+  chain_ = std::move(P.chain);
+  own_bwd_ = P.own_bwd;
+  top_fwd_ = P.top_fwd;
+  premap_ = std::move(P.premap);
+  fused_ = std::move(P.fused);
   d_nodes_ = upload(nodes);
-  d_perm_ = upload(sym.perm_);
-  d_bdry_ = upload(bdry_all);
-  d_pinv_ = upload(pinv);
+  d_perm_ = upload(perm);
+  d_bdry_ = upload(P.bdry);
+  d_pinv_ = upload(premap_.pinv);
   d_fwd_ = upload(premap_.fwd);
-  d_asm_src_ = upload(asrc);
-  d_asm_pos_ = upload(apos);
-  d_lists_ = upload(jobs.lists);
+  d_asm_src_ = upload(P.asrc);
+  d_asm_pos_ = upload(P.apos);
+  d_lists_ = upload(P.lists);
   {      // node descriptors in launch order (front_leaf, backward) and per backward_rect job
-    std::vector<GNode> hn(jobs.lists.size()), rn(jobs.rects.size());
-    for (size_t k = 0; k < jobs.lists.size(); ++k) hn[k] = nodes[jobs.lists[k]];
-    for (size_t k = 0; k < jobs.rects.size(); ++k) rn[k] = nodes[jobs.rects[k].node];
+    std::vector<GNode> hn(P.lists.size()), rn(P.rects.size());
+    for (size_t k = 0; k < P.lists.size(); ++k) hn[k] = nodes[P.lists[k]];
+    for (size_t k = 0; k < P.rects.size(); ++k) rn[k] = nodes[P.rects[k].node];
     d_hnodes_ = upload(hn);
     d_rnodes_ = upload(rn);
   }
-  d_start_ = upload(jobs.starts);
-  d_tiles_ = upload(jobs.tiles);
-  d_singles_ = upload(jobs.singles);
-  d_rectjobs_ = upload(jobs.rects);
+  d_start_ = upload(P.starts);
+  d_tiles_ = upload(P.tiles);
+  d_singles_ = upload(P.singles);
+  d_rectjobs_ = upload(P.rects);
   d_fused_wg_ = upload(fused_.wg);
   d_fused_slots_ = upload(fused_.slots);
   if (part_.split()) {
@@ -2356,14 +1944,14 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
     nroots_ = (int)roots.size();
     d_roots_ = upload(roots);
     std::vector<int> own(n_, 0);
-    for (int t = 0; t < nnodes_; ++t)
+    for (int t = 0; t < nnodes; ++t)
       if (part_.owner[t] == my_rank || (part_.owner[t] < 0 && my_rank == 0))
-        for (int k = 0; k < nodes[t].ns; ++k) own[sym.perm_[nodes[t].first + k]] = 1;
+        for (int k = 0; k < nodes[t].ns; ++k) own[perm[nodes[t].first + k]] = 1;
     d_own_orig_ = upload(own);
     std::vector<int> kind(n_, 0), top_unk;
-    for (int t = 0; t < nnodes_; ++t)
+    for (int t = 0; t < nnodes; ++t)
       for (int k = 0; k < nodes[t].ns; ++k) {
-        const int i = sym.perm_[nodes[t].first + k];
+        const int i = perm[nodes[t].first + k];
         kind[i] = part_.owner[t] < 0 ? 2 : (part_.owner[t] == my_rank ? 1 : 0);
         if (part_.owner[t] < 0) top_unk.push_back(i);
       }
@@ -2391,7 +1979,7 @@ void GpuChol::build(const MfChol& sym, Ctx* ctx) {
   ck(hipMalloc((void**)&d_slabs_, std::max<long long>(premap_.slab_doubles, 1) * sizeof(double)), "hipMalloc slabs");
   allocs_.push_back(d_slabs_);
   ck(hipMemset(d_slabs_, 0, std::max<long long>(premap_.slab_doubles, 1) * sizeof(double)), "memset slabs");
-  ck(hipMalloc((void**)&d_linv_, std::max<long long>(loff, 1) * sizeof(double)), "hipMalloc linv");
+  ck(hipMalloc((void**)&d_linv_, std::max<long long>(T.linv_doubles, 1) * sizeof(double)), "hipMalloc linv");
   allocs_.push_back(d_linv_);
   ck(hipMalloc((void**)&d_rect_, std::max(n_, 1) * sizeof(double)), "hipMalloc rect");
   allocs_.push_back(d_rect_);
@@ -2467,6 +2055,15 @@ void GpuChol::factor_solve(hipStream_t st, double* d_vals, const double* d_b, do
   ck(hipGraphLaunch(ge.exec, st), "hipGraphLaunch");
 }
 
+namespace {
+int timer_class(Kind k) {      // KernelTimer class of a launch kind
+  if (k <= Kind::SingleDenseNarrow) return KC_CHOL_SINGLE;
+  if (k == Kind::Start) return KC_CHOL_START;
+  if (k <= Kind::Update2) return KC_CHOL_STEP;
+  return k == Kind::BwdRect ? KC_CHOL_BWD_RECT : KC_CHOL_BWD;
+}
+}  // namespace
+
 // Issues chain_[begin, end) in order
 void GpuChol::run(hipStream_t st, int begin, int end, const double* d_vals, const double* d_b, double* d_x, KernelTimer* tm) {
   for (int i = begin; i < end; ++i) {
@@ -2475,7 +2072,7 @@ void GpuChol::run(hipStream_t st, int begin, int end, const double* d_vals, cons
     const dim3 grid(L.cnt), block(L.block);
     const bool narrow = L.kind == Kind::SingleNarrow || L.kind == Kind::SingleDenseNarrow;
     const bool dense = L.kind == Kind::SingleDense || L.kind == Kind::SingleDenseNarrow;
-    if (tm) tm->begin(st, L.timer, L.bytes);
+    if (tm) tm->begin(st, timer_class(L.kind), L.bytes);
     switch (L.kind) {
       case Kind::Leaf:
         hipLaunchKernelGGL(front_leaf_kernel, grid, block, L.lds, st, d_hnodes_ + L.ofs, d_lists_ + L.ofs, d_asm_src_, d_asm_pos_,

@@ -28,90 +28,12 @@
 
 #include <vector>
 
-#include "bwd_fused.hpp"
-#include "chol_premap.hpp"
-#include "mfchol.hpp"
+#include "chol_plan.hpp"
 
 namespace mgb {
 
 class KernelTimer;   // amg.hpp: optional HIP-event bracketing of individual launches
 struct Ctx;          // amg.hpp: device, stream and (sharded jobs) the allreduce callback
-
-struct RootXchg {     // one subtree root of a split factorisation: where its Schur complement lives and travels
-  long long off;      // front offset
-  long long xoff;     // offset of its packed lower triangle (+ right-hand-side row) in the exchange buffer
-  int ld, ns, nb;     // leading dimension nf + 1, own columns, boundary size
-  int owned;          // 1 on the rank that factors this subtree
-};
-
-struct GNode {
-  long long off;      // offset of the (nf+1) x (nf+1) column-major front
-  long long loff;     // offset of this node's 32x32 pivot blocks of L (one per panel)
-  int nf, ns, first, parent;
-  int bofs;           // offset of this node's bdry / ea lists (nb entries each)
-  int child[2];       // -1 if absent
-  int iofs;           // offset of the two (nf+1)-long inverse extend-add maps (-1: leaf)
-  int a0, a1;         // range of this node's entries in the assembly list
-  int pld;            // pre-mapped store (chol_premap.hpp): the parent's leading dimension,
-  int fofs;           // ... where this node's forward map begins,
-  long long eoff;     // ... and the offset of its slab in the parent (-1: the Schur complement stays in the front)
-};
-
-struct StartJob {     // one workgroup of front_start: 32 columns x 256 rows (counted from the chunk's first row) of one front,
-                      // with everything of the node and its children inline (no dependent descriptor loads)
-  long long off, loff;      // front, first pivot block
-  long long boff[2];        // first boundary entry of each child's front (own front offset if absent)
-  int cld[2];               // child leading dimensions (0 = no child)
-  int nf, ns, iofs, first;
-  int node, chunk, rb;
-  int a0, a1;         // range of the (column-sorted) assembly list
-  long long soff[2];  // pre-mapped consumer launches: the front's contribution slab per child slot (unused slot: any valid offset)
-};
-
-struct StepTile {     // one workgroup of front_step: a 64x64 tile of the trailing matrix of one front
-  long long off;      // front offset
-  long long loff;     // offset of THIS panel's pivot block
-  int nf, ns;
-  short ti, tj;
-  int pad;            // node index
-};
-
-struct SingleTile {   // one workgroup of front_single: a tile of a single-panel front, with everything it needs inline
-  long long off, loff;      // front, pivot block
-  long long boff[2];        // first boundary entry of each child's front (own front offset if absent)
-  int cld[2];               // child leading dimensions (0 = no child)
-  int nf, ns, iofs, a0, a1, first;
-  short ti, tj;
-  int pld, fofs;      // pre-mapped store: the parent's leading dimension, where the front's forward map begins
-  long long eoff;     // ... and the offset of its slab in the parent (-1: the Schur complement stays in the front)
-  long long soff[2];  // pre-mapped consumer launches: the front's contribution slab per child slot
-};
-
-struct RectJob {      // one workgroup of backward_rect: 64 own columns of one front
-  int node, chunk;
-};
-
-// The chain's environment knobs (all optional), read once per process
-struct CholKnobs {
-  bool graph;          // MGB_CHOL_GRAPH=0: plain launches instead of hipGraph replay
-  bool prof;           // MGB_CHOL_PROF set: phase stamps of every launch, printed after each plain-launch unsplit chain
-  bool leaf;           // MGB_CHOL_LEAF=0: no front_leaf heights
-  bool single;         // MGB_CHOL_SINGLE=0: no front_single heights
-  bool step2;          // MGB_CHOL_STEP2=0: one panel per launch everywhere (the scheme before front_step2)
-  bool wide;           // MGB_CHOL_WIDE=0: one panel per launch beyond the fused kernel's tile count (no panel + update pairs)
-  bool start_pivot;    // MGB_CHOL_START_PIVOT=0: the first pivot block is factored by the assembling workgroup
-  int step2_tiles;     // MGB_CHOL_STEP2_TILES (224): largest launch, in tiles, that runs two panels fused
-  int dense_tiles;     // MGB_CHOL_DENSE_TILES (512): single-panel launches above this many tiles run three tiles per CU
-  int bwd_split_nf;    // MGB_BWD_SPLIT_NF (192): front size above which the backward sweep of a height has a backward_rect launch
-  bool bwd_fused;      // MGB_CHOL_BWD_FUSED=0: the backward sweep as one or two launches per height (no backward_fused launch)
-  int bwd_cut;         // MGB_CHOL_BWD_CUT (2): height of the subtrees the fused backward launch gives one workgroup each (raised by
-                       // up to two heights until they are at most 256, one per CU; trees that need more keep the per-height launches)
-  int bwd_fused_nf;    // MGB_CHOL_BWD_FUSED_NF (384): heights with a larger front keep their own backward launches; 0: no limit
-  int bwd_fused_threads;  // MGB_CHOL_BWD_FUSED_THREADS (512): workgroup size of the fused backward launch (a power of two, 64 .. 512)
-  int premap;          // MGB_CHOL_PREMAP (1): children store their Schur complements in parent order (chol_premap.hpp) for
-                       // 1: front_single consumers, 2: front_start consumers too; 0: every launch gathers through the index maps
-  int premap_tiles;    // MGB_CHOL_PREMAP_TILES (400): largest launch, in workgroups, that reads pre-mapped slabs
-};
 
 class GpuChol {
  public:
@@ -120,6 +42,7 @@ class GpuChol {
   GpuChol& operator=(const GpuChol&) = delete;
   ~GpuChol();
   static const CholKnobs& knobs();
+  using Kind = mgb::Kind;      // the launch kinds (chol_plan.hpp): the codes schedule_info reports
   // ctx (nullable): on a sharded context (ctx->world a power of two the tree can be split into) the factorisation is
   // split by subtrees -- this rank factors its subtree, the subtree roots' Schur complements (with their right-hand-side
   // rows) are summed over the ranks (one rank contributes each), every rank factors the replicated top and sweeps back
@@ -161,16 +84,12 @@ class GpuChol {
   // its fronts' contribution slabs instead of gathering, and how many of its fronts store their Schur complement into one
   void premap_info(int cap, int* consumer, int* producers) const;
   double slab_bytes() const { return (double)premap_.slab_doubles * 8; }
-  static PremapKnobs premap_knobs();      // the rule's knobs as this process reads them
   // per unknown (original ordering, nullable outputs): its tree node (postorder) and its column among that node's own columns
   static void unknown_columns(const MfChol& sym, int* node, int* col);
 
  private:
   template <class T>
   T* upload(const std::vector<T>& v);
-  struct Jobs;
-  int schedule(const std::vector<std::vector<int>>& heights, const std::vector<GNode>& nodes,
-               const std::vector<std::vector<StartJob>>& sjobs, const MfChol& sym, Jobs& jobs);
   void run(hipStream_t st, int begin, int end, const double* d_vals, const double* d_b, double* d_x, KernelTimer* tm);
   void enqueue(hipStream_t st, const double* d_vals, const double* d_b, double* d_x, KernelTimer* tm);
   void print_stamps(hipStream_t st);
@@ -198,7 +117,7 @@ class GpuChol {
     hipGraphExec_t exec;
   };
   std::vector<GraphEntry> graphs_;
-  int n_ = 0, nnodes_ = 0, nheights_ = 0, max_nf_ = 0;
+  int n_ = 0;
   long long total_front_ = 0;
   double flops_ = 0;
   // device
@@ -208,7 +127,6 @@ class GpuChol {
   double* d_slabs_ = nullptr;     // pre-mapped child contributions: zeroed once by build(), written by the producers only
   int* d_fwd_ = nullptr;          // ... the forward maps (child boundary row -> parent front row)
   PremapPlan premap_;             // ... their host tables (all flags off for split factorisations)
-  const std::vector<std::vector<int>>* premap_heights_ = nullptr;     // (during build) the height lists that plan covers
   double* d_y_ = nullptr;         // solution in the new ordering
   int* d_fail_ = nullptr;
   long long* d_prof_ = nullptr;   // MGB_CHOL_PROF=1: phase stamps of workgroup 0 of every launch but backward_rect
@@ -226,27 +144,10 @@ class GpuChol {
   StepTile* d_tiles_ = nullptr;
   SingleTile* d_singles_ = nullptr;
   RectJob* d_rectjobs_ = nullptr;
-  const std::vector<std::vector<int>>* fused_heights_ = nullptr;      // (during build) the height lists the plan covers
   FusedPlan fused_;               // fused backward sweep (unsplit factorisations): host tables, empty where it is off
   int* d_fused_wg_ = nullptr;     // ... its workgroup records
   int* d_fused_slots_ = nullptr;  // ... and the LDS slot of every boundary entry (parallel to d_bdry_)
-  // host schedule: every dispatch of the chain, decided once by build()
-  enum class Kind : unsigned char {
-    Leaf, Single, SingleNarrow, SingleDense, SingleDenseNarrow, Start, Step, Step2, Panel2, Update2, BwdRect, Bwd256, Bwd1024, BwdFused
-  };
-  struct Launch {
-    Kind kind;
-    int ofs, cnt;       // job range, one workgroup per job, in lists (Leaf, Bwd*), singles (Single*), starts (Start),
-                        // tiles (Step, Step2, Panel2, Update2), rects (BwdRect) or the fused sweep's workgroup records (BwdFused)
-    int block;          // threads per workgroup
-    size_t lds;         // dynamic LDS bytes
-    int p, npiv;        // first panel, leading pivot workgroups (step kinds)
-    bool rect;          // Bwd*: the rectangular part ran in the BwdRect launch before
-    int timer;          // KernelTimer class
-    double bytes;       // algorithmic bytes
-    bool premap = false;     // Single*, Start: reads the contribution slabs (no gather)
-    int nproducers = 0;      // Leaf, Single*: fronts of the launch that store into a slab
-  };
+  // host schedule: every dispatch of the chain, decided once by plan_chain (chol_plan.hpp)
   // own forward | own backward | (split) top forward | top backward, in launch order; a launch's position is its profile slot.
   // Own: this rank's subtree when split, else everything; top: the replicated separators above the subtrees.
   std::vector<Launch> chain_;

@@ -1,5 +1,7 @@
 #include "mfchol.hpp"
 
+#include "chol_plan.hpp"
+
 #include <sched.h>
 
 #include <atomic>
@@ -650,6 +652,28 @@ CholPartition MfChol::partition(int world) const {
   part.world = world;
   part.roots = frontier;
   return part;
+}
+
+CholTree MfChol::view() const {
+  CholTree T;
+  T.n = n_;
+  T.flops = flops_;
+  T.perm = &perm_;
+  for (size_t t = 0; t < nodes_.size(); ++t) {
+    const Node& nd = nodes_[t];
+    if (nd.children.size() > 2) throw InternalError("MfChol: elimination tree is not binary");
+    T.ns.push_back(nd.ns);
+    T.nf.push_back(nd.nf());
+    T.first.push_back(nd.first);
+    T.parent.push_back(nd.parent);
+    for (size_t s = 0; s < 2; ++s) T.child[s].push_back(nd.children.size() > s ? nd.children[s] : -1);
+    T.bdry.push_back(&nd.bdry);
+    T.ea.push_back(&nd.ea);
+    T.a_idx.push_back(&a_idx_[t]);
+    T.a_pos.push_back(&a_pos_[t]);
+  }
+  T.layout();
+  return T;
 }
 
 std::vector<int> MfChol::top_value_indices(const CholPartition& part) const {

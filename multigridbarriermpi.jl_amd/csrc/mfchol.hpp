@@ -17,6 +17,8 @@
 
 namespace mgb {
 
+struct CholTree;      // chol_plan.hpp
+
 // Split of the elimination tree over the ranks of a row-block sharded job (the reference factors through MUMPS
 // distributed over its MPI ranks, README.md:23, tools/profile_ops.jl:117-126): the `world` subtrees hanging log2(world)
 // levels below the root go to one rank each; the separators above them (the "top") are factored redundantly by every
@@ -72,28 +74,10 @@ class MfChol {
     ns.clear(); nf.clear(); parent.clear();
     for (const Node& nd : nodes_) { ns.push_back(nd.ns); nf.push_back(nd.nf()); parent.push_back(nd.parent); }
   }
-  // what the backward sweep's schedule needs per node: own size, first own unknown (new ordering), parent and the
-  // boundary list (new indices, ascending; the pointers stay valid as long as this object)
-  void bwd_tables(std::vector<int>& ns, std::vector<int>& first, std::vector<int>& parent, std::vector<const std::vector<int>*>& bdry) const {
-    ns.clear(); first.clear(); parent.clear(); bdry.clear();
-    for (const Node& nd : nodes_) { ns.push_back(nd.ns); first.push_back(nd.first); parent.push_back(nd.parent); bdry.push_back(&nd.bdry); }
-  }
-  // what the pre-mapped child contributions of the device factorisation need per node: own size, front size, parent, the
-  // two child slots (-1: absent) and the extend-add list (position of boundary entry i in the parent's front; the pointers
-  // stay valid as long as this object)
-  void premap_tables(std::vector<int>& ns, std::vector<int>& nf, std::vector<int>& parent, std::vector<int>& child0,
-                     std::vector<int>& child1, std::vector<const std::vector<int>*>& ea) const {
-    tree(ns, nf, parent);
-    child0.clear(); child1.clear(); ea.clear();
-    for (const Node& nd : nodes_) {
-      child0.push_back(nd.children.size() > 0 ? nd.children[0] : -1);
-      child1.push_back(nd.children.size() > 1 ? nd.children[1] : -1);
-      ea.push_back(&nd.ea);
-    }
-  }
+  // the symbolic structure the device factorisation plans from (chol_plan.hpp): handed out once, pointers into this object
+  CholTree view() const;
 
  private:
-  friend class GpuChol;   // the device factorisation reuses this symbolic structure verbatim
   struct Node {
     int parent = -1;
     int first = 0, ns = 0;      // own dofs: new indices [first, first+ns)

@@ -143,7 +143,7 @@ class Reference:
 
 
 # ---------------------------------------------------------------------------------------------------------- the cases
-# The 14 launch kinds of the device chain (GpuChol::Kind, the codes of mgb_amg_chol_schedule, AMG.CHOL_KINDS)
+# The 14 launch kinds of the device chain (Kind of csrc/chol_plan.hpp, the codes of mgb_amg_chol_schedule, AMG.CHOL_KINDS)
 KINDS = ("Leaf", "Single", "SingleNarrow", "SingleDense", "SingleDenseNarrow", "Start", "Step", "Step2", "Panel2", "Update2",
          "BwdRect", "Bwd256", "Bwd1024", "BwdFused")
 
@@ -266,6 +266,42 @@ def plan_tree(p, dim):
     ns, nf, par = (np.zeros(nn.value, dtype=np.int32) for _ in range(3))
     _lib.call("mgb_plan_chol_tree", p, dim, nn.value, C.byref(nn), _lib.iptr(ns), _lib.iptr(nf), _lib.iptr(par))
     return ns, nf, par
+
+
+# CholKnobs (csrc/chol_plan.hpp) in field order: the environment variable and the default of each
+KNOBS = (("MGB_CHOL_GRAPH", 1), ("MGB_CHOL_PROF", 0), ("MGB_CHOL_LEAF", 1), ("MGB_CHOL_SINGLE", 1), ("MGB_CHOL_STEP2", 1),
+         ("MGB_CHOL_WIDE", 1), ("MGB_CHOL_START_PIVOT", 1), ("MGB_CHOL_STEP2_TILES", 224), ("MGB_CHOL_DENSE_TILES", 512),
+         ("MGB_BWD_SPLIT_NF", 192), ("MGB_CHOL_BWD_FUSED", 1), ("MGB_CHOL_BWD_CUT", 2), ("MGB_CHOL_BWD_FUSED_NF", 384),
+         ("MGB_CHOL_BWD_FUSED_THREADS", 512), ("MGB_CHOL_PREMAP", 1), ("MGB_CHOL_PREMAP_TILES", 400))
+
+
+def variant_knobs(variant):
+    """the variant's knob values as {environment variable: int}, defaults filled in (MGB_LEAF is not a chain knob)"""
+    return {name: int(VARIANTS[variant].get(name, dflt)) for name, dflt in KNOBS}
+
+
+def plan_schedule(p, dim, knobs=None, world=1, rank=0):
+    """The host plan of the device chain (mgb_plan_chol_schedule).  knobs: None (the values this process reads from the
+    environment) or a dict as variant_knobs() gives.  Per launch: kind (name), ofs, cnt, block, lds, p, npiv, rect,
+    consumer, producers; the job arrays; own_bwd / top_fwd; world (what the tree was split over)."""
+    from mgb_amd import _lib
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    kn = None if knobs is None else np.array([knobs[name] for name, _ in KNOBS], dtype=np.int32)
+    info = np.zeros(10, dtype=np.int32)
+    head = (p, dim, None if kn is None else ip(kn), world, rank, ip(info))
+    _lib.call("mgb_plan_chol_schedule", *head, 0, None, 0, None, 0, None, 0, None, 0, None, 0, None, 0, None, None)
+    nl, own_bwd, top_fwd, nlists, nstarts, ntiles, nsingles, nrects, nasm, split = (int(v) for v in info)
+    launch = np.zeros((nl, 10), dtype=np.int32)
+    lists, apos, asrc = np.zeros(nlists, dtype=np.int32), np.zeros(nasm, dtype=np.int32), np.zeros(nasm, dtype=np.int32)
+    starts, tiles = np.zeros((nstarts, 5), dtype=np.int32), np.zeros((ntiles, 3), dtype=np.int32)
+    singles, rects = np.zeros((nsingles, 3), dtype=np.int32), np.zeros((nrects, 2), dtype=np.int32)
+    _lib.call("mgb_plan_chol_schedule", *head, nl, ip(launch), nlists, ip(lists), nstarts, ip(starts), ntiles, ip(tiles), nsingles,
+              ip(singles), nrects, ip(rects), nasm, ip(apos), ip(asrc))
+    names = ("ofs", "cnt", "block", "lds", "p", "npiv", "rect", "consumer", "producers")
+    out = {n: launch[:, i + 1] for i, n in enumerate(names)}
+    out.update(kinds=[KINDS[k] for k in launch[:, 0]], own_bwd=own_bwd, top_fwd=top_fwd, lists=lists, starts=starts, tiles=tiles,
+               singles=singles, rects=rects, apos=apos, asrc=asrc, world=split)
+    return out
 
 
 def free_plan(h, p):

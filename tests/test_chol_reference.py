@@ -25,7 +25,7 @@ def test_chol_kind_table_covers_every_kind():
     documented = re.findall(r"(\d+) (\w+)", block)
     assert [int(c) for c, _ in documented] == list(range(14))
     assert tuple(n for _, n in documented) == R.KINDS == M.AMG.CHOL_KINDS
-    with open(os.path.join(ROOT, "multigridbarriermpi.jl_amd", "csrc", "gpuchol.hpp")) as f:
+    with open(os.path.join(ROOT, "multigridbarriermpi.jl_amd", "csrc", "chol_plan.hpp")) as f:
         enum = re.search(r"enum class Kind : unsigned char \{([^}]*)\}", f.read()).group(1)
     assert tuple(k.strip() for k in enum.split(",") if k.strip()) == R.KINDS
     covered = set()

@@ -72,6 +72,10 @@ else:
     sched = A.chol_schedule(l)
     res.update(kinds=np.array(sched["kinds"]), workgroups=sched["workgroups"])
     if mode == "solve":
+        hg, hp, hdim, _, _ = R.plan(kind, L)      # the host plan of the same tree, knobs from this process's environment
+        host = R.plan_schedule(hp, hdim)
+        R.free_plan(hg, hp)
+        res.update(host_kinds=np.array(host["kinds"]), host_workgroups=host["cnt"])
         def solve(vals, g):             # a pivot flagged on these SPD matrices is a failure of that case: NaN, not an exit
             try:
                 return A.solve_linear(l, vals, g, solver="gpu")
@@ -138,6 +142,11 @@ def _coverage(got, must, never):
     return sorted(set(must) - kinds), sorted(set(never) & kinds)
 
 
+def _host_plan_differs(got):
+    """the host plan (mgb_plan_chol_schedule, taken in the child) against AMG.chol_schedule(): kinds and workgroups"""
+    return not (np.array_equal(got["host_kinds"], got["kinds"]) and np.array_equal(got["host_workgroups"], got["workgroups"]))
+
+
 _WORKLOADS = {}
 
 
@@ -171,6 +180,8 @@ def test_every_launch_kind_meets_the_reference(gpu_required, tmp_path_factory, k
         sched = _schedule_text(got)
         if missing or present:
             failures.append("%s L=%d %s: schedule lacks %s / has %s (%s)" % (kind, L, variant, missing, present, sched))
+        if _host_plan_differs(got):
+            failures.append("%s L=%d %s: the host plan differs from the device schedule (%s)" % (kind, L, variant, sched))
         for mi, m in enumerate(w["mats"]):
             ref, sols = w["refs"][m]
             for k, g in enumerate(w["rhs"]):
@@ -214,6 +225,8 @@ def test_largest_sizes_meet_the_backward_error_bound(gpu_required, tmp_path, kin
         sched = _schedule_text(got)
         if missing or present:
             failures.append("%s L=%d %s: schedule lacks %s / has %s (%s)" % (kind, L, variant, missing, present, sched))
+        if _host_plan_differs(got):
+            failures.append("%s L=%d %s: the host plan differs from the device schedule (%s)" % (kind, L, variant, sched))
         for k, g in enumerate(rhs):
             x = got["x"][0, k]
             eta = ref.eta(x, g)

@@ -54,6 +54,10 @@ else:
     sched = A.chol_schedule(l)
     res.update(kinds=np.array(sched["kinds"]), workgroups=sched["workgroups"], consumer=sched["premap_consumer"],
                producers=sched["premap_producers"], slab_bytes=A.chol_info(l)["slab_bytes"])
+    hg, hp, hdim, _, _ = R.plan(kind, L)      # the host plan of the same tree, knobs from this process's environment
+    host = R.plan_schedule(hp, hdim)
+    R.free_plan(hg, hp)
+    res.update(host_consumer=host["consumer"].astype(bool), host_producers=host["producers"])
     if mode == "solve":
         res["x"] = np.array([[A.solve_linear(l, data["m_" + m], g, solver="gpu") for g in rhs] for m in "ac"])
     else:                               # replay: the same level buffers and slabs, new values each time
@@ -120,7 +124,9 @@ def _workload(tmp_path_factory, kind, L, env):
 
 
 def _first_launches(got):
-    """(kind, consumer, producers) of the first launch of every height, leaves first"""
+    """(kind, consumer, producers) of the first launch of every height, leaves first; the host plan (mgb_plan_chol_schedule,
+    taken in the child) must report the same consumers and producers as AMG.chol_schedule()"""
+    assert np.array_equal(got["host_consumer"], got["consumer"]) and np.array_equal(got["host_producers"], got["producers"])
     return [(str(k), bool(c), int(p)) for k, c, p in zip(got["kinds"], got["consumer"], got["producers"]) if str(k) in _FIRST]
 
 
