@@ -31,11 +31,16 @@ __device__ inline unsigned xcd_block(unsigned b, unsigned nb) {
 }
 
 // ---------------------------------------------------------------- reductions
-__device__ inline double wave_sum(double v) {
+// THE shuffle tree: lane j of every aligned group of G lanes adds lane j + o, o = G/2 .. 1; the group's sum lands in its lane 0.
+// Every row sum and every block sum of the Newton path goes through it, so two kernels that feed it the same values in the same
+// lanes get the same bits.
+template <int G, class T>
+__device__ inline T group_sum(T v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  for (int o = G / 2; o > 0; o >>= 1) v += __shfl_down(v, o, G);
   return v;
 }
+__device__ inline double wave_sum(double v) { return group_sum<64>(v); }
 
 // sum over the block in a fixed order; result valid in thread 0
 __device__ inline double block_sum(double v, double* lds) {
@@ -81,14 +86,17 @@ __device__ inline void block_sum_n(const double (&v)[N], double (&out)[N]) {
 // measured), so the ticket is two-level: 8 shard counters (block id mod 8: one XCD each under round-robin placement, for
 // speed only) on cache lines of their own, whose last arrivers meet on a top counter.
 // scratch layout: kTicketDoubles doubles of ticket words (zero between launches), then the partials.
-// out_dev / out_host (either may be null): device result for a following collective, pinned host memory for the host.
+// The ticket and the read-back exist once, in grid_finish_fn; grid_finish is that plus the stores of the sums.
 constexpr int kTicketDoubles = kReductionHeader;      // 9 counters, one 128-byte line each (atomics on one line serialise)
 constexpr int kTicketStride = 32;                     // unsigned words per line
 static_assert(kReductionHeader * sizeof(double) >= 9 * kTicketStride * sizeof(unsigned), "ticket words");
-template <int NOUT>
-__device__ inline void grid_finish(const double (&r)[NOUT] /* valid in thread 0 */, double* scratch, double* out_dev,
-                                   double* out_host, double* lds, HostSignal sig = HostSignal(), unsigned slot = 0xffffffffu) {
-  if (slot == 0xffffffffu) slot = blockIdx.x;      // position of this block's partial in the fixed summation order
+// grid_finish_fn: `fn(tot)` runs in thread 0 of the last block with the NOUT sums, e.g. to turn two dots into a step length that
+// the next launch reads from device memory -- no host round trip inside a Krylov iteration.  `slot` is the position of this
+// block's partial in the fixed summation order (default: the block id).
+template <int NOUT, class Fn>
+__device__ inline void grid_finish_fn(const double (&r)[NOUT] /* valid in thread 0 */, double* scratch, Fn&& fn,
+                                      unsigned slot = 0xffffffffu) {
+  if (slot == 0xffffffffu) slot = blockIdx.x;
   __shared__ int is_last;
   unsigned* ticket = reinterpret_cast<unsigned*>(scratch);      // counter k lives at ticket[kTicketStride * k]: a 128-byte line each
   double* partials = scratch + kTicketDoubles;
@@ -130,65 +138,61 @@ __device__ inline void grid_finish(const double (&r)[NOUT] /* valid in thread 0 
   }
   double tot[NOUT];
   block_sum_n<NOUT>(acc, tot);
-  (void)lds;
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0) fn(tot);
+}
+
+// Tell a polling host that this launch's results are in pinned memory; run by ONE thread of the launch, after its result stores
+// (drained here): bump the device counter, then release-store the new value where the host polls.
+__device__ inline void host_signal(const HostSignal& sig) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const unsigned long long q = __hip_atomic_load(sig.seq_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+  __hip_atomic_store(sig.seq_dev, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(sig.seq_host, q, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// grid_finish: the sums go to out_dev / out_host (either may be null: device result for a following collective, pinned host
+// memory for the host), then the host is signalled.
+template <int NOUT>
+__device__ inline void grid_finish(const double (&r)[NOUT] /* valid in thread 0 */, double* scratch, double* out_dev,
+                                   double* out_host, HostSignal sig = HostSignal(), unsigned slot = 0xffffffffu) {
+  grid_finish_fn<NOUT>(
+      r, scratch,
+      [&](const double (&tot)[NOUT]) {
 #pragma unroll
-    for (int o = 0; o < NOUT; ++o) {
-      if (out_dev) out_dev[o] = tot[o];
-      if (out_host) __hip_atomic_store(&out_host[o], tot[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-  if (sig.seq_host && threadIdx.x == 0) {      // results first (drained), then the sequence number the host polls
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long q = __hip_atomic_load(sig.seq_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-    __hip_atomic_store(sig.seq_dev, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(sig.seq_host, q, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        for (int o = 0; o < NOUT; ++o) {
+          if (out_dev) out_dev[o] = tot[o];
+          if (out_host) __hip_atomic_store(&out_host[o], tot[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        if (sig.seq_host) host_signal(sig);      // results first, then the sequence number the host polls
+      },
+      slot);
+}
+
+// ---------------------------------------------------------------- runtime value -> template argument
+// f.template operator()<G>() for the lane-group width of a CSR matrix (DevCsr::group) / the threads per element of an element
+// operator (DevElOp::tpe); an unknown value runs the widest instantiation.  Returns what f returns.
+template <class F>
+inline decltype(auto) dispatch_group(int group, F&& f) {
+  switch (group) {
+    case 1: return f.template operator()<1>();
+    case 2: return f.template operator()<2>();
+    case 4: return f.template operator()<4>();
+    case 8: return f.template operator()<8>();
+    case 16: return f.template operator()<16>();
+    case 32: return f.template operator()<32>();
+    default: return f.template operator()<64>();
   }
 }
-// The same hand-off with the finishing arithmetic left to the caller: `fn(tot)` runs in thread 0 of the last block with the
-// NOUT sums (fixed summation order, as grid_finish), e.g. to turn two dots into a step length that the next launch reads
-// from device memory -- no host round trip inside a Krylov iteration.
-template <int NOUT, class Fn>
-__device__ inline void grid_finish_fn(const double (&r)[NOUT] /* valid in thread 0 */, double* scratch, double* lds, Fn&& fn) {
-  __shared__ int is_last_fn;
-  unsigned* ticket = reinterpret_cast<unsigned*>(scratch);
-  double* partials = scratch + kTicketDoubles;
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o)
-      __hip_atomic_store(&partials[(size_t)blockIdx.x * NOUT + o], r[o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned shard = blockIdx.x & 7u, nshards = gridDim.x < 8u ? gridDim.x : 8u;
-    const unsigned in_shard = (gridDim.x - shard + 7u) / 8u;
-    bool last = false;
-    if (__hip_atomic_fetch_add(&ticket[kTicketStride * shard], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == in_shard - 1) {
-      __hip_atomic_store(&ticket[kTicketStride * shard], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last = __hip_atomic_fetch_add(&ticket[kTicketStride * 8], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nshards - 1;
-      if (last) __hip_atomic_store(&ticket[kTicketStride * 8], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    is_last_fn = last;
+template <class F>
+inline decltype(auto) dispatch_tpe(int tpe, F&& f) {
+  switch (tpe) {
+    case 8: return f.template operator()<8>();
+    case 16: return f.template operator()<16>();
+    case 32: return f.template operator()<32>();
+    case 64: return f.template operator()<64>();
+    case 128: return f.template operator()<128>();
+    default: return f.template operator()<256>();
   }
-  __syncthreads();
-  if (!is_last_fn) return;      // workgroup-uniform
-  double tot[NOUT], acc[NOUT];
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) acc[o] = 0.0;
-  for (int i0 = threadIdx.x; i0 < (int)gridDim.x; i0 += 4 * kBlock) {      // one round trip per batch of 4 NOUT loads (see grid_finish)
-    double v[4][NOUT];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = min(i0 + u * kBlock, (int)gridDim.x - 1);
-#pragma unroll
-      for (int o = 0; o < NOUT; ++o) v[u][o] = __hip_atomic_load(&partials[(size_t)i * NOUT + o], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int o = 0; o < NOUT; ++o) acc[o] = (i0 + u * kBlock < (int)gridDim.x) ? acc[o] + v[u][o] : acc[o];
-  }
-  block_sum_n<NOUT>(acc, tot);
-  (void)lds;
-  if (threadIdx.x == 0) fn(tot);
 }
 
 }  // namespace

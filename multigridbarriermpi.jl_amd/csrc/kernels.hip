@@ -18,25 +18,19 @@ namespace mgb {
 
 namespace {
 
-
 // ---------------------------------------------------------------- SpMV
-// y = (y0 ? y0 : 0) + A x: the double instantiation of spmv_kernel_t (kernels_tpl.hpp)
-template <int G>
-void spmv_launch(hipStream_t st, const DevCsr& A, const double* x, const double* y0, double* y) {
-  const int grid = grid_for((long long)A.rows * G);     // small problems keep one row per lane group
-  hipLaunchKernelGGL((spmv_kernel_t<G, double>), dim3(grid), dim3(kBlock), 0, st, A.rows, A.rowptr, A.colidx, A.vals, x, y0, y);
-}
-
+// y = (y0 ? y0 : 0) + A x is spmv_t<double> (kernels_tpl.hpp)
+//
 // Element-local SpMV (DevElCsr): a workgroup takes kElPerBlock consecutive elements per pass, stages their x entries in LDS
 // (thread = (element, column slot): consecutive threads read consecutive ecols entries -- coalesced -- and gather x once per
-// element column), then every lane group forms its row exactly as spmv_kernel<G> does: lane j adds nonzeros j, j + G, ...,
-// fixed shuffle tree -- bitwise the same y.  bytes = nnz * 9 + (rows + 1) * 4 + nel * cmax * 12 + rows * 16.
+// element column), then every lane group forms its rows through row_sums<G>, the pipeline of spmv_kernel_t, with x read from LDS
+// -- bitwise the same y.  bytes = nnz * 9 + (rows + 1) * 4 + nel * cmax * 12 + rows * 16.
 template <int G>
 __global__ __launch_bounds__(kBlock) void spmv_el_kernel(int rows, DevElCsr E, const int* __restrict__ rowptr,
                                                           const double* __restrict__ vals, const double* __restrict__ x,
                                                           const double* y0, double* y) {
   extern __shared__ double xs[];      // els_per_pass x cmax
-  const int lane = threadIdx.x % G, grp = threadIdx.x / G;
+  const int grp = threadIdx.x / G;
   constexpr int GR = kBlock / G;
   const int rpe = E.rows_per_el;
   const int els = max(1, min(E.nel, (kBlock * 4) / rpe));      // elements per pass: ~1024 rows
@@ -49,51 +43,34 @@ __global__ __launch_bounds__(kBlock) void spmv_el_kernel(int rows, DevElCsr E, c
     const long long r0 = (long long)e0 * rpe;
     const int nrows = (int)min((long long)ne * rpe, (long long)rows - r0);
     for (int rr0 = grp; rr0 < nrows; rr0 += kSpmvU * GR) {
-      int b[kSpmvU], e[kSpmvU];
-      double acc[kSpmvU], base[kSpmvU];
+      const double* xe[kSpmvU];      // the x entries of the element each row belongs to
 #pragma unroll
-      for (int u = 0; u < kSpmvU; ++u) {
-        const int rr = rr0 + u * GR;
-        const bool ok = rr < nrows;
-        b[u] = ok ? rowptr[r0 + rr] : 0;
-        e[u] = ok ? rowptr[r0 + rr + 1] : 0;
-        base[u] = (ok && y0 && lane == 0) ? y0[r0 + rr] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < kSpmvU; ++u) {
-        const int rr = rr0 + u * GR;
-        const double* xe = xs + (rr / rpe) * E.cmax;
-        const int k = b[u] + lane;
-        acc[u] = (k < e[u]) ? vals[k] * xe[E.lcol[k]] : 0.0;
-        for (int kk = k + G; kk < e[u]; kk += G) acc[u] += vals[kk] * xe[E.lcol[kk]];
-      }
-#pragma unroll
-      for (int u = 0; u < kSpmvU; ++u) {
-        double a = acc[u];
-#pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) a += __shfl_down(a, o, G);
-        const int rr = rr0 + u * GR;
-        if (lane == 0 && rr < nrows) y[r0 + rr] = base[u] + a;
-      }
+      for (int u = 0; u < kSpmvU; ++u) xe[u] = xs + ((rr0 + u * GR) / rpe) * E.cmax;
+      row_sums<G, double>(r0, rr0, GR, nrows, rowptr, E.lcol, vals, y0, [&](int c, int u) { return xe[u][c]; },
+                          [&](int rr, double v) { y[r0 + rr] = v; });
     }
   }
 }
 
-template <int G>
-void spmv_el_launch(hipStream_t st, const DevCsr& A, const DevElCsr& E, const double* x, const double* y0, double* y) {
-  const int els = std::max(1, std::min(E.nel, (kBlock * 4) / E.rows_per_el));
-  const int npass = (E.nel + els - 1) / els;
-  const int grid = std::max(1, std::min(npass, kMaxBlocks * 4));
-  hipLaunchKernelGGL(spmv_el_kernel<G>, dim3(grid), dim3(kBlock), (size_t)els * E.cmax * sizeof(double), st, A.rows, E, A.rowptr,
-                     A.vals, x, y0, y);
-}
+struct SpmvElLaunch {
+  hipStream_t st;
+  const DevCsr& A;
+  const DevElCsr& E;
+  const double *x, *y0;
+  double* y;
+  template <int G>
+  void operator()() const {
+    const int els = std::max(1, std::min(E.nel, (kBlock * 4) / E.rows_per_el));
+    const int npass = (E.nel + els - 1) / els;
+    const int grid = std::max(1, std::min(npass, kMaxBlocks * 4));
+    hipLaunchKernelGGL(spmv_el_kernel<G>, dim3(grid), dim3(kBlock), (size_t)els * E.cmax * sizeof(double), st, A.rows, E, A.rowptr,
+                       A.vals, x, y0, y);
+  }
+};
 
 
 // ---------------------------------------------------------------- barrier
-using Cone = ConeT<double>;      // kernels_tpl.hpp: load_cone<double>, pow_a<double>
-
-// phi_ref (nullable, n x ncones): cone distances of every row at the current iterate; a trial row with
-// phi < frac*phi_ref is treated as infeasible (fraction-to-the-boundary rule of the line search).
+// sum_q w F(Dz_q) and sum_q w <c_q, Dz_q>; phi_ref / frac / phi_out as in barrier_value (kernels_tpl.hpp)
 __global__ __launch_bounds__(kBlock) void barrier_f0_kernel(int n, BarrierParams P, const double* __restrict__ Dz,
                                                              const double* __restrict__ w,
                                                              const double* __restrict__ c,
@@ -106,34 +83,25 @@ __global__ __launch_bounds__(kBlock) void barrier_f0_kernel(int n, BarrierParams
     const double* dz = Dz + q * P.K;
     const double* cq = c + q * P.K;
     const double wq = w[q];
-    double F = 0.0;
-    for (int ci = 0; ci < P.ncones; ++ci) {
-      if (!P.active(ci, q)) {      // inactive piece: no constraint at this node
-        if (phi_out) phi_out[q * P.ncones + ci] = INFINITY;
-        continue;
-      }
-      const ConeAM<double> am = cone_am<double>(P, ci, q);
-      Cone k = load_cone<double>(P.cone[ci], dz, am.a);
-      if (phi_ref && !(k.phi >= frac * phi_ref[q * P.ncones + ci])) k.ok = false;
-      if (phi_out) phi_out[q * P.ncones + ci] = k.phi;
-      F += k.ok ? (-log(k.phi) - am.mu * log(k.s)) : INFINITY;
-    }
-    accF += wq * F;
+    accF += wq * barrier_value<double>(P, q, dz, phi_ref, frac, phi_out);
     double lin = 0.0;
     for (int j = 0; j < P.K; ++j) lin += cq[j] * dz[j];
     accL += wq * lin;
   }
   const double r[2] = {block_sum(accF, lds), block_sum(accL, lds)};
-  grid_finish<2>(r, scratch, out_dev, out_host, lds, sig);
+  grid_finish<2>(r, scratch, out_dev, out_host, sig);
 }
 
 
 // One objective evaluation of the line search in ONE launch (reference: f0 = apply_D, then map_rows of the barrier,
 // then two dots -- SURVEY 8a a3/a4): x = s + alpha * nstep is formed on the fly (and written to s_out for the
 // caller that accepts the trial), Dz = Dz0 + B x is computed for 64 nodes (64 K consecutive rows of B) per pass with
-// the lane layout and summation order of spmv_kernel<G> -- bitwise the same Dz -- kept in LDS and written once, and
-// the barrier terms of those nodes are accumulated straight from LDS.  Saves the waxpby and barrier_f0 launches and
+// the lane layout and summation order of row_sums<G> (kernels_tpl.hpp) -- bitwise the same Dz -- kept in LDS and written
+// once, and the barrier terms of those nodes are accumulated straight from LDS.  Saves the waxpby and barrier_f0 launches and
 // the re-read of Dz; bytes = spmv(B) + n (K + 2 + ncones [+ ncones]) 8.
+// The row loop is row_sums written out, with group_sum<G> as its tree: through the shared function this kernel ran 4 to 5 %
+// slower at fem2d L=8 and 9 (profiles/newton_kernels_refactor_bench.txt); tests/test_gpu_linesearch.py holds its Dz to the
+// bits of apply_D.
 constexpr int kTrialNodes = 64;
 // NA = 1..3 trial points x_a = s + alpha_a * nstep share ONE pass over B (each nonzero is read once and feeds NA
 // accumulators; per point the operations and their order are exactly those of the NA = 1 kernel, so every Dz and every sum
@@ -146,7 +114,6 @@ __global__ __launch_bounds__(kBlock) void trial_f0_kernel(int n, int N, BarrierP
                                                            const double* __restrict__ w, const double* __restrict__ c,
                                                            const double* __restrict__ phi_ref, double frac, double* scratch,
                                                            HostSignal sig) {
-  __shared__ double lds[kBlock / 64];
   __shared__ double dzs[NA][kTrialNodes * kMaxK];
   constexpr int GR = kBlock / G;      // rows per pass
   const int K = P.K, lane = threadIdx.x % G, grp = threadIdx.x / G;
@@ -162,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void trial_f0_kernel(int n, int N, BarrierP
   for (int ch = xcd_block(blockIdx.x, gridDim.x); ch < nchunks; ch += gridDim.x) {
     const int q0 = ch * kTrialNodes, nq = min(kTrialNodes, n - q0), nrows = nq * K;
     const long long r0 = (long long)q0 * K;
-    for (int rr0 = grp; rr0 < nrows; rr0 += kSpmvU * GR) {
+    for (int rr0 = grp; rr0 < nrows; rr0 += kSpmvU * GR) {      // row_sums<G> written out for NA points, see above
       int b[kSpmvU], e[kSpmvU], ci[kSpmvU];
       double acc[NA][kSpmvU], base[kSpmvU], va[kSpmvU];
 #pragma unroll
@@ -196,9 +163,7 @@ __global__ __launch_bounds__(kBlock) void trial_f0_kernel(int n, int N, BarrierP
       for (int a = 0; a < NA; ++a)
 #pragma unroll
         for (int u = 0; u < kSpmvU; ++u) {
-          double t = acc[a][u];
-#pragma unroll
-          for (int o = G / 2; o > 0; o >>= 1) t += __shfl_down(t, o, G);
+          const double t = group_sum<G>(acc[a][u]);
           const int rr = rr0 + u * GR;
           if (lane == 0 && rr < nrows) {
             const double v = base[u] + t;
@@ -213,20 +178,7 @@ __global__ __launch_bounds__(kBlock) void trial_f0_kernel(int n, int N, BarrierP
       const double* dz = dzs[pa] + pnode * K;
       const double* cq = c + q * K;
       const double wq = w[q];
-      double* phi_out = T.phi_out[pa];
-      double F = 0.0;
-      for (int ci2 = 0; ci2 < P.ncones; ++ci2) {
-        if (!P.active(ci2, q)) {
-          if (phi_out) phi_out[q * P.ncones + ci2] = INFINITY;
-          continue;
-        }
-        const ConeAM<double> am = cone_am<double>(P, ci2, q);
-        Cone k = load_cone<double>(P.cone[ci2], dz, am.a);
-        if (phi_ref && !(k.phi >= frac * phi_ref[q * P.ncones + ci2])) k.ok = false;
-        if (phi_out) phi_out[q * P.ncones + ci2] = k.phi;
-        F += k.ok ? (-log(k.phi) - am.mu * log(k.s)) : INFINITY;
-      }
-      accF += wq * F;
+      accF += wq * barrier_value<double>(P, q, dz, phi_ref, frac, T.phi_out[pa]);
       double lin = 0.0;
       for (int j = 0; j < K; ++j) lin += cq[j] * dz[j];
       accL += wq * lin;
@@ -243,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void trial_f0_kernel(int n, int N, BarrierP
   block_sum_n<2 * NA>(mine, r);      // one pair of barriers for all the points' sums
   // the partials go to the slot of the chunk sequence this block worked on, so the sums are those of the natural order;
   // results land at T.out_dev[0] .. (2 NA consecutive doubles: the points' (F, c.Dz) pairs) and its pinned host twin
-  grid_finish<2 * NA>(r, scratch, T.out_dev, T.out_host, lds, sig, xcd_block(blockIdx.x, gridDim.x));
+  grid_finish<2 * NA>(r, scratch, T.out_dev, T.out_host, sig, xcd_block(blockIdx.x, gridDim.x));
 }
 
 inline int trial_grid(int n) {
@@ -251,37 +203,39 @@ inline int trial_grid(int n) {
   return b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b);
 }
 
-template <int G>
-void trial_launch(hipStream_t st, const DevCsr& B, int n, const BarrierParams& P, const double* s, const double* nstep,
-                  const TrialSet& T, const double* Dz0, const double* w, const double* c, const double* phi_ref, double frac,
-                  double* scratch, HostSignal sig) {
-#define MGB_TRIAL_NA(NA)                                                                                                    \
-  hipLaunchKernelGGL((trial_f0_kernel<G, NA>), dim3(trial_grid(n)), dim3(kBlock), 0, st, n, B.cols, P, B.rowptr, B.colidx,   \
-                     B.vals, s, nstep, T, Dz0, w, c, phi_ref, frac, scratch, sig)
-  switch (T.na) {
-    case 1: MGB_TRIAL_NA(1); break;
-    case 2: MGB_TRIAL_NA(2); break;
-    default: MGB_TRIAL_NA(3); break;
+struct TrialLaunch {
+  hipStream_t st;
+  const DevCsr& B;
+  int n;
+  const BarrierParams& P;
+  const double *s, *nstep;
+  const TrialSet& T;
+  const double *Dz0, *w, *c, *phi_ref;
+  double frac;
+  double* scratch;
+  HostSignal sig;
+  template <int G, int NA>
+  void launch() const {
+    hipLaunchKernelGGL((trial_f0_kernel<G, NA>), dim3(trial_grid(n)), dim3(kBlock), 0, st, n, B.cols, P, B.rowptr, B.colidx, B.vals, s,
+                       nstep, T, Dz0, w, c, phi_ref, frac, scratch, sig);
   }
-#undef MGB_TRIAL_NA
-}
+  template <int G>
+  void operator()() const {
+    switch (T.na) {
+      case 1: launch<G, 1>(); break;
+      case 2: launch<G, 2>(); break;
+      default: launch<G, 3>(); break;
+    }
+  }
+};
 
 // map_rows of the barrier itself (src:161-170 for the closures MultiGridBarrier builds from a convex set): F per row, and the
 // per-row Hessian in the reference's flattened K x K shape (column (j-1) K + k, test/test_map_rows_compare.jl:73) expanded
 // from the packed slots of barrier_f2_kernel.
 __global__ __launch_bounds__(kBlock) void barrier_rows_F_kernel(int n, BarrierParams P, const double* __restrict__ Dz,
                                                                  double* __restrict__ out) {
-  for (long long q = (long long)blockIdx.x * kBlock + threadIdx.x; q < n; q += (long long)gridDim.x * kBlock) {
-    const double* dz = Dz + q * P.K;
-    double F = 0.0;
-    for (int ci = 0; ci < P.ncones; ++ci) {
-      if (!P.active(ci, q)) continue;
-      const ConeAM<double> am = cone_am<double>(P, ci, q);
-      Cone k = load_cone<double>(P.cone[ci], dz, am.a);
-      F += k.ok ? (-log(k.phi) - am.mu * log(k.s)) : INFINITY;
-    }
-    out[q] = F;
-  }
+  for (long long q = (long long)blockIdx.x * kBlock + threadIdx.x; q < n; q += (long long)gridDim.x * kBlock)
+    out[q] = barrier_value<double>(P, q, Dz + q * P.K, nullptr, 0.0, nullptr);
 }
 
 __global__ __launch_bounds__(kBlock) void expand_hessian_rows_kernel(int n, BarrierParams P, const double* __restrict__ Y,
@@ -340,7 +294,7 @@ __global__ __launch_bounds__(kBlock) void dot_kernel(int n, const double* __rest
   for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock)
     acc += x[i] * y[i];
   const double r[1] = {block_sum(acc, lds)};
-  grid_finish<1>(r, scratch, out_dev, out_host, lds, sig);
+  grid_finish<1>(r, scratch, out_dev, out_host, sig);
 }
 
 __global__ __launch_bounds__(kBlock) void dot_owned_kernel(int n, const double* __restrict__ x, const double* __restrict__ y,
@@ -353,7 +307,7 @@ __global__ __launch_bounds__(kBlock) void dot_owned_kernel(int n, const double* 
     if (k == 1 || (k == 2 && count_top)) acc += x[i] * y[i];      // select, never multiply by a mask: the other entries may hold anything
   }
   const double r[1] = {block_sum(acc, lds)};
-  grid_finish<1>(r, scratch, out_dev, nullptr, lds);
+  grid_finish<1>(r, scratch, out_dev, nullptr);
 }
 
 __global__ __launch_bounds__(kBlock) void gather_top_kernel(int ntop, const int* __restrict__ top, const double* __restrict__ g,
@@ -385,7 +339,7 @@ __global__ __launch_bounds__(kBlock) void sum_kernel(int n, const double* __rest
   double acc = 0.0;
   for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) acc += x[i];
   const double r[1] = {block_sum(acc, lds)};
-  grid_finish<1>(r, scratch, out_dev, out_host, lds);
+  grid_finish<1>(r, scratch, out_dev, out_host);
 }
 
 __global__ __launch_bounds__(kBlock) void isfinite_kernel(int n, const double* __restrict__ x, int* flag) {
@@ -398,29 +352,11 @@ __global__ __launch_bounds__(kBlock) void isfinite_kernel(int n, const double* _
 }  // namespace
 
 void launch_spmv(hipStream_t st, const DevCsr& A, const double* x, const double* y0, double* y) {
-  if (A.rows == 0) return;
-  switch (A.group) {
-    case 1: spmv_launch<1>(st, A, x, y0, y); break;
-    case 2: spmv_launch<2>(st, A, x, y0, y); break;
-    case 4: spmv_launch<4>(st, A, x, y0, y); break;
-    case 8: spmv_launch<8>(st, A, x, y0, y); break;
-    case 16: spmv_launch<16>(st, A, x, y0, y); break;
-    case 32: spmv_launch<32>(st, A, x, y0, y); break;
-    default: spmv_launch<64>(st, A, x, y0, y); break;
-  }
+  spmv_t<double>(st, A, A.vals, x, y0, y);
 }
 
 void launch_spmv_el(hipStream_t st, const DevCsr& A, const DevElCsr& E, const double* x, const double* y0, double* y) {
-  if (A.rows == 0) return;
-  switch (A.group) {
-    case 1: spmv_el_launch<1>(st, A, E, x, y0, y); break;
-    case 2: spmv_el_launch<2>(st, A, E, x, y0, y); break;
-    case 4: spmv_el_launch<4>(st, A, E, x, y0, y); break;
-    case 8: spmv_el_launch<8>(st, A, E, x, y0, y); break;
-    case 16: spmv_el_launch<16>(st, A, E, x, y0, y); break;
-    case 32: spmv_el_launch<32>(st, A, E, x, y0, y); break;
-    default: spmv_el_launch<64>(st, A, E, x, y0, y); break;
-  }
+  if (A.rows != 0) dispatch_group(A.group, SpmvElLaunch{st, A, E, x, y0, y});
 }
 
 void launch_waxpby(hipStream_t st, int n, const double* x, double alpha, const double* y, double* out) {
@@ -433,17 +369,7 @@ int f0_blocks(int n) { return std::max(grid_for(n), trial_grid(n)); }
 void launch_trial_set(hipStream_t st, const DevCsr& B, int n, BarrierParams P, const double* s, const double* nstep,
                       const TrialSet& T, const double* Dz0, const double* w, const double* c, const double* phi_ref, double frac,
                       double* scratch, HostSignal sig) {
-#define MGB_TRIAL(G) trial_launch<G>(st, B, n, P, s, nstep, T, Dz0, w, c, phi_ref, frac, scratch, sig)
-  switch (B.group) {
-    case 1: MGB_TRIAL(1); break;
-    case 2: MGB_TRIAL(2); break;
-    case 4: MGB_TRIAL(4); break;
-    case 8: MGB_TRIAL(8); break;
-    case 16: MGB_TRIAL(16); break;
-    case 32: MGB_TRIAL(32); break;
-    default: MGB_TRIAL(64); break;
-  }
-#undef MGB_TRIAL
+  dispatch_group(B.group, TrialLaunch{st, B, n, P, s, nstep, T, Dz0, w, c, phi_ref, frac, scratch, sig});
 }
 
 void launch_trial_f0(hipStream_t st, const DevCsr& B, int n, BarrierParams P, const double* s, double alpha,

@@ -23,26 +23,6 @@ __global__ __launch_bounds__(kBlock) void convert_kernel(long long n, const A* _
   for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) out[i] = (B)in[i];
 }
 
-template <int G, class T>
-void spmv_launch_t(hipStream_t st, const DevCsr& A, const T* vals, const T* x, const T* y0, T* y) {
-  hipLaunchKernelGGL((spmv_kernel_t<G, T>), dim3(grid_for((long long)A.rows * G)), dim3(kBlock), 0, st, A.rows, A.rowptr, A.colidx,
-                     vals, x, y0, y);
-}
-
-template <class T>
-void spmv_t(hipStream_t st, const DevCsr& A, const T* vals, const T* x, const T* y0, T* y) {
-  if (A.rows == 0) return;
-  switch (A.group) {
-    case 1: spmv_launch_t<1, T>(st, A, vals, x, y0, y); break;
-    case 2: spmv_launch_t<2, T>(st, A, vals, x, y0, y); break;
-    case 4: spmv_launch_t<4, T>(st, A, vals, x, y0, y); break;
-    case 8: spmv_launch_t<8, T>(st, A, vals, x, y0, y); break;
-    case 16: spmv_launch_t<16, T>(st, A, vals, x, y0, y); break;
-    case 32: spmv_launch_t<32, T>(st, A, vals, x, y0, y); break;
-    default: spmv_launch_t<64, T>(st, A, vals, x, y0, y); break;
-  }
-}
-
 }  // namespace
 
 void launch_spmv_f32(hipStream_t st, const DevCsr& A, const float* vals, const float* x, const float* y0, float* y) {

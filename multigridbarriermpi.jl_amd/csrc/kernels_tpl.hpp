@@ -12,51 +12,77 @@ namespace {
 constexpr int kMaxK = 8;      // rows of D (capi.cpp rejects larger problems for the barrier kernels)
 
 // G lanes cooperate on one row: lane j reads nonzero j, j+G, ... (coalesced across the group and, because consecutive rows are
-// adjacent in CSR storage, across the 64/G rows of a wave); the G partial sums are combined with a fixed-order shuffle tree
-// -> bitwise reproducible.  kSpmvU rows are in flight per lane group (memory-level parallelism of the dependent
+// adjacent in CSR storage, across the 64/G rows of a wave); the G partial sums are combined with the fixed-order shuffle tree
+// (group_sum) -> bitwise reproducible.  kSpmvU rows are in flight per lane group (memory-level parallelism of the dependent
 // rowptr -> nonzero -> x chain).
 constexpr int kSpmvU = 2;
+
+// THE row pipeline of the CSR products on the Newton path (spmv_kernel_t, spmv_el_kernel; trial_f0_kernel restates it for its
+// NA points, see there): rows r0 + row0 + u step, u < kSpmvU, of the nrows rows from r0 on; per row the sum over its nonzeros k
+// of vals[k] * xv(col[k], u) -- the first nonzero of each lane predicated (its loads go out for all rows before anything
+// waits), the tail strided by G -- reduced by group_sum<G>; lane 0 hands base0[r0 + row] + sum (base0 nullable) to
+// store(row, value), row counted from r0.  A kernel chooses where x comes from, never how a row is summed: same nonzeros, same x
+// -> same bits.
+template <int G, class T, class I, class C, class XV, class Store>
+__device__ inline void row_sums(long long r0, I row0, I step, I nrows, const int* __restrict__ rowptr, const C* __restrict__ col,
+                                const T* __restrict__ vals, const T* base0, XV&& xv, Store&& store) {
+  const int lane = threadIdx.x % G;
+  int b[kSpmvU], e[kSpmvU], ci[kSpmvU];
+  T acc[kSpmvU], base[kSpmvU], va[kSpmvU];
+#pragma unroll
+  for (int u = 0; u < kSpmvU; ++u) {
+    const I row = row0 + u * step;
+    const bool ok = row < nrows;
+    b[u] = ok ? rowptr[r0 + row] : 0;
+    e[u] = ok ? rowptr[r0 + row + 1] : 0;
+    base[u] = (ok && base0 && lane == 0) ? base0[r0 + row] : T(0);
+  }
+#pragma unroll
+  for (int u = 0; u < kSpmvU; ++u) {
+    const int k = b[u] + lane;
+    const bool in = k < e[u];
+    ci[u] = in ? (int)col[k] : -1;
+    va[u] = in ? vals[k] : T(0);
+  }
+#pragma unroll
+  for (int u = 0; u < kSpmvU; ++u) acc[u] = (ci[u] >= 0) ? va[u] * xv(ci[u], u) : T(0);
+#pragma unroll
+  for (int u = 0; u < kSpmvU; ++u)
+    for (int k = b[u] + lane + G; k < e[u]; k += G) acc[u] += vals[k] * xv((int)col[k], u);
+#pragma unroll
+  for (int u = 0; u < kSpmvU; ++u) {
+    const T t = group_sum<G>(acc[u]);
+    const I row = row0 + u * step;
+    if (lane == 0 && row < nrows) store(row, base[u] + t);
+  }
+}
+
 template <int G, class T>
 __global__ __launch_bounds__(kBlock) void spmv_kernel_t(int rows, const int* __restrict__ rowptr, const int* __restrict__ colidx,
                                                          const T* __restrict__ vals, const T* __restrict__ x, const T* y0, T* y) {
-  const int lane = threadIdx.x % G;
   const long long stride = (long long)gridDim.x * (kBlock / G);
   for (long long row0 = (long long)xcd_block(blockIdx.x, gridDim.x) * (kBlock / G) + threadIdx.x / G; row0 < rows;
-       row0 += kSpmvU * stride) {
-    int b[kSpmvU], e[kSpmvU];
-    T acc[kSpmvU], base[kSpmvU];
-#pragma unroll
-    for (int u = 0; u < kSpmvU; ++u) {
-      const long long row = row0 + u * stride;
-      const bool ok = row < rows;
-      b[u] = ok ? rowptr[row] : 0;
-      e[u] = ok ? rowptr[row + 1] : 0;
-      base[u] = (ok && y0 && lane == 0) ? y0[row] : T(0);
-      acc[u] = T(0);
-    }
-    int ci[kSpmvU];
-    T va[kSpmvU];
-#pragma unroll
-    for (int u = 0; u < kSpmvU; ++u) {
-      const int k = b[u] + lane;
-      const bool in = k < e[u];
-      ci[u] = in ? colidx[k] : -1;
-      va[u] = in ? vals[k] : T(0);
-    }
-#pragma unroll
-    for (int u = 0; u < kSpmvU; ++u) acc[u] = (ci[u] >= 0) ? va[u] * x[ci[u]] : T(0);
-#pragma unroll
-    for (int u = 0; u < kSpmvU; ++u)
-      for (int k = b[u] + lane + G; k < e[u]; k += G) acc[u] += vals[k] * x[colidx[k]];
-#pragma unroll
-    for (int u = 0; u < kSpmvU; ++u) {
-      T a = acc[u];
-#pragma unroll
-      for (int o = G / 2; o > 0; o >>= 1) a += __shfl_down(a, o, G);
-      const long long row = row0 + u * stride;
-      if (lane == 0 && row < rows) y[row] = base[u] + a;
-    }
+       row0 += kSpmvU * stride)
+    row_sums<G, T>(0, row0, stride, (long long)rows, rowptr, colidx, vals, y0, [&](int c, int) { return x[c]; },
+                   [&](long long row, T v) { y[row] = v; });
+}
+
+// y = (y0 ? y0 : 0) + A x with A.group lanes per row; small problems keep one row per lane group
+template <class T>
+struct SpmvLaunch {
+  hipStream_t st;
+  const DevCsr& A;
+  const T *vals, *x, *y0;
+  T* y;
+  template <int G>
+  void operator()() const {
+    hipLaunchKernelGGL((spmv_kernel_t<G, T>), dim3(grid_for((long long)A.rows * G)), dim3(kBlock), 0, st, A.rows, A.rowptr, A.colidx,
+                       vals, x, y0, y);
   }
+};
+template <class T>
+void spmv_t(hipStream_t st, const DevCsr& A, const T* vals, const T* x, const T* y0, T* y) {
+  if (A.rows != 0) dispatch_group(A.group, SpmvLaunch<T>{st, A, vals, x, y0, y});
 }
 
 template <class T>
@@ -121,6 +147,27 @@ __device__ inline T pick3(const T (&q)[3], int i) {
   return i == 0 ? q[0] : (i == 1 ? q[1] : q[2]);
 }
 
+// F of row q: the sum of the barrier's terms at dz, +inf outside the domain.  phi_ref (nullable, n x ncones) holds the cone
+// distances of every row at the current iterate: a term with phi < frac * phi_ref counts as infeasible (fraction-to-the-boundary
+// rule of the line search).  phi_out (nullable, n x ncones) receives this evaluation's distances, +inf for an inactive term.
+// Every kernel that needs F calls this, so values from different launches compare as values of one function.
+template <class T>
+__device__ inline T barrier_value(const BarrierParams& P, long long q, const T* dz, const T* phi_ref, T frac, T* phi_out) {
+  T F = T(0);
+  for (int ci = 0; ci < P.ncones; ++ci) {
+    if (!P.active(ci, q)) {      // inactive piece: no constraint at this node
+      if (phi_out) phi_out[q * P.ncones + ci] = T(INFINITY);
+      continue;
+    }
+    const ConeAM<T> am = cone_am<T>(P, ci, q);
+    ConeT<T> k = load_cone<T>(P.cone[ci], dz, am.a);
+    if (phi_ref && !(k.phi >= frac * phi_ref[q * P.ncones + ci])) k.ok = false;
+    if (phi_out) phi_out[q * P.ncones + ci] = k.phi;
+    F += k.ok ? (-log(k.phi) - am.mu * log(k.s)) : T(INFINITY);
+  }
+  return F;
+}
+
 // per row: w F(Dz) and w <c, Dz> (double outputs: the sums over the rows are formed in double by the caller's reduction)
 template <class T>
 __global__ __launch_bounds__(kBlock) void barrier_f0_rows_kernel_t(int n, BarrierParams P, const T* __restrict__ Dz,
@@ -128,13 +175,7 @@ __global__ __launch_bounds__(kBlock) void barrier_f0_rows_kernel_t(int n, Barrie
                                                                     double* __restrict__ outF, double* __restrict__ outC) {
   for (long long q = (long long)blockIdx.x * kBlock + threadIdx.x; q < n; q += (long long)gridDim.x * kBlock) {
     const T* dz = Dz + q * P.K;
-    T F = T(0);
-    for (int ci = 0; ci < P.ncones; ++ci) {
-      if (!P.active(ci, q)) continue;
-      const ConeAM<T> am = cone_am<T>(P, ci, q);
-      const ConeT<T> k = load_cone<T>(P.cone[ci], dz, am.a);
-      F += k.ok ? (-log(k.phi) - am.mu * log(k.s)) : T(INFINITY);
-    }
+    const T F = barrier_value<T>(P, q, dz, nullptr, T(0), nullptr);
     T cd = T(0);
 #pragma unroll
     for (int j = 0; j < kMaxK; ++j) cd += (j < P.K) ? c[q * P.K + j] * dz[j] : T(0);
@@ -237,7 +278,6 @@ __global__ __launch_bounds__(kBlock) void barrier_f2_kernel_t(int n, BarrierPara
     }
   }
 }
-
 
 }  // namespace
 }  // namespace mgb

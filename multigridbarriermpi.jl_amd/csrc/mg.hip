@@ -339,11 +339,11 @@ __global__ __launch_bounds__(kBlock) void dof_gather_kernel(DevElOp E, const dou
   }
   if (epi.mode == MG_PAP || epi.mode == MG_POWER) {
     const double r[1] = {block_sum(acc, lds)};
-    grid_finish_fn<1>(r, epi.scratch, lds, [&](const double (&tot)[1]) { mg_finish_scalars(epi, tot[0]); });
+    grid_finish_fn<1>(r, epi.scratch, [&](const double (&tot)[1]) { mg_finish_scalars(epi, tot[0]); });
   }
 }
 
-// assembled level: G lanes per row as spmv_kernel<G> (fixed shuffle tree), epilogue by lane 0
+// assembled level: G lanes per row, combined by group_sum<G> as in spmv_kernel_t; epilogue by lane 0
 template <int G>
 __global__ __launch_bounds__(kBlock) void csr_apply_kernel(int rows, const int* __restrict__ rowptr, const int* __restrict__ colidx,
                                                             const double* __restrict__ vals, MgEpi epi) {
@@ -361,13 +361,12 @@ __global__ __launch_bounds__(kBlock) void csr_apply_kernel(int rows, const int* 
       if (epi.vmul) x *= epi.vmul[j];
       acc += vals[k] * x;
     }
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) acc += __shfl_down(acc, o, G);
+    acc = group_sum<G>(acc);
     if (lane == 0) racc += mg_epilogue(epi, (int)row, vsc * acc);
   }
   if (epi.mode == MG_PAP || epi.mode == MG_POWER) {
     const double r[1] = {block_sum(racc, lds)};
-    grid_finish_fn<1>(r, epi.scratch, lds, [&](const double (&tot)[1]) { mg_finish_scalars(epi, tot[0]); });
+    grid_finish_fn<1>(r, epi.scratch, [&](const double (&tot)[1]) { mg_finish_scalars(epi, tot[0]); });
   }
 }
 
@@ -402,7 +401,7 @@ __global__ __launch_bounds__(kBlock) void power_start_kernel(int n, const double
   double acc = 0.0;
   for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) acc += ev[i] * ev[i] / dinv[i];
   const double r[1] = {block_sum(acc, lds)};
-  grid_finish_fn<1>(r, scratch, lds, [&](const double (&tot)[1]) { scal[SC_VSCALE] = tot[0] > 0.0 ? 1.0 / sqrt(tot[0]) : 0.0; });
+  grid_finish_fn<1>(r, scratch, [&](const double (&tot)[1]) { scal[SC_VSCALE] = tot[0] > 0.0 ? 1.0 / sqrt(tot[0]) : 0.0; });
 }
 
 // In-place Gauss-Jordan inversion of an SPD matrix in LDS (no pivoting: the pivots of an SPD matrix are positive), one workgroup.
@@ -494,20 +493,14 @@ __global__ __launch_bounds__(kBlock) void pcg_update_kernel(int n, double* __res
 __global__ __launch_bounds__(kBlock) void pcg_dot_kernel(int n, const double* __restrict__ r, const double* __restrict__ z, double* scal,
                                                           double* scratch, double* host4, HostSignal sig) {
   __shared__ double lds[kBlock / 64];
-  auto signal = [&]() {      // thread 0 of one block
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long q = __hip_atomic_load(sig.seq_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-    __hip_atomic_store(sig.seq_dev, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(sig.seq_host, q, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  };
   if (scal[SC_DONE] != 0.0) {      // finished earlier in this batch: nothing moves, the host still gets its signal
-    if (sig.seq_host && blockIdx.x == 0 && threadIdx.x == 0) signal();
+    if (sig.seq_host && blockIdx.x == 0 && threadIdx.x == 0) host_signal(sig);
     return;
   }
   double acc = 0.0;
   for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) acc += r[i] * z[i];
   const double rr[1] = {block_sum(acc, lds)};
-  grid_finish_fn<1>(rr, scratch, lds, [&](const double (&tot)[1]) {
+  grid_finish_fn<1>(rr, scratch, [&](const double (&tot)[1]) {
     const double rz = tot[0];
     const double it = scal[SC_ITER] + 1.0;
     double done = 0.0;
@@ -530,7 +523,7 @@ __global__ __launch_bounds__(kBlock) void pcg_dot_kernel(int n, const double* __
       __hip_atomic_store(&host4[2], rz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(&host4[3], scal[SC_RZ0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    if (sig.seq_host) signal();
+    if (sig.seq_host) host_signal(sig);
   });
 }
 
@@ -568,52 +561,75 @@ YList make_ylist(const BarrierParams& P) {
 
 // persistent workgroups: as many as are resident on the device at once (occupancy query: LDS and registers), each walking
 // its share of the passes with the next pass's loads in flight behind the current one's arithmetic
-template <int TPE>
-int elop_grid(const DevElOp& E) {
-  static const int ncu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  constexpr int epb = kBlock / TPE;
-  const int npass = (E.nel + epb - 1) / epb;
-  const size_t lds = (size_t)epb * E.slot_doubles * sizeof(double);
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, elop_apply_kernel<TPE>, kBlock, lds) != hipSuccess || per_cu < 1)
-    per_cu = 2;
-  return std::max(1, std::min(npass, ncu * per_cu));
-}
-
-int elop_grid_of(const DevElOp& E) {
-  switch (E.tpe) {
-    case 8: return elop_grid<8>(E);
-    case 16: return elop_grid<16>(E);
-    case 32: return elop_grid<32>(E);
-    case 64: return elop_grid<64>(E);
-    case 128: return elop_grid<128>(E);
-    default: return elop_grid<256>(E);
+struct ElopGrid {
+  const DevElOp& E;
+  template <int TPE>
+  int operator()() const {
+    static const int ncu = [] {
+      int dev = 0, n = 256;
+      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+      return n > 0 ? n : 256;
+    }();
+    constexpr int epb = kBlock / TPE;
+    const int npass = (E.nel + epb - 1) / epb;
+    const size_t lds = (size_t)epb * E.slot_doubles * sizeof(double);
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, elop_apply_kernel<TPE>, kBlock, lds) != hipSuccess || per_cu < 1)
+      per_cu = 2;
+    return std::max(1, std::min(npass, ncu * per_cu));
   }
-}
+};
+
+int elop_grid_of(const DevElOp& E) { return dispatch_tpe(E.tpe, ElopGrid{E}); }
+
+struct ElopPhase1 {
+  hipStream_t st;
+  const DevElOp& E;
+  int K, nY, grid;
+  size_t lds;
+  const YList& tab;
+  const double *Y, *v, *vmul, *vscale;
+  double* elbuf;
+  int diag;
+  const double* done;
+  template <int TPE>
+  void operator()() const {
+    hipLaunchKernelGGL(elop_apply_kernel<TPE>, dim3(grid), dim3(kBlock), lds, st, E, K, nY, tab, Y, v, vmul, vscale, elbuf, diag, done);
+  }
+};
 
 void launch_elop_phase1(hipStream_t st, const DevElOp& E, const BarrierParams& P, const double* Y, const double* v, const double* vmul,
                         const double* vscale, double* elbuf, int diag, const double* done) {
   const int epb = kBlock / E.tpe;
   const size_t lds = (size_t)epb * E.slot_doubles * sizeof(double);
   const YList tab = make_ylist(P);
-  const int grid = elop_grid_of(E);
-#define MGB_ELOP(T)                                                                                                            \
-  hipLaunchKernelGGL(elop_apply_kernel<T>, dim3(grid), dim3(kBlock), lds, st, E, P.K, P.nY(), tab, Y, v, vmul, vscale, elbuf,    \
-                     diag, done)
-  switch (E.tpe) {
-    case 8: MGB_ELOP(8); break;
-    case 16: MGB_ELOP(16); break;
-    case 32: MGB_ELOP(32); break;
-    case 64: MGB_ELOP(64); break;
-    case 128: MGB_ELOP(128); break;
-    default: MGB_ELOP(256); break;
-  }
-#undef MGB_ELOP
+  dispatch_tpe(E.tpe, ElopPhase1{st, E, P.K, P.nY(), elop_grid_of(E), lds, tab, Y, v, vmul, vscale, elbuf, diag, done});
 }
+
+struct ElopAssemble {
+  hipStream_t st;
+  const DevElOp& E;
+  const DevElAsm& A;
+  int nY, grid;
+  size_t lds;
+  const double* Y;
+  double* elmat;
+  template <int TPE>
+  void operator()() const {
+    hipLaunchKernelGGL(elop_assemble_kernel<TPE>, dim3(grid), dim3(kBlock), lds, st, E, A, nY, Y, elmat);
+  }
+};
+
+struct CsrApply {
+  hipStream_t st;
+  const DevCsr& A;
+  const MgEpi& epi;
+  template <int G>
+  void operator()() const {
+    hipLaunchKernelGGL(csr_apply_kernel<G>, dim3(grid_for((long long)A.rows * G)), dim3(kBlock), 0, st, A.rows, A.rowptr, A.colidx,
+                       A.vals, epi);
+  }
+};
 
 }  // namespace
 
@@ -632,16 +648,7 @@ void launch_elop_assemble(hipStream_t st, const DevElOp& E, const DevElAsm& A, B
   const int npass = (E.nel + epb - 1) / epb;
   const int grid = std::max(1, std::min(npass, kMaxBlocks * 2));
   const size_t lds = (size_t)epb * A.slot_doubles * sizeof(double);
-#define MGB_ELASM(T) hipLaunchKernelGGL(elop_assemble_kernel<T>, dim3(grid), dim3(kBlock), lds, st, E, A, P.nY(), Y, elmat)
-  switch (E.tpe) {
-    case 8: MGB_ELASM(8); break;
-    case 16: MGB_ELASM(16); break;
-    case 32: MGB_ELASM(32); break;
-    case 64: MGB_ELASM(64); break;
-    case 128: MGB_ELASM(128); break;
-    default: MGB_ELASM(256); break;
-  }
-#undef MGB_ELASM
+  dispatch_tpe(E.tpe, ElopAssemble{st, E, A, P.nY(), grid, lds, Y, elmat});
   hipLaunchKernelGGL(gather_sum_kernel, dim3(grid_for(A.nnzA)), dim3(kBlock), 0, st, A.nnzA, A.aptr, A.aidx, elmat, avals);
 }
 
@@ -673,19 +680,7 @@ void launch_csr_apply(hipStream_t st, const DevCsr& A, const MgEpi& epi_in) {
     epi.vmul = epi.dinv;
     epi.vscale = epi.coef;
   }
-#define MGB_CSR_APPLY(G)                                                                                                       \
-  hipLaunchKernelGGL(csr_apply_kernel<G>, dim3(grid_for((long long)A.rows * G)), dim3(kBlock), 0, st, A.rows, A.rowptr, A.colidx, \
-                     A.vals, epi)
-  switch (A.group) {
-    case 1: MGB_CSR_APPLY(1); break;
-    case 2: MGB_CSR_APPLY(2); break;
-    case 4: MGB_CSR_APPLY(4); break;
-    case 8: MGB_CSR_APPLY(8); break;
-    case 16: MGB_CSR_APPLY(16); break;
-    case 32: MGB_CSR_APPLY(32); break;
-    default: MGB_CSR_APPLY(64); break;
-  }
-#undef MGB_CSR_APPLY
+  dispatch_group(A.group, CsrApply{st, A, epi});
 }
 
 void launch_expand_sym(hipStream_t st, int nnz_full, const int* map, const double* lower, double* full, int N, const int* diagpos,
