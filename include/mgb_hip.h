@@ -319,6 +319,13 @@ int mgb_amg_prolongation(mgb_amg a, int level, int* rows, int* cols, int* nnz, i
 /* x = H(s)^{-1} g by the V-cycle-preconditioned CG the Newton loop runs with solver 2; *converged = 0 if it stopped at maxit */
 int mgb_amg_pcg_solve_linear(mgb_amg a, int level, const double* s, const double* g, double* x, int* iters, double* relres,
                              int* converged);
+/* tests: lambda_max(Dinv A) of `level` for every later V-cycle setup (mgb_amg_vcycle, mgb_amg_pcg_solve_linear, solver 2) in place
+ * of the device's warm-started estimate; 0 unpins (the default); a negative or non-finite value is an argument error */
+int mgb_amg_mg_pin_lmax(mgb_amg a, int level, double lmax);
+/* x = V(b): one V-cycle of the preconditioner of solver 2 at the Hessian H(s) of level `top`, enqueued exactly as CG enqueues it
+ * (single-GPU contexts; the parameters of mgb_amg_set_pcg apply); lmax_used[l] (one double per level of the hierarchy) = the
+ * lambda the Chebyshev coefficients of level l were built from, for the levels above the coarsest one of the cycle, 0 elsewhere */
+int mgb_amg_vcycle(mgb_amg a, int top, const double* s, const double* b, double* x, double* lmax_used);
 /* CG / V-cycle parameters (a value <= 0, or < 0 for the two flags, keeps the current one): relative tolerance on
  * sqrt(<r, M r>), iteration cap, applications of H per Chebyshev pre-/post-smoothing, power steps per level and Newton matrix,
  * Chebyshev interval fractions, CG iterations enqueued between two looks at the convergence flag, direct solve of a step whose

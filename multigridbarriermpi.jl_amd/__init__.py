@@ -1173,6 +1173,18 @@ class AMG:
         call("mgb_amg_pcg_solve_linear", self.handle, l, dptr(s), dptr(g), dptr(x), C.byref(it), C.byref(rr), C.byref(ok))
         return x, it.value, rr.value, bool(ok.value)
 
+    def pin_lmax(self, l, lmax):
+        """Use `lmax` as lambda_max(Dinv H) of level l in every later V-cycle setup instead of the device's estimate; 0 unpins."""
+        call("mgb_amg_mg_pin_lmax", self.handle, int(l), float(lmax))
+
+    def vcycle(self, top, s, b):
+        """x = V(b), one V-cycle of the preconditioner of solver="pcg" at H(s) of level `top`; returns (x, lambda_max used per
+        level: zero on the coarsest level of the cycle and outside it)."""
+        s, b = f64(s), f64(b)
+        x, used = np.empty_like(b), np.zeros(self.L)
+        call("mgb_amg_vcycle", self.handle, int(top), dptr(s), dptr(b), dptr(x), dptr(used))
+        return x, used
+
     MG_KERNEL_NAMES = ("hessian_apply", "chebyshev_step", "hessian_apply_csr", "prolong", "restrict", "hessian_apply_unfused_csr")
 
     def time_mg_kernels(self, l, reps=50, nrot=1):

@@ -129,6 +129,8 @@ PROTOTYPES = {
     "mgb_amg_prolongation": [H, C.c_int, c_int_p, c_int_p, c_int_p, c_i32_p, c_i32_p, c_dbl_p],
     "mgb_amg_pcg_solve_linear": [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, c_int_p],
     "mgb_amg_mg_info": [H, C.c_int, c_int_p],
+    "mgb_amg_mg_pin_lmax": [H, C.c_int, C.c_double],
+    "mgb_amg_vcycle": [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_amg_elop_info": [H, C.c_int, c_int_p],
     "mgb_amg_time_mg_kernels": [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_locator_create": [H, H, C.POINTER(H)],

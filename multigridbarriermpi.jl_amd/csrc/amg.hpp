@@ -417,6 +417,7 @@ class Amg {
       DevCsrOwned P, PT;              // prolongation to level l + 1 (N_{l+1} x N_l) and its transpose
       DevBuf<double> dinv, x, b, r, d0, d1, ev0, ev1, coef, Ainv;
       bool ev_warm = false;           // ev0 holds the dominant vector of an earlier matrix of this level
+      double lmax_pin = 0.0;          // > 0: lambda_max(Dinv A) of this level is given (mg_pin_lmax), no power steps
     };
     std::unique_ptr<Mg> mg;
   };
@@ -498,6 +499,11 @@ class Amg {
   void mg_prolong(int l, const double* xc_host, double* xf_host);      // level l -> l + 1
   void mg_restrict(int l, const double* rf_host, double* rc_host);     // level l + 1 -> l
   int mg_coarsest(int top);      // coarsest level of the V-cycle below `top`
+  // tests: lambda_max(Dinv A) of level l for every later V-cycle setup, in place of the device's estimate (0 unpins)
+  void mg_pin_lmax(int l, double lmax);
+  // x = V(b) at the Hessian of level `top` at s: the V-cycle exactly as CG enqueues it (never skipped: no done flag), and
+  // lmax_used[l] (L doubles) = the lambda the coefficients of level c0 < l <= top were built from, 0 elsewhere
+  void vcycle(int top, const double* s_host, const double* b_host, double* x_host, double* lmax_used);
   // read-only description of level l's element operator (built through mg_ensure_elop if it is not yet), kElopInfo ints:
   // valid, tpe, rows_per_el, cmax, nnz_max, ncls, nel, K, nY, pipelined, element assembly valid, grid, passes per workgroup
   static constexpr int kElopInfo = 13;

@@ -537,7 +537,7 @@ void Amg::mg_values(int top) {
     if (lv.plan.N == 0) continue;
     const bool mf = (l == top) && mf_top;
     mg_level_values(lv, mf);
-    if (l > c0) mg_estimate(lv, mf, 0.0);
+    if (l > c0) mg_estimate(lv, mf, lv.mg->lmax_pin);
   }
   Level& lc = level(c0);
   if (lc.plan.N <= kDenseMax)
@@ -735,6 +735,32 @@ double Amg::mg_smooth(int l, const double* s_host, const double* b_host, double*
   hip_check(hipStreamSynchronize(ctx_.stream), "sync mg_smooth");
   m.x.download(x_host, lv.plan.N);
   return used;
+}
+
+void Amg::mg_pin_lmax(int l, double lmax) {
+  if (!(lmax >= 0.0) || !std::isfinite(lmax)) throw ArgError("mg_pin_lmax: lambda must be finite and >= 0 (0 unpins)");
+  mg_of(level(l)).lmax_pin = lmax;
+}
+
+void Amg::vcycle(int top, const double* s_host, const double* b_host, double* x_host, double* lmax_used) {
+  Level& lv = level(top);
+  mg_prepare(top);
+  eval_Y_at(lv, s_host);
+  mg_values(top);
+  pcg_r_.upload(b_host, lv.plan.N);
+  mg_vcycle(top, top, pcg_r_.p, pcg_z_.p, nullptr);
+  std::fill(lmax_used, lmax_used + L(), 0.0);
+  for (int l = mg_coarsest(top) + 1; l <= top; ++l)
+    hip_check(hipMemcpyAsync(lmax_used + l, level(l).mg->coef.p + kChebStride - 1, sizeof(double), hipMemcpyDeviceToHost, ctx_.stream),
+              "D2H lmax");
+  hip_check(hipStreamSynchronize(ctx_.stream), "sync vcycle");
+  pcg_z_.download(x_host, lv.plan.N);
+  int fail = 0;
+  hip_check(hipMemcpy(&fail, mg_fail_.p, sizeof(int), hipMemcpyDeviceToHost), "D2H mg flag");
+  if (fail) {
+    hip_check(hipMemset(mg_fail_.p, 0, sizeof(int)), "memset mg flag");
+    throw NumericError("vcycle: the coarsest-level matrix is not positive definite");
+  }
 }
 
 void Amg::mg_prolong(int l, const double* xc_host, double* xf_host) {

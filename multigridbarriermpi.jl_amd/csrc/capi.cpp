@@ -1063,6 +1063,18 @@ int mgb_amg_pcg_solve_linear(mgb_amg a, int level, const double* s, const double
     if (converged) *converged = ok ? 1 : 0;
   });
 }
+int mgb_amg_mg_pin_lmax(mgb_amg a, int level, double lmax) {
+  return guard([&] {
+    need(a && level >= 0 && level < a->amg->L(), "mg_pin_lmax: bad arguments");
+    a->amg->mg_pin_lmax(level, lmax);
+  });
+}
+int mgb_amg_vcycle(mgb_amg a, int top, const double* s, const double* b, double* x, double* lmax_used) {
+  return guard([&] {
+    need(a && s && b && x && lmax_used && top >= 0 && top < a->amg->L(), "vcycle: bad arguments");
+    a->amg->vcycle(top, s, b, x, lmax_used);
+  });
+}
 int mgb_amg_time_mg_kernels(mgb_amg a, int level, int reps, int nrot, double* ms6, double* bytes6, double* alg6) {
   return guard([&] {
     need(a && ms6 && bytes6 && alg6 && reps > 0 && nrot >= 1 && nrot <= 64 && level >= 0 && level < a->amg->L(),
