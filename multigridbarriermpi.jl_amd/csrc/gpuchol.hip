@@ -1539,8 +1539,9 @@ __device__ __forceinline__ void load_panel_rows(double (&f)[PB], const double* _
   for (int r = 0; r < PB; ++r) f[r] = Fj[(long long)ld * min(r, kw - 1)];
 }
 
-// x_p = L_pp^-T u_p of one 32-wide panel by one wave (the substitution of backward_kernel): up = the panel's entries in LDS
-__device__ __forceinline__ void panel_substitute(const double (&lc)[PB], double* up, int kw, int lane) {
+// x_p = L_pp^-T u_p of one 32-wide panel by one wave (the substitution of backward_kernel): up = the panel's entries in LDS.
+// Returns x_c of the lane's column c = lane & 31 (0 beyond the panel).
+__device__ __forceinline__ double panel_substitute(const double (&lc)[PB], double* up, int kw, int lane) {
   const int c = lane & 31;
   double uc = (c < kw) ? up[c] : 0.0;
 #pragma unroll
@@ -1549,6 +1550,7 @@ __device__ __forceinline__ void panel_substitute(const double (&lc)[PB], double*
     uc = (c == m) ? xm : fma(-lc[m], xm, uc);                 // lanes c > m: lc[m] == 0
   }
   if (lane < kw) up[c] = uc;
+  return uc;
 }
 
 // sum_i L[k0 + i][j] x_(k0 + i) over the kw rows of a solved panel, as backward_kernel adds it up with NSL row slices:
@@ -1569,6 +1571,25 @@ __device__ __forceinline__ double panel_dot(const double (&f)[PB], const double*
   return t;
 }
 
+// the same with the solved panel in registers: lane r of xq holds x_(k0 + r) (what panel_substitute returns), broadcast by
+// constant-lane v_readlane -- no LDS read, and so no LDS wait, per row on the substituting wave's critical path
+template <int NSL>
+__device__ __forceinline__ double panel_dot_lanes(const double (&f)[PB], double xq, int kw) {
+  double s[NSL];
+#pragma unroll
+  for (int q = 0; q < NSL; ++q) s[q] = 0.0;
+#pragma unroll
+  for (int r = 0; r < PB; ++r) {
+    const double v = fma(f[r], readlane_f64(xq, r), s[r % NSL]);
+    s[r % NSL] = (r < kw) ? v : s[r % NSL];
+    if (r % 8 == 7) __builtin_amdgcn_sched_barrier(0);      // (a fence every eight rows: the broadcasts stay by their fma)
+  }
+  double t = s[0];
+#pragma unroll
+  for (int q = 1; q < NSL; ++q) t += s[q];
+  return t;
+}
+
 // the same for any slice count (the 1 024-thread heights, which the default threshold keeps out of the fused launch)
 __device__ inline double panel_dot_any(const double* __restrict__ Fj, long long ld, const double* up, int kw, int nsl) {
   double t = 0.0;
@@ -1578,6 +1599,33 @@ __device__ inline double panel_dot_any(const double* __restrict__ Fj, long long 
     t = q ? t + s : s;
   }
   return t;
+}
+
+// the update of one earlier column by a solved panel (kw rows at up) with nslp slices: from the column's 32 entries in f
+// where the slice count has a register form and f holds them, else from the front (Fj: the column's first entry)
+__device__ __forceinline__ double panel_update(const double (&f)[PB], bool in_f, const double* __restrict__ Fj, long long ld,
+                                               const double* up, int kw, int nslp) {
+  if (in_f && nslp == 1) return panel_dot<1>(f, up, kw);
+  if (in_f && nslp == 2) return panel_dot<2>(f, up, kw);
+  if (in_f && nslp == 4) return panel_dot<4>(f, up, kw);
+  return panel_dot_any(Fj, ld, up, kw, nslp);
+}
+
+// One panel of the looking-ahead wave: the solved panel at q0 (xq: its entries by lane, also at u + q0) is applied to the 32
+// columns below it, which are substituted straight away.  The rows of L and the pivot block (lnext) of the next step are
+// loaded right after the last use of f and lc, in the order of their use, behind no branch (k0 = 0: clamped copies).
+__device__ __forceinline__ void lookahead_step(double (&lc)[PB], double (&f)[PB], double& xq, const double* __restrict__ F, int ld,
+                                               int ns, int nt, int q0, double* u, const double* __restrict__ lnext, int lane) {
+  const int k0 = q0 - PB, qw = min(PB, ns - q0), jc = k0 + (lane & 31);
+  const int jw = min(nt, (q0 + 63) & ~63), nslp = nt / jw;      // the slices of backward_kernel<nt> for this panel
+  const double s = nslp == 1   ? panel_dot_lanes<1>(f, xq, qw)
+                   : nslp == 2 ? panel_dot_lanes<2>(f, xq, qw)
+                   : nslp == 4 ? panel_dot_lanes<4>(f, xq, qw)
+                               : panel_dot_any(F + (long long)ld * q0 + jc, ld, u + q0, qw, nslp);
+  if (lane < PB) u[jc] -= s;
+  load_panel_rows(f, F, ld, k0, PB, k0 - PB + (lane & 31));
+  xq = panel_substitute(lc, u + k0, PB, lane);
+  load_pivot_block(lc, lnext, lane);
 }
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -1594,6 +1642,7 @@ __global__ __launch_bounds__(512) void backward_fused_kernel(const int* __restri
                                                               const int* __restrict__ perm, double* y, double* x, long long* prof) {
   extern __shared__ double sh[];
   STAMP(0);      // stamps: 1 staged, 2 path done, 3 .. 6 the subtree's levels (6: the fourth and every later one), 7 end
+                 // (6 -> 7: the one pass that stores the path fronts' solutions; a subtree level stores its own fronts)
   int* rec = (int*)sh;
   double* xs = sh + wstride / 2;
   double* red = xs + xs_cap;
@@ -1666,9 +1715,11 @@ __global__ __launch_bounds__(512) void backward_fused_kernel(const int* __restri
       const bool sub = act && gw == 0 && npanel > 0;      // this wave does the front's substitutions
       // Software pipeline: the pivot block of the next panel is loaded as soon as a substitution is done (the first one
       // before the rectangular part), the rows of L of the next update as soon as an update is done (they arrive during
-      // the substitution in between) -- each batch of 32 loads under ONE wave-uniform branch, a phase before its use.
-      // (Issuing both batches from every wave under no branch makes every wait a counted one, and was measured slower:
-      // 168 us against 132 for the launch at fem2d L=7 -- the idle waves' loads queue in front of the needed ones.)
+      // the substitution in between).  In the loop the waves share (below) each batch of 32 loads sits under ONE
+      // wave-uniform branch, a phase before its use, so that only the waves that need a batch issue it.  (Issuing both
+      // batches from EVERY wave under no branch was measured slower: 168 us against 132 for the launch at fem2d L=7 -- the
+      // idle waves' loads queue in front of the needed ones.)  The looking-ahead wave alone, in its own loop, issues both
+      // of ITS batches under no branch: it needs both, and its waits become counted ones.
       double lc[PB], f[PB];
       if (sub) load_pivot_block(lc, linv + loff + (long long)(npanel - 1) * 2 * PB * PB, lane);
       if (items > 0) {      // u -= L21' x_bdry
@@ -1712,33 +1763,65 @@ __global__ __launch_bounds__(512) void backward_fused_kernel(const int* __restri
           }
         __syncthreads();
       }
-      if (act && npanel > 1) load_panel_rows(f, F, ld, (npanel - 1) * PB, ns - (npanel - 1) * PB, gtid);
-      for (int it = 0; it < maxp; ++it) {
-        const int pp = npanel - 1 - it, k0 = pp * PB, kw = min(PB, ns - k0);
-        if (sub && pp >= 0) {
-          panel_substitute(lc, u + k0, kw, lane);
-          if (pp > 0) load_pivot_block(lc, linv + loff + (long long)(pp - 1) * 2 * PB * PB, lane);
-        }
+      // Look-ahead: a solved panel x_q (at q0) is applied to the 32 columns of the panel below it (pp, at k0) by the wave
+      // that substitutes, which then substitutes that panel straight away, and to all earlier columns by the other waves
+      // of the group meanwhile.  Iteration `it` of a group of G > 1 waves:
+      //   wave 0:  u[k0 .. k0+32) -= L[q0.., k0..]' x_q   (x_q: its own LDS writes of the last iteration; LDS keeps a
+      //            x_pp = L_pp^-T u[k0 .. k0+kw)            wave's accesses in order)
+      //   others:  u[0 .. k0)     -= L[q0.., 0..k0)' x_q  (x_q visible since the barrier that ended the last iteration)
+      // Within an iteration wave 0 touches only u[k0 .. q0+qw); the others write only u[0 .. k0) and read u[q0 .. q0+qw),
+      // which nobody writes: ONE barrier per panel, maxp per front, the same for every wave of the workgroup (maxp is the
+      // level record's).  A group of one wave plays both roles in sequence, u[0 .. q0) -= ... and then the substitution.
+      // Column j still receives u - s_rect, then - s_p for p = npanel-1 down to j/32 + 1 (one per iteration, a barrier
+      // between any two), each s_p added up as panel_dot / panel_dot_any do, then the substitution: the same bits.
+      // f: L[q0 + r][column] of the next update, wave 0's column k0 + (lane & 31), the others' their own; reloaded right
+      // after its use, as the pivot block is.
+      const bool lead = sub && G > 1 && npanel > 1;      // substitutes and looks ahead, no other columns (a front of one
+                                                         // panel has nothing to look ahead to: the shared loop below)
+      if (lead) {
+        // The looking-ahead wave runs a loop of its own, in a straight line: both its batches of 32 loads are issued
+        // unconditionally (clamped at the first panel) and in the order of their use -- rows of L, then the pivot block --
+        // so every wait is a counted one and leaves the younger batch in flight.  (Under the wave-uniform branches of a
+        // loop shared with the other waves the compiler waits for ALL loads before a use: the batch issued just before
+        // was then waited for twice per panel, ~1 us each.)  It executes one barrier per panel and the rest of the
+        // level's maxp after its last panel, as every other wave does.
+        int k0 = (npanel - 1) * PB;
+        load_panel_rows(f, F, ld, k0, ns - k0, k0 - PB + (lane & 31));
+        double xq = panel_substitute(lc, u + k0, ns - k0, lane);
+        load_pivot_block(lc, linv + loff + (long long)(npanel - 2) * 2 * PB * PB, lane);
         __syncthreads();
-        if (it == maxp - 1) break;
-        if (act && pp > 0) {      // u_j -= sum_{i in p} L[i][j] x_i for the earlier columns j
-          const int jw = min(nt, (k0 + 63) & ~63), nslp = nt / jw;
-          for (int jc = gtid; jc < k0; jc += GT) {
-            double s;
-            if (jc >= GT) {      // fronts wider than their share of the workgroup: the columns beyond it, unpipelined
-              s = panel_dot_any(F + (long long)ld * k0 + jc, ld, u + k0, kw, nslp);
-            } else if (nslp == 1 || nslp == 2 || nslp == 4) {
-              s = nslp == 1 ? panel_dot<1>(f, u + k0, kw) : nslp == 2 ? panel_dot<2>(f, u + k0, kw) : panel_dot<4>(f, u + k0, kw);
-            } else {
-              s = panel_dot_any(F + (long long)ld * k0 + jc, ld, u + k0, kw, nslp);
+        for (int pp = npanel - 2; pp >= 0; --pp) {      // (at the first panel the loads repeat themselves: clamped)
+          lookahead_step(lc, f, xq, F, ld, ns, nt, k0, u, linv + loff + (long long)max(pp - 1, 0) * 2 * PB * PB, lane);
+          k0 -= PB;
+          __syncthreads();
+        }
+        for (int it = npanel; it < maxp; ++it) __syncthreads();
+      } else {
+        // the other waves of a group (G > 1), wave 0 of a group whose front has one panel (it substitutes, nobody updates),
+        // the one wave of a group of one, and idle waves (barriers only)
+        const int OT = G > 1 ? GT - 64 : GT, ot = G > 1 ? gtid - 64 : gtid;      // the threads of the earlier columns
+        if (act && npanel > 1) load_panel_rows(f, F, ld, (npanel - 1) * PB, ns - (npanel - 1) * PB, ot);
+        for (int it = 0; it < maxp; ++it) {
+          const int pp = npanel - 1 - it, k0 = pp * PB, kw = min(PB, ns - k0), q0 = k0 + PB, qw = min(PB, ns - q0);
+          if (act && pp >= 0) {      // wave-uniform, as every branch below (it > 0: never wave 0 of a group with G > 1)
+            if (it > 0) {      // u_j -= sum_{i in q} L[i][j] x_i
+              const int jw = min(nt, (q0 + 63) & ~63), nslp = nt / jw, hi = G > 1 ? k0 : q0;
+              // (columns beyond the group's threads, of fronts wider than their share of the workgroup: unpipelined)
+              for (int jc = ot; jc < hi; jc += OT)
+                u[jc] -= panel_update(f, jc < OT, F + (long long)ld * q0 + jc, ld, u + q0, qw, nslp);
+              if (hi > PB) load_panel_rows(f, F, ld, k0, PB, ot);
             }
-            u[jc] -= s;
+            if (sub) {
+              panel_substitute(lc, u + k0, kw, lane);
+              if (pp > 0) load_pivot_block(lc, linv + loff + (long long)(pp - 1) * 2 * PB * PB, lane);
+            }
           }
-          if (pp > 1) load_panel_rows(f, F, ld, k0 - PB, PB, gtid);
+          __syncthreads();
         }
-        __syncthreads();
       }
-      if (act && (uni(j[FJ_FLAGS]) & 1)) {
+      // a subtree front is stored at once (nothing waits for these stores; the next level's work covers the load of perm);
+      // the path fronts are stored in one pass at the end
+      if (lv >= sub_lv && act && (uni(j[FJ_FLAGS]) & 1)) {
         const int first = uni(j[FJ_FIRST]);
         for (int i = gtid; i < ns; i += GT) {
           const double v = u[i];
@@ -1751,6 +1834,23 @@ __global__ __launch_bounds__(512) void backward_fused_kernel(const int* __restri
     if (lv >= sub_lv) STAMP(min(3 + lv - sub_lv, 6));
   }
   for (int k = 3 + nlevels - sub_lv; k < 7; ++k) STAMP(k);      // fewer than four subtree levels: the rest read as empty phases
+  // The path fronts this workgroup stores, in one pass at the end (xs keeps them): a wave per front, the loads of perm of
+  // all of them in flight together.  (Stored front by front, each store waited for its perm entries with nothing to cover
+  // them: one global round trip per path front on the workgroup that stores the ancestors -- the leftmost one, the last
+  // to finish.  The jobs of the path levels come first in the record.)
+  const int npath = sub_lv < nlevels ? rec[kFusedHdr + kFusedLevelInts * sub_lv] : njobs;
+  __syncthreads();
+  for (int jb = wave; jb < npath; jb += W) {
+    const int* j = jobs + kFusedJobInts * jb;
+    if (!(uni(j[FJ_FLAGS]) & 1)) continue;
+    const int ns = uni(j[FJ_NS]), first = uni(j[FJ_FIRST]);
+    const double* u = xs + uni(j[FJ_BASE]);
+    for (int i = lane; i < ns; i += 64) {
+      const double v = u[i];
+      y[first + i] = v;
+      x[perm[first + i]] = v;
+    }
+  }
   STAMP(7);
 }
 
