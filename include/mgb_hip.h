@@ -558,6 +558,54 @@ int mgb_geo_estimate_host(mgb_geo g, const double* z /* n x S */, int S, int u, 
                           const unsigned char* mask_or_null, double* eta /* nel x 3 */, double* J_or_null, double* N_or_null,
                           double* sigma_or_null, double* out /* MGB_ESTIMATE_COLS */);
 
+/* ---- error indicators of the steps of a parabolic run --------------------------------------------- *
+ * Single-GPU contexts, fp64.  A run has snapshots Z_0 .. Z_B (n x S row-major, B + 1 = len(ts)) at strictly increasing finite
+ * times, h_k = ts[k] - ts[k-1].  Step k = 1..B solved  min int (1/2h_k)(s1 - 2 u u_(k-1)) + (1/p) s2 + f_k u,  whose strong form is
+ * (u_k - u_(k-1)) / h_k + f_k - div sigma_k = 0  with the natural condition  sigma_k . n + h_k^N = 0  on the free facets: the
+ * residual of mgb_estimate with own_scale (lambda = scale, default 1; lambda_i = p_i is not offered) plus one term.  Everything
+ * not named here is mgb_estimate's, unchanged: the facet tables, h_e, the power rule, the ascending sum orders, fp contraction
+ * off, the NaN rules.
+ *   flux          Sigma^m, m = 0..B, the nodal flux of snapshot m, bit for bit what mgb_geo_field_flux gives for it; one launch
+ *                 for all B + 1 fields; sigma holds (B + 1) x n x dim
+ *   node i        d_i = (u^k_i - u^(k-1)_i) / h_k, a subtraction, then a division;
+ *                 rho_i = (f_k,i + d_i) - lambda div(I Sigma^k)(x_i)  (f null: 0);  rate term  w_i |d_i|^r
+ *   element e     vol_e, jump_e, neu_e from Sigma^k exactly as in mgb_estimate, the Neumann data those of the step's new time;
+ *                 tim_e = sum_{i in e} w_i |Sigma^k_i - Sigma^(k-1)_i|_2^r, the 2-norm a square root of the squares summed in
+ *                 ascending component order, local i ascending (at p = 2 this is |grad (u_k - u_(k-1))|, the classical time
+ *                 indicator of implicit Euler)
+ *   parts         B x nel x 4: vol, jump, neu, tim
+ *   out           B x 2 x MGB_ESTIMATE_COLS:  row 0 is mgb_estimate's row: sum vol | sum jump | sum neu | max eta_e^r | max |J_Fj|;
+ *                 row 1 is  sum tim | sum_i w_i |d_i|^r | 0 | max_e tim_e | max_i |d_i|  (the rate sum per element in ascending
+ *                 local order, then over the elements)
+ * f: f_rows = 1 -- n values for every step -- or f_rows = B -- row k - 1 for step k.  h (host): h_rows x nf x q, h_rows 1 or B,
+ * null: the boundary contributes nothing; mask (host, nf bytes) as for mgb_estimate.
+ * A non-finite u^k_i, u^(k-1)_i, Sigma^k, Sigma^(k-1), f or h makes what it feeds NaN, and the maxima are NaN-sticky: a NaN in
+ * snapshot m reaches steps m and m + 1 and no other.
+ * Bitwise: a repeated call repeats; what a step's numbers are made of depends on its two snapshots, its f, h and h_k alone, so B
+ * steps in one call give the bits of B calls with B = 1; sigma[m] is mgb_geo_field_flux of snapshot m; where the two snapshots of
+ * a step hold the same values, row 0 and vol, jump, neu are the bits of mgb_estimate on that snapshot with own_scale = 1 and the
+ * same scale, f, h and mask, and tim, the rate and both maxima of row 1 are exactly 0.
+ * mgb_estimate_steps: four launches whatever B is -- the flux on grid (ceil(n / 256), B + 1), then the kernels of mgb_estimate
+ * with the step in blockIdx.y: facet_terms_kernel on (workgroups, B) (left out when there is no facet), element_indicator_kernel
+ * on (workgroups, B), estimate_finish on 2 B workgroups, one per row of totals.  No atomics.  The table of the snapshots, the
+ * step sizes, h and the mask are copied up per call; the per-facet values and the partials live with the boundary handle and
+ * grow on demand.  One wait, one copy of 10 B doubles to the host.
+ * MGB_E_ARG, before anything is launched or written: a null argument or field; B < 1 or B + 1 > 65535; ts not finite or not
+ * strictly increasing; S < 1; u outside [0, S); p or r not finite or < 1; a non-finite scale; f_rows or h_rows neither 1 nor B; a
+ * vector of the wrong length or of another context; an output (sigma, parts) that is also an input or the other output; a sharded
+ * context. */
+int mgb_estimate_steps(mgb_boundary b, int B, const mgb_vec* z /* B + 1 vectors of n x S */, const double* ts_host /* B + 1 */,
+                       int S, int u, double p, mgb_vec p_nodal_or_null, mgb_vec f_or_null, int f_rows, double r, double scale,
+                       const double* h_host_or_null /* h_rows x nf x q */, int h_rows, const unsigned char* mask_host_or_null,
+                       mgb_vec sigma /* (B + 1) x n x dim */, mgb_vec parts /* B x nel x 4 */,
+                       double* out_host /* B x 2 x MGB_ESTIMATE_COLS */);
+/* host only: the same routines, serially, step after step; sigma ((B + 1) x n x dim), J (B x nif) and N (B x nf) nullable */
+int mgb_geo_estimate_steps_host(mgb_geo g, int B, const double* const* z /* B + 1 arrays of n x S */, const double* ts /* B + 1 */,
+                                int S, int u, double p, const double* p_nodal_or_null, const double* f_or_null, int f_rows, double r,
+                                double scale, const double* h_or_null, int h_rows, const unsigned char* mask_or_null,
+                                double* sigma_or_null, double* parts /* B x nel x 4 */, double* J_or_null, double* N_or_null,
+                                double* out /* B x 2 x MGB_ESTIMATE_COLS */);
+
 /* ---- mixed boundary conditions: Dirichlet on part of the boundary, Neumann data on the rest ------- *
  * Single-GPU contexts, fp64.
  * Dirichlet subspace.  mgb_geo_dirichlet_on adds "sub:<name>:<l>" for every level l (read back with mgb_geo_matrix_info / _get;

@@ -41,6 +41,7 @@ __all__ = [
     "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
     "dirichlet_on", "neumann_load", "NeumannLoad",
     "interior", "InteriorFacets", "estimate", "ErrorIndicators", "mark", "refine_triangles", "adapt",
+    "estimate_steps", "StepIndicators", "refine_times", "adapt_time",
 ]
 
 
@@ -2533,6 +2534,187 @@ def adapt(K, L, p, steps, theta=0.5, **amgb_kwargs) -> list:
         out.append((K, sol, ind))
         if step < steps:
             K = refine_triangles(K, mark(ind.coarse(int(L)), theta))
+    return out
+
+
+# --------------------------------------------------------------------------- error indicators of parabolic runs
+
+
+class StepIndicators:
+    """Result of estimate_steps(), B = len(ts) - 1 steps.  `ts`, `hs` (B,) the times and the steps, `r`
+    the power.  `parts` (B, nel, 4): vol_e, jump_e, neu_e -- their sum is eta_e^r of the step problem -- and tim_e; it stays on
+    the device until first used.  Arrays of length B: `volume`, `jump`, `neumann`, `space` (their sum), `time` (sum of tim_e),
+    `rate` (the L^r norm of the difference quotient d = (u_k - u_(k-1)) / h_k), `rate_max` (max |d_i|), `eta_max` (max_e eta_e),
+    `jump_max` (max |J_Fj|), `time_max` (max_e tim_e).  `columns` (B, 2, 5): the totals as the C ABI returns them.  `sigma`: the
+    (B + 1, n * dim) device HPCMatrix of the fluxes of all snapshots.  `total_space` = (sum_k h_k space_k)^(1/r), `total_time` =
+    (sum_k h_k time_k)^(1/r), `total` = (sum_k h_k (space_k + time_k))^(1/r).  A non-finite input shows as NaN in the steps it
+    feeds."""
+
+    def __init__(self, geometry, ts, parts_dev, cols, sigma, r):
+        self.geometry, self.r = geometry, float(r)
+        self.ts = np.array(ts, dtype=np.float64)
+        self.hs = np.diff(self.ts)
+        self._dev, self._parts = parts_dev, None
+        self.columns = np.array(cols, dtype=np.float64).reshape(len(self.hs), 2, 5)
+        self.sigma = sigma
+        c, q = self.columns, 1.0 / self.r
+        self.volume, self.jump, self.neumann = c[:, 0, 0].copy(), c[:, 0, 1].copy(), c[:, 0, 2].copy()
+        self.space = (c[:, 0, 0] + c[:, 0, 1]) + c[:, 0, 2]
+        self.time = c[:, 1, 0].copy()
+        self.rate, self.rate_max = c[:, 1, 1] ** q, c[:, 1, 4].copy()
+        self.eta_max, self.jump_max, self.time_max = c[:, 0, 3] ** q, c[:, 0, 4].copy(), c[:, 1, 3].copy()
+        self.total_space = float(np.sum(self.hs * self.space) ** q)
+        self.total_time = float(np.sum(self.hs * self.time) ** q)
+        self.total = float(np.sum(self.hs * (self.space + self.time)) ** q)
+
+    @property
+    def parts(self) -> np.ndarray:
+        if self._parts is None:
+            self._parts = self._dev.to_numpy().reshape(len(self.hs), -1, 4)
+            self._dev = None
+        return self._parts
+
+    def elements(self) -> np.ndarray:
+        """sum_k h_k eta_{e,k}^r, (nel,): where in space the run is inaccurate; feeds mark() and refine_triangles()."""
+        P = self.parts
+        return np.tensordot(self.hs, (P[:, :, 0] + P[:, :, 1]) + P[:, :, 2], axes=1)
+
+    def coarse(self, L: Optional[int] = None) -> np.ndarray:
+        """elements() summed over the consecutive elements of each element of the coarse mesh, as ErrorIndicators.coarse."""
+        L = len(self.geometry.refine) if L is None else int(L)
+        E = self.elements()
+        group = (2 ** self.geometry.discretization["dim"]) ** (L - 1)
+        if L < 1 or len(E) % group:
+            raise ValueError("StepIndicators.coarse: %d elements are not groups of %d" % (len(E), group))
+        return E.reshape(-1, group).sum(axis=1)
+
+    def __repr__(self):
+        return "StepIndicators(steps=%d, total=%r, total_space=%r, total_time=%r, r=%r)" % (
+            len(self.hs), self.total, self.total_space, self.total_time, self.r)
+
+
+def estimate_steps(par, p, f1=None, u=0, r=2.0, scale=1.0, dirichlet=None, neumann=None) -> StepIndicators:
+    """Error indicators of every step of a parabolic run, from one set of launches whatever the number of steps
+    (csrc/estimate.hip; contract in include/mgb_hip.h and DESIGN.md section 4m).  Step k solved an implicit-Euler problem whose
+    strong form is (u_k - u_(k-1)) / h_k + f_k - div sigma_k = 0: per step the space indicator of that problem (estimate()'s
+    residual with lambda = `scale` plus the difference quotient), the time indicator sum_e sum_i w_i |sigma_k - sigma_(k-1)|^r
+    and the norm of the difference quotient.  `par`: a ParabolicSOL (snapshots as HPCMatrix or numpy arrays); `p`, `u`: as for
+    energy; `f1`, `dirichlet`, `neumann`: as parabolic_solve takes them (f1 None is its default 0.5, pass 0.0 for no forcing;
+    h(t, x) is taken at ts[1:]; values at the facet nodes, (nf, q) or (B, nf, q), are taken too), so estimate_steps(parabolic_solve(g, **kw), **kw) describes that run; `r` >= 1 the power."""
+    if not isinstance(par, ParabolicSOL):
+        raise TypeError("estimate_steps: par must be a ParabolicSOL")
+    if neumann is not None and dirichlet is None:
+        raise ValueError("estimate_steps: neumann= needs dirichlet= (the data act on the facets that dirichlet= does not select)")
+    geometry, fields = par.geometry, list(par.u)
+    ts = np.array(par.ts, dtype=np.float64).reshape(-1)
+    if len(ts) < 2:
+        raise ValueError("estimate_steps: par must hold at least two snapshots, got %d times" % len(ts))
+    if len(fields) != len(ts):
+        raise ValueError("estimate_steps: par.u has %d snapshots for %d times" % (len(fields), len(ts)))
+    if not np.all(np.isfinite(ts)) or not np.all(np.diff(ts) > 0):
+        raise ValueError("estimate_steps: par.ts must be finite and strictly increasing")
+    if not isinstance(geometry, Geometry) or geometry._geo is None:
+        raise TypeError("estimate_steps: the geometry of par must come from native_to_mpi / fem*d_mpi")
+    if geometry.x.backend.world > 1:
+        raise NotImplementedError("estimate_steps: sharded contexts (world > 1) are not supported")
+    if isinstance(r, (str, bytes)) or not np.isscalar(r) or not (math.isfinite(float(r)) and float(r) >= 1.0):
+        raise ValueError("estimate_steps: r must be a finite real >= 1, got %r" % (r,))
+    if isinstance(scale, (str, bytes)) or not np.isscalar(scale) or not math.isfinite(float(scale)):
+        raise ValueError("estimate_steps: scale must be a finite real, got %r" % (scale,))
+    B = len(ts) - 1
+    if B + 1 > 65535:
+        raise ValueError("estimate_steps: at most 65535 snapshots per call, got %d" % (B + 1))
+    loc, backend = _locator_of(geometry)
+    b = boundary(geometry)
+    vecs = [_nodal_values(geometry, zk, backend, "estimate_steps") for zk in fields]
+    S = vecs[0][1]
+    if any(Sk != S for _, Sk in vecs):
+        raise ValueError("estimate_steps: the snapshots of par.u have different numbers of columns")
+    u = _energy_column(u, S, "u", "estimate_steps")
+    n, dim = len(geometry.w), geometry.discretization["dim"]
+    x = np.asarray(_to_cpu_array(geometry.x)).reshape(n, -1)
+    p0, pn = _energy_exponent(p, x, "estimate_steps")
+    f1 = 0.5 if f1 is None else f1      # parabolic_solve's default, lambda x: 0.5, without a Python call per node
+    if not callable(f1) and np.isscalar(f1) and not isinstance(f1, (str, bytes)):
+        f1 = np.full(n, float(f1))
+    try:
+        f_timed, f_row = _parabolic_forcing(f1, x, ts)
+    except (TypeError, ValueError) as e:
+        raise type(e)(str(e).replace("parabolic_solve:", "estimate_steps: f1:", 1))
+    fa = np.ascontiguousarray(np.stack([f_row(k) for k in range(B)]) if f_timed else f_row(0).reshape(1, n), dtype=np.float64)
+    hv = mask = None
+    if dirichlet is not None:
+        sel = _boundary_selection(dirichlet, b, "estimate_steps")
+        if sel is None:
+            raise ValueError("estimate_steps: dirichlet=None selects nothing")
+        hv, mask, _ = _neumann_data(geometry, 0.0 if neumann is None else neumann, sel == 0, ts[1:], "estimate_steps")
+        if hv.shape[0] not in (1, B):
+            raise ValueError("estimate_steps: neumann gives %d fields for %d steps" % (hv.shape[0], B))
+    if geometry._boundary_dev is None:
+        hd = C.c_void_p()
+        call("mgb_boundary_create", loc, geometry._geo, C.byref(hd))
+        geometry._boundary_dev = hd
+    nel = n // geometry.discretization["block"]
+    pv = HPCVector(pn, backend) if pn is not None else None
+    fv = HPCVector(fa, backend)
+    parts = HPCVector(B * nel * 4, backend)
+    sigma = HPCMatrix.__new__(HPCMatrix)
+    sigma.shape, sigma.backend, sigma._v = (B + 1, n * dim), backend, HPCVector((B + 1) * n * dim, backend)
+    table = (C.c_void_p * (B + 1))(*[v.handle.value for v, _ in vecs])
+    out = np.empty((B, 2, 5))
+    call("mgb_estimate_steps", geometry._boundary_dev, B, table, dptr(ts), S, u, p0, pv.handle if pv is not None else None, fv.handle,
+         fa.shape[0], float(r), float(scale), dptr(hv), 1 if hv is None else hv.shape[0], u8ptr(mask), sigma._v.handle, parts.handle,
+         dptr(out))
+    return StepIndicators(geometry, ts, parts, out, sigma, r)
+
+
+def refine_times(ts, marked) -> np.ndarray:
+    """The time twin of refine_triangles, on the host: the midpoint (ts[k] + ts[k + 1]) / 2 is inserted into every interval k of
+    `marked` (indices into the len(ts) - 1 intervals); every other time keeps its bits and its order.  An empty `marked` returns
+    a bitwise copy.  An index out of range, a duplicate, or a midpoint that does not fall strictly between its neighbours is a
+    ValueError."""
+    ts = np.array(ts, dtype=np.float64)
+    if ts.ndim != 1 or ts.size < 2:
+        raise ValueError("refine_times: ts must be a 1-D array with at least 2 entries")
+    if not np.all(np.isfinite(ts)) or not np.all(np.diff(ts) > 0):
+        raise ValueError("refine_times: ts must be finite and strictly increasing")
+    marked = np.asarray(marked).reshape(-1)
+    if marked.size and not np.issubdtype(marked.dtype, np.integer):
+        raise TypeError("refine_times: marked must hold interval indices")
+    marked = [int(k) for k in marked]
+    if any(not 0 <= k < ts.size - 1 for k in marked):
+        raise ValueError("refine_times: marked holds an index outside [0, %d)" % (ts.size - 1))
+    if len(set(marked)) != len(marked):
+        raise ValueError("refine_times: marked holds an interval twice")
+    chosen, out = set(marked), []
+    for k in range(ts.size - 1):
+        out.append(ts[k])
+        if k in chosen:
+            mid = (ts[k] + ts[k + 1]) / 2
+            if not ts[k] < mid < ts[k + 1]:
+                raise ValueError("refine_times: the midpoint of interval %d does not fall strictly between its end points" % k)
+            out.append(mid)
+    out.append(ts[-1])
+    return np.array(out, dtype=np.float64)
+
+
+def adapt_time(geometry, ts, p, steps, theta=0.5, **kw) -> list:
+    """Solve, estimate, mark, refine the times, solve again: the time twin of adapt.  Every round runs parabolic_solve(geometry,
+    ts=ts, p=p, **kw) and estimate_steps on it; the time indicators h_k time_k feed mark(., theta) and refine_times gives the next
+    ts.  Returns the steps + 1 triples (ts, par, StepIndicators), the last one on the finest grid.  f1, dirichlet and neumann of
+    `kw` also go to estimate_steps."""
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("adapt_time: steps must be >= 0")
+    ts = np.array(ts, dtype=np.float64)
+    est_kw = {k: kw[k] for k in ("f1", "dirichlet", "neumann") if k in kw}
+    out = []
+    for step in range(steps + 1):
+        par = parabolic_solve(geometry, p=p, ts=ts, **kw)
+        ind = estimate_steps(par, p, **est_kw)
+        out.append((ts, par, ind))
+        if step < steps:
+            ts = refine_times(ts, mark(ind.hs * ind.time, theta))
     return out
 
 

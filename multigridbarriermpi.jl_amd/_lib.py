@@ -156,6 +156,10 @@ PROTOTYPES = {
     "mgb_estimate": [H, H, C.c_int, C.c_int, C.c_double, H, H, C.c_double, C.c_int, C.c_double, c_dbl_p, c_u8_p, H, c_dbl_p],
     "mgb_geo_estimate_host": [H, c_dbl_p, C.c_int, C.c_int, C.c_double, c_dbl_p, c_dbl_p, C.c_double, C.c_int, C.c_double, c_dbl_p,
                               c_u8_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p],
+    "mgb_estimate_steps": [H, C.c_int, C.POINTER(H), c_dbl_p, C.c_int, C.c_int, C.c_double, H, H, C.c_int, C.c_double, C.c_double,
+                           c_dbl_p, C.c_int, c_u8_p, H, H, c_dbl_p],
+    "mgb_geo_estimate_steps_host": [H, C.c_int, C.POINTER(c_dbl_p), c_dbl_p, C.c_int, C.c_int, C.c_double, c_dbl_p, c_dbl_p, C.c_int,
+                                    C.c_double, C.c_double, c_dbl_p, C.c_int, c_u8_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_geo_dirichlet_on": [H, C.c_char_p, c_u8_p],
     "mgb_geo_boundary_incidence": [H, c_int_p, c_int_p, c_i32_p, c_i32_p, c_i32_p],
     "mgb_boundary_incidence": [H, c_int_p, c_int_p, c_i32_p, c_i32_p, c_i32_p],

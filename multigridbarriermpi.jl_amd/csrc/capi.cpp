@@ -69,6 +69,8 @@ struct mgb_boundary_s {
   DevBuf<int> inodes, elem_facet;
   DevBuf<double> iweights, inormal;
   DevBuf<double> est_sigma, est_J, est_N, est_scratch, est_h;      // ... flux, per-facet values, partials, Neumann data: grown on demand
+  DevBuf<double> est_dt;                           // mgb_estimate_steps: the step sizes of the call ...
+  DevBuf<const double*> est_table;                 // ... and the device table of its snapshots, uploaded per call
 };
 struct mgb_plan_s {
   LevelPlan plan;
@@ -1728,6 +1730,156 @@ int mgb_geo_estimate_host(mgb_geo g, const double* z, int S, int u, double p, co
     }
     if (sigma_out) std::copy(sigma.begin(), sigma.end(), sigma_out);
     std::copy(res, res + reduce::kCols, out);
+  });
+}
+
+// ---- error indicators of the steps of a parabolic run (estimate.hpp / estimate.hip)
+namespace {
+void need_steps_shape(const char* who, int B, const double* ts, int S, int u, double p, double r, double scale, bool has_f, int f_rows,
+                      bool has_h, int h_rows) {
+  const std::string w(who);
+  need_field_shape(w, B, S, u, p);
+  if (B + 1 > 65535) throw std::invalid_argument(w + ": at most 65535 snapshots per call");
+  for (int k = 0; k <= B; ++k)
+    if (!std::isfinite(ts[k]) || (k > 0 && !(ts[k] > ts[k - 1]))) throw std::invalid_argument(w + ": ts must be finite and strictly increasing");
+  if (!good_q(r)) throw std::invalid_argument(w + ": r must be finite and >= 1");
+  if (!std::isfinite(scale)) throw std::invalid_argument(w + ": the scale must be finite");
+  if (has_f && f_rows != 1 && f_rows != B) throw std::invalid_argument(w + ": f must have 1 or B rows");
+  if (has_h && h_rows != 1 && h_rows != B) throw std::invalid_argument(w + ": h must have 1 or B rows");
+}
+}  // namespace
+int mgb_estimate_steps(mgb_boundary bd, int B, const mgb_vec* z, const double* ts_host, int S, int u, double p, mgb_vec p_nodal,
+                       mgb_vec f, int f_rows, double r, double scale, const double* h_host, int h_rows, const unsigned char* mask_host,
+                       mgb_vec sigma, mgb_vec parts, double* out_host) {
+  return guard([&] {
+    need(bd && z && ts_host && sigma && parts && out_host, "estimate_steps: null argument");
+    need_steps_shape("estimate_steps", B, ts_host, S, u, p, r, scale, f != nullptr, f_rows, h_host != nullptr, h_rows);
+    mgb_locator_s* loc = bd->loc;
+    need(loc->ctx->ctx.world == 1, "estimate_steps: sharded contexts are not supported");
+    const interp::Locator& L = loc->loc;
+    const boundary::Facets& F = bd->F;
+    const boundary::Interior& I = bd->I;
+    std::vector<const double*> table;
+    field_table("estimate_steps", loc, B + 1, z, S, table);
+    need(sigma->n == (long long)(B + 1) * L.n * L.dim, "estimate_steps: sigma must hold (B + 1) x n x dim values");
+    need(parts->n == (long long)B * I.nel * estimate::kStepParts, "estimate_steps: parts must hold B x nel x 4 values");
+    need(!p_nodal || p_nodal->n == L.n, "estimate_steps: p_nodal must hold n values");
+    need(!f || f->n == (long long)f_rows * L.n, "estimate_steps: f must hold f_rows x n values");
+    need(sigma->ctx == loc->ctx && parts->ctx == loc->ctx && (!p_nodal || p_nodal->ctx == loc->ctx) && (!f || f->ctx == loc->ctx),
+         "estimate_steps: vectors of another context");
+    need(sigma != parts && sigma != p_nodal && sigma != f && parts != p_nodal && parts != f, "estimate_steps: an output is also an input");
+    for (int b = 0; b <= B; ++b) need(z[b] != sigma && z[b] != parts, "estimate_steps: an output is also an input");
+    const bool neu = h_host != nullptr && F.nf > 0;
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const int facets = I.nif + (neu ? F.nf : 0);
+    const size_t nJ = (size_t)B * I.nif, nN = (size_t)B * F.nf, nd = estimate::scratch_doubles(I.nel, L.block, facets, F.q, B, 2),
+                 nh = (size_t)(neu ? h_rows : 0) * F.nf * F.q;
+    // an earlier call's launches may still read the buffers: wait before any of them is replaced
+    if (bd->est_J.n < nJ || bd->est_scratch.n < nd || (neu && (bd->est_N.n < nN || bd->est_h.n < nh ||
+        (mask_host && bd->mask.n < (size_t)F.nf)))) {
+      hip_check(hipStreamSynchronize(st), "sync estimate_steps");
+      if (bd->est_J.n < nJ) bd->est_J.alloc(nJ);
+      if (bd->est_scratch.n < nd) bd->est_scratch.alloc(nd);
+      if (neu && bd->est_N.n < nN) bd->est_N.alloc(nN);
+      if (neu && bd->est_h.n < nh) bd->est_h.alloc(nh);
+      if (neu && mask_host && bd->mask.n < (size_t)F.nf) bd->mask.alloc((size_t)F.nf);
+    }
+    std::vector<double> dt((size_t)B);
+    for (int k = 0; k < B; ++k) dt[k] = ts_host[k + 1] - ts_host[k];
+    bd->est_dt.upload(dt.data(), dt.size());
+    bd->est_table.upload(table.data(), table.size());
+    if (neu) {
+      hip_check(hipMemcpyAsync(bd->est_h.p, h_host, nh * sizeof(double), hipMemcpyHostToDevice, st), "H2D h");
+      if (mask_host) hip_check(hipMemcpyAsync(bd->mask.p, mask_host, (size_t)F.nf, hipMemcpyHostToDevice, st), "H2D mask");
+    }
+    energy::Args E;
+    E.own = L.view(loc->cellptr.p, loc->cellelem.p, loc->x.p);
+    E.w = loc->w.p;
+    E.p_nodal = p_nodal ? p_nodal->buf.p : nullptr;
+    E.p = p;
+    E.z = bd->est_table.p;
+    E.n = L.n, E.S = S, E.u = u, E.B = B + 1;
+    energy::launch_field_flux(st, L.dim, L.k, E, nullptr, sigma->buf.p);
+    hip_check(hipGetLastError(), "estimate_steps flux launch");
+    estimate::Args A;
+    A.own = E.own;
+    A.w = E.w, A.p_nodal = E.p_nodal, A.p = p;
+    A.sigma = sigma->buf.p;
+    A.f = f ? f->buf.p : nullptr;
+    A.f_stride = f && f_rows == B && B > 1 ? L.n : 0;
+    A.r = r, A.scale = scale, A.own_scale = true;
+    A.n = L.n, A.nel = I.nel, A.nlf = I.nlf, A.q = F.q;
+    A.inodes = bd->inodes.p, A.iweights = bd->iweights.p, A.inormal = bd->inormal.p, A.nif = I.nif;
+    A.bnodes = bd->nodes.p, A.bweights = bd->weights.p, A.bnormal = bd->normal.p;
+    A.mask = neu && mask_host ? bd->mask.p : nullptr;
+    A.h = neu ? bd->est_h.p : nullptr;
+    A.h_stride = neu && h_rows == B && B > 1 ? (long long)F.nf * F.q : 0;
+    A.nf = F.nf;
+    A.elem_facet = bd->elem_facet.p;
+    A.B = B, A.steps = true;
+    A.z = bd->est_table.p, A.S = S, A.u = u, A.dt = bd->est_dt.p;
+    estimate::launch_estimate(st, L.dim, L.k, A, bd->est_J.p, bd->est_N.p, parts->buf.p, bd->est_scratch.p);
+    hip_check(hipGetLastError(), "estimate_steps launch");
+    hip_check(hipStreamSynchronize(st), "sync estimate_steps");
+    hip_check(hipMemcpy(out_host, bd->est_scratch.p + estimate::results_offset(I.nel, L.block, facets, F.q, B, 2),
+                        (size_t)B * 2 * reduce::kCols * sizeof(double), hipMemcpyDeviceToHost), "D2H");
+  });
+}
+int mgb_geo_estimate_steps_host(mgb_geo g, int B, const double* const* z, const double* ts, int S, int u, double p,
+                                const double* p_nodal, const double* f, int f_rows, double r, double scale, const double* h, int h_rows,
+                                const unsigned char* mask, double* sigma_out, double* parts, double* J, double* N, double* out) {
+  return guard([&] {
+    need(g && z && ts && parts && out, "geo_estimate_steps_host: null argument");
+    need_steps_shape("geo_estimate_steps_host", B, ts, S, u, p, r, scale, f != nullptr, f_rows, h != nullptr, h_rows);
+    for (int b = 0; b <= B; ++b) need(z[b] != nullptr, "geo_estimate_steps_host: null field");
+    need(g->g.w.size() == (size_t)g->g.n, "geo_estimate_steps_host: the geometry must carry one weight per node");
+    if (p_nodal)
+      for (int i = 0; i < g->g.n; ++i) need(good_q(p_nodal[i]), "geo_estimate_steps_host: every p_nodal must be finite and >= 1");
+    boundary::Facets F;
+    boundary::Interior I;
+    boundary::build_facet_lists(g->g, &F, &I);
+    const int n = g->g.n, dim = F.dim;
+    energy::Args E;
+    E.own.block = g->g.block;
+    E.own.nel = n / g->g.block;
+    E.own.x = g->g.x.data();
+    E.w = g->g.w.data();
+    E.p_nodal = p_nodal;
+    E.p = p;
+    E.n = n, E.S = S, E.u = u, E.B = 1;
+    const size_t nsig = (size_t)n * dim;
+    std::vector<double> sigma((size_t)(B + 1) * nsig), Jv((size_t)B * I.nif), Nv((size_t)B * F.nf), dt((size_t)B);
+    for (int b = 0; b <= B; ++b) estimate::field_flux_host(dim, F.k, E, z[b], sigma.data() + (size_t)b * nsig);
+    for (int k = 0; k < B; ++k) dt[k] = ts[k + 1] - ts[k];
+    const bool neu = h != nullptr && F.nf > 0;
+    estimate::Args A;
+    A.own = E.own;
+    A.w = E.w, A.p_nodal = p_nodal, A.p = p;
+    A.sigma = sigma.data();
+    A.f = f;
+    A.f_stride = f && f_rows == B && B > 1 ? n : 0;
+    A.r = r, A.scale = scale, A.own_scale = true;
+    A.n = n, A.nel = I.nel, A.nlf = I.nlf, A.q = F.q;
+    A.inodes = I.nodes.data(), A.iweights = I.weights.data(), A.inormal = I.normal.data(), A.nif = I.nif;
+    A.bnodes = F.nodes.data(), A.bweights = F.weights.data(), A.bnormal = F.normal.data();
+    A.mask = neu ? mask : nullptr;
+    A.h = neu ? h : nullptr;
+    A.h_stride = neu && h_rows == B && B > 1 ? (long long)F.nf * F.q : 0;
+    A.nf = F.nf;
+    A.elem_facet = I.elem_facet.data();
+    A.B = B, A.steps = true;
+    A.z = z, A.S = S, A.u = u, A.dt = dt.data();
+    std::vector<double> pv((size_t)B * I.nel * estimate::kStepParts), res((size_t)B * 2 * reduce::kCols);
+    estimate::estimate_host(dim, F.k, A, pv.data(), Jv.data(), Nv.data(), res.data());
+    std::copy(pv.begin(), pv.end(), parts);
+    if (J) std::copy(Jv.begin(), Jv.end(), J);
+    if (N) {
+      if (neu) std::copy(Nv.begin(), Nv.end(), N);
+      else std::fill(N, N + (size_t)B * F.nf, 0.0);
+    }
+    if (sigma_out) std::copy(sigma.begin(), sigma.end(), sigma_out);
+    std::copy(res.begin(), res.end(), out);
   });
 }
 

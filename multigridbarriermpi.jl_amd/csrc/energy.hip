@@ -7,7 +7,9 @@
 // The fields come as a device table of B pointers: the snapshots of a parabolic run are separate allocations and are not copied.
 // What a field's result is made of depends on n alone, never on B or on the field's place in the batch: a batch gives the bits
 // of its fields reduced one by one.
-//   flux_kernel<DIM, K>: one thread per node writes sigma = a^(p-2) g, dim doubles.
+//   flux_kernel<DIM, K>: grid (workgroups(n), B); one thread per node of field blockIdx.y writes sigma = a^(p-2) g, dim
+//     doubles, into row blockIdx.y of flux (B x n x dim).  The fields come through the device table A.z, or, where A.z is null,
+//     as the ONE field z (mgb_geo_field_flux, mgb_estimate: no table to upload).
 #include "energy.hpp"
 
 namespace mgb {
@@ -37,13 +39,14 @@ __global__ void __launch_bounds__(kThreads) energy_kernel(Args A, double* __rest
 template <int DIM, int K>
 __global__ void __launch_bounds__(kThreads) flux_kernel(Args A, const double* __restrict__ z, double* __restrict__ flux) {
   const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= A.n) return;
+  if (i >= A.n) return;      // no barrier in this kernel
+  const int b = blockIdx.y;
   Node<DIM, K> N;
   N.init(A, (int)i);
   double sigma[DIM];
-  N.flux(z, A.S, A.u, sigma);
+  N.flux(A.z ? A.z[b] : z, A.S, A.u, sigma);
 #pragma unroll
-  for (int k = 0; k < DIM; ++k) flux[(size_t)i * DIM + k] = sigma[k];
+  for (int k = 0; k < DIM; ++k) flux[((size_t)b * A.n + i) * DIM + k] = sigma[k];
 }
 
 struct LaunchEnergy {
@@ -65,7 +68,7 @@ struct LaunchFlux {
   double* flux;
   template <int DIM, int K>
   void operator()() const {
-    hipLaunchKernelGGL((flux_kernel<DIM, K>), dim3((unsigned)workgroups(A.n)), dim3(kThreads), 0, stream, A, z, flux);
+    hipLaunchKernelGGL((flux_kernel<DIM, K>), dim3((unsigned)workgroups(A.n), (unsigned)A.B), dim3(kThreads), 0, stream, A, z, flux);
   }
 };
 
@@ -78,7 +81,8 @@ void launch_field_energy(hipStream_t stream, int dim, int k, const Args& A, doub
 }
 
 void launch_field_flux(hipStream_t stream, int dim, int k, const Args& A, const double* z, double* flux) {
-  if (A.n <= 0 || A.S <= 0) throw ArgError("field_flux: empty field");
+  if (A.n <= 0 || A.S <= 0 || A.B <= 0 || A.B > 65535) throw ArgError("field_flux: empty field, or more than 65535 fields");
+  if ((A.z == nullptr) == (z == nullptr) || (z && A.B != 1)) throw ArgError("field_flux: one field, or a table of B fields");
   LaunchFlux l{stream, A, z, flux};
   interp::dispatch(dim, k, l);
 }

@@ -153,7 +153,8 @@ inline size_t results_offset(int n, int B) { return (size_t)workgroups(n) * B * 
 // field; all pointers of A are device pointers (A.z a device table of B device pointers); the B x kCols results are at
 // scratch + results_offset
 void launch_field_energy(hipStream_t stream, int dim, int k, const Args& A, double* scratch);
-// one launch, one thread per node: flux (n x dim) of the field z; of A the geometry, exponent, S and u are read
+// one launch on grid (workgroups, A.B), one thread per node: flux (A.B x n x dim) of the fields of the device table A.z, or of
+// the ONE field z where A.z is null (then A.B = 1); of A the geometry, exponent, S, u, B and z are read
 void launch_field_flux(hipStream_t stream, int dim, int k, const Args& A, const double* z, double* flux);
 #endif
 

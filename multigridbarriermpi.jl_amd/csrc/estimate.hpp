@@ -19,6 +19,24 @@
 //   A non-finite Sigma, f or h, or an exponent that is not a finite real >= 1, makes the term it feeds NaN, and with it the
 //   numbers of the element and the totals; the maxima are NaN-sticky.
 // The arithmetic is kept as written (fp contract off), as energy.hpp's is.
+//
+// Steps of a parabolic run.  Snapshots Z_0 .. Z_B at strictly increasing times, h_k = ts[k] - ts[k-1];
+// step k = 1..B solved  min int (1/2h_k)(s1 - 2 u u_(k-1)) + (1/p) s2 + f_k u,  whose strong form is
+// (u_k - u_(k-1)) / h_k + f_k - div sigma_k = 0  with the natural condition  sigma_k . n + h_k^N = 0: the residual above with
+// lambda = scale (own_scale) and ONE more term.  Field b = k - 1 of a call with Args::steps set:
+//   Sigma^m, m = 0..B: the nodal flux of snapshot m, (B + 1) x n x dim; step k reads Sigma^k and Sigma^(k-1).
+//   Node i:     d_i = (u^k_i - u^(k-1)_i) / h_k, a subtraction, then a division;  rho_i = (f_k,i + d_i) - lambda div(I Sigma^k)(x_i);
+//               rate term  w_i |d_i|^r;  time term  w_i |Sigma^k_i - Sigma^(k-1)_i|_2^r, the 2-norm a square root of the squares
+//               summed in ascending component order, the power through powq.
+//   Element e:  vol, jump, neu from Sigma^k as above (Neumann data of the step's new time);  tim_e = sum_{i in e} of the time terms,
+//               local i ascending.  Four numbers per (step, element): vol, jump, neu, tim.
+//   Two rows of totals per step, through reduce::combine:  row 0 as above;
+//               row 1:  sum tim | sum_i w_i |d_i|^r | 0 | max_e tim_e | max_i |d_i|  (the rate sum per element in ascending local
+//               order, then over the elements).
+//   A non-finite u^k_i, u^(k-1)_i or h_k makes d_i NaN, a non-finite Sigma^k_i or Sigma^(k-1)_i the time term; a NaN in snapshot m
+//   reaches steps m and m + 1 and no other.  What a step's numbers are made of depends on its two snapshots, its f, h and h_k
+//   alone: a batch of B steps gives the bits of B calls with B = 1.  Where both snapshots of a step hold the same values, d = 0
+//   exactly, rho = (f + 0.0) - lambda div, and row 0 and vol, jump, neu are those of the single field with own_scale.
 #pragma once
 #include "boundary.hpp"
 
@@ -27,6 +45,7 @@ namespace estimate {
 
 using namespace reduce;       // kCols (MGB_ESTIMATE_COLS), kThreads, combine, nanmax
 constexpr int kParts = 3;     // vol, jump, neu
+constexpr int kStepParts = 4; // vol, jump, neu, tim of a step
 using norms::powq;
 
 struct Args {
@@ -53,7 +72,23 @@ struct Args {
   const double* h = nullptr;               // nf x q
   int nf = 0;
   const int* elem_facet = nullptr;         // nel x nlf: interior facet, or -1 - boundary facet
+  // B fields in one call (blockIdx.y); steps: field b is step b + 1 of a parabolic run and the members below are read.  In a
+  // call, sigma is the first flux ((B + 1) x n x dim for steps), f and h the first rows; field() moves them to one field
+  int B = 1;
+  bool steps = false;
+  const double* const* z = nullptr;        // B + 1 snapshots of n x S
+  int S = 0, u = 0;
+  const double* dt = nullptr;              // B step sizes h_k
+  long long f_stride = 0, h_stride = 0;    // 0: one row for every step; n and nf x q: a row per step
+  // of ONE field, set by field(): the previous flux, the two snapshots and the step size
+  const double* sigma_prev = nullptr;
+  const double* z_new = nullptr;
+  const double* z_old = nullptr;
+  double hk = 1.0;
 };
+
+inline int parts_of(const Args& A) { return A.steps ? kStepParts : kParts; }
+inline int rows_of(const Args& A) { return A.steps ? 2 : 1; }
 
 // every column is a sum or a maximum of non-negative values: zeros, which hides reduce::identity and its -inf
 MGB_HD void identity(double* c) { c[0] = c[1] = c[2] = c[3] = c[4] = 0.0; }
@@ -73,8 +108,58 @@ MGB_HD double diameter(double ws) {
 
 template <int DIM, int K>
 struct Terms {
-  // w_i |rho_i|^r of node i
-  MGB_HD static double node(const Args& A, int i) {
+  // field b of a call: what the routines below read
+  MGB_HD static Args field(const Args& A, int b) {
+    Args a = A;
+    if (!A.steps) return a;      // one field: the call's pointers are the field's
+    const size_t nsig = (size_t)A.n * DIM;
+    a.sigma_prev = A.sigma + (size_t)b * nsig;
+    a.sigma = A.sigma + ((size_t)b + 1) * nsig;
+    if (A.f) a.f = A.f + (size_t)b * A.f_stride;
+    if (A.h) a.h = A.h + (size_t)b * A.h_stride;
+    a.z_old = A.z[b];
+    a.z_new = A.z[b + 1];
+    a.hk = A.dt[b];
+    return a;
+  }
+
+  // d_i = (u^k_i - u^(k-1)_i) / h_k of node i of a step
+  MGB_HD static double quotient(const Args& A, int i) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double a = A.z_new[(size_t)i * A.S + A.u], b = A.z_old[(size_t)i * A.S + A.u];
+    bool good = interp::finite(a);
+    good = good & interp::finite(b);
+    good = good & interp::finite(A.hk);
+    if (!good) return nan();
+    const double diff = a - b;
+    return diff / A.hk;
+  }
+
+  // the step-only numbers of node i from its d:  tim = w_i |Sigma^k_i - Sigma^(k-1)_i|_2^r,  rate = w_i |d_i|^r,  ad = |d_i|
+  MGB_HD static void step(const Args& A, int i, double d, double& tim, double& rate, double& ad) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const double* sn = A.sigma + (size_t)i * DIM;
+    const double* so = A.sigma_prev + (size_t)i * DIM;
+    bool good = true;
+    double ss = 0.0;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {
+      const double diff = sn[k] - so[k];
+      ss += diff * diff;
+      good = good & interp::finite(sn[k]);
+      good = good & interp::finite(so[k]);
+    }
+    tim = good ? A.w[i] * powq(sqrt(ss), A.r) : nan();
+    ad = fabs(d);      // NaN stays NaN
+    rate = A.w[i] * powq(ad, A.r);
+  }
+
+  // w_i |rho_i|^r of node i; d = d_i of a step, not read for a single field
+  MGB_HD static double node(const Args& A, int i, double d = 0.0) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -95,8 +180,9 @@ struct Terms {
     bool good = good_exponent(pi);
     good = good & interp::finite(fi);
     good = good & interp::finite(div);
+    if (A.steps) good = good & (d == d);
     if (!good) return nan();
-    const double rho = fi - lambda(A, i) * div;
+    const double rho = (A.steps ? fi + d : fi) - lambda(A, i) * div;
     return A.w[i] * powq(fabs(rho), A.r);
   }
 
@@ -178,48 +264,81 @@ MGB_HD void element_columns(const double* parts, double* c) {
   c[4] = 0.0;
 }
 
-// host restatement: the same routines, serially -- facets, then elements in ascending order
+// the element's contribution to row 1 of a step: tim_e, its rate sum and its largest |d_i|
+MGB_HD void step_columns(double tim, double rate, double dmax, double* c) {
+  c[0] = tim;
+  c[1] = rate;
+  c[2] = 0.0;
+  c[3] = tim;
+  c[4] = dmax;
+}
+
+// host restatement: the same routines, serially -- field after field; in a field the facets, then the elements in ascending order
 struct HostEstimate {
-  Args A;
-  double* eta;      // nel x kParts
-  double* J;        // nif
-  double* N;        // nf or null (no Neumann data)
-  double* out;      // kCols
+  Args A;           // the call: A.B fields
+  double* eta;      // B x nel x parts_of(A)
+  double* J;        // B x nif
+  double* N;        // B x nf or null (no Neumann data)
+  double* out;      // B x rows_of(A) x kCols
   template <int DIM, int K>
   void operator()() const {
     using T = Terms<DIM, K>;
-    double acc[kCols];
-    identity(acc);
-    for (int F = 0; F < A.nif; ++F) {
-      double s = 0.0;
-      for (int j = 0; j < A.q; ++j) {
-        double aj;
-        s += T::jump(A, F, j, aj);
-        acc[4] = nanmax(acc[4], aj);
-      }
-      J[F] = s;
-    }
-    if (A.h)
-      for (int F = 0; F < A.nf; ++F) {
+    const int block = A.own.block, np = parts_of(A), nr = rows_of(A);
+    for (int b = 0; b < A.B; ++b) {
+      const Args Ab = T::field(A, b);
+      double* Jb = J + (size_t)b * A.nif;
+      double* Nb = A.h ? N + (size_t)b * A.nf : nullptr;
+      double acc[kCols], acc1[kCols];
+      identity(acc);
+      identity(acc1);
+      for (int F = 0; F < A.nif; ++F) {
         double s = 0.0;
-        if (!A.mask || A.mask[F])
-          for (int j = 0; j < A.q; ++j) s += T::neumann(A, F, j);
-        N[F] = s;
+        for (int j = 0; j < A.q; ++j) {
+          double aj;
+          s += T::jump(Ab, F, j, aj);
+          acc[4] = nanmax(acc[4], aj);
+        }
+        Jb[F] = s;
       }
-    const int block = A.own.block;
-    for (int e = 0; e < A.nel; ++e) {
-      double ts = 0.0, ws = 0.0;
-      for (int li = 0; li < block; ++li) {
-        ts += T::node(A, e * block + li);
-        ws += A.w[e * block + li];
+      if (A.h)
+        for (int F = 0; F < A.nf; ++F) {
+          double s = 0.0;
+          if (!A.mask || A.mask[F])
+            for (int j = 0; j < A.q; ++j) s += T::neumann(Ab, F, j);
+          Nb[F] = s;
+        }
+      for (int e = 0; e < A.nel; ++e) {
+        double ts = 0.0, ws = 0.0, tim = 0.0, rate = 0.0, dmax = 0.0;
+        for (int li = 0; li < block; ++li) {
+          const int i = e * block + li;
+          double d = 0.0;
+          if (A.steps) {
+            double t, rt, ad;
+            d = T::quotient(Ab, i);
+            T::step(Ab, i, d, t, rt, ad);
+            tim += t;
+            rate += rt;
+            dmax = nanmax(dmax, ad);
+          }
+          ts += T::node(Ab, i, d);
+          ws += A.w[i];
+        }
+        double* parts = eta + ((size_t)b * A.nel + e) * np;
+        T::element(Ab, e, ts, ws, Jb, Nb, parts);
+        double c[kCols];
+        element_columns(parts, c);
+        combine(acc, c);
+        if (A.steps) {
+          parts[3] = tim;
+          step_columns(tim, rate, dmax, c);
+          combine(acc1, c);
+        }
       }
-      double* parts = eta + (size_t)e * kParts;
-      T::element(A, e, ts, ws, J, A.h ? N : nullptr, parts);
-      double c[kCols];
-      element_columns(parts, c);
-      combine(acc, c);
+      double* row = out + (size_t)b * nr * kCols;
+      for (int k = 0; k < kCols; ++k) row[k] = acc[k];
+      if (A.steps)
+        for (int k = 0; k < kCols; ++k) row[kCols + k] = acc1[k];
     }
-    for (int k = 0; k < kCols; ++k) out[k] = acc[k];
   }
 };
 
@@ -258,18 +377,20 @@ inline long long element_workgroups(int nel, int block) {
   const int epw = kThreads / block;
   return ((long long)nel + epw - 1) / epw;
 }
-// doubles of scratch: element partials (kCols each), facet partial maxima, then the kCols results
-inline size_t scratch_doubles(int nel, int block, int facets, int q) {
-  return (size_t)element_workgroups(nel, block) * kCols + (size_t)facet_workgroups(facets, q) + kCols;
+// doubles of scratch of a call of B fields with R rows of totals each: element partials (B x R x workgroups x kCols), facet
+// partial maxima (B x workgroups), then the B x R x kCols results
+inline size_t results_offset(int nel, int block, int facets, int q, int B = 1, int R = 1) {
+  return (size_t)B * ((size_t)R * element_workgroups(nel, block) * kCols + (size_t)facet_workgroups(facets, q));
 }
-inline size_t results_offset(int nel, int block, int facets, int q) {
-  return (size_t)element_workgroups(nel, block) * kCols + (size_t)facet_workgroups(facets, q);
+inline size_t scratch_doubles(int nel, int block, int facets, int q, int B = 1, int R = 1) {
+  return results_offset(nel, block, facets, q, B, R) + (size_t)B * R * kCols;
 }
 
 #if defined(__HIPCC__)
 // estimate.hip: up to three launches on `stream` behind the flux launch that wrote A.sigma -- facet_terms_kernel (left out when
-// there is no facet), element_indicator_kernel, estimate_finish.  All pointers are device pointers; J: nif, N: nf (read only
-// where A.h is set), eta: nel x kParts; the kCols results are at scratch + results_offset
+// there is no facet), element_indicator_kernel, estimate_finish, each with the field in blockIdx.y (the finish: one workgroup
+// per row of totals).  All pointers are device pointers; J: B x nif, N: B x nf (read only where A.h is set), eta: B x nel x
+// parts_of(A); the B x rows_of(A) x kCols results are at scratch + results_offset
 void launch_estimate(hipStream_t stream, int dim, int k, const Args& A, double* J, double* N, double* eta, double* scratch);
 #endif
 
