@@ -230,6 +230,24 @@ int mgb_amg_solve_linear(mgb_amg a, int level, const double* lower_vals, const d
 /* the same solve with the device multifrontal Cholesky (csrc/gpuchol.hip): the solver the Newton loop uses
  * by default.  Returns MGB_E_NUMERIC if a pivot is not positive. */
 int mgb_amg_solve_linear_gpu(mgb_amg a, int level, const double* lower_vals, const double* g, double* x);
+/* The owner-local pieces of a sharded Newton step, one call each, through the functions the solve itself calls (tests).
+ * Inside a solve on a sharded context whose factorisation keeps its values local (mgb_amg_chol_values_local) the Newton
+ * vectors are valid on a rank's own unknowns and on the replicated top only; the entry points above take the
+ * allreduce-everything branches instead.  MGB_E_ARG on an unsharded context ("sharded contexts only") and on a level whose
+ * values are summed over the ranks.  Collective: every rank calls them in the same order.
+ *   f1_owner: g [N] = the gradient as the device holds it, complete where kind >= 1 (top entries summed over the ranks: the
+ *     one collective of ntop + 1 doubles); *gg = |g|^2 summed over the owners, as the device produced it; kind [N] per
+ *     unknown: 0 = interior of another rank's subtree, 1 = of this rank's, 2 = top (separator).  gg, kind nullable.
+ *   f2_local: this rank's contributions to the Hessian values (lower triangle, pattern order), before any reduction.
+ *   solve_linear_local: local_vals = this rank's contributions to the matrix, g valid where kind >= 1.  x [N] = the solution
+ *     where kind >= 1, zero elsewhere; *inc = <g, x> and *flag (1 = a pivot was not positive on some rank, else 0) as the
+ *     step's one scalar collective left them -- a non-positive pivot is RETURNED, never MGB_E_NUMERIC, so the ranks stay in
+ *     lock step; vals_after [nnz] = the values buffer behind the solve (entries among top unknowns <- their sums over the
+ *     ranks, every other entry untouched).  inc, flag, vals_after nullable. */
+int mgb_amg_f1_owner(mgb_amg a, int level, const double* s, double t, double* g, double* gg, int32_t* kind);
+int mgb_amg_f2_local(mgb_amg a, int level, const double* s, double t, double* lower_vals);
+int mgb_amg_solve_linear_local(mgb_amg a, int level, const double* local_vals, const double* g, double* x, double* inc,
+                               int* flag, double* vals_after);
 /* Newton linear solver: 0 (default) = GPU multifrontal Cholesky, 1 = host multifrontal Cholesky, 2 = conjugate gradients
  * preconditioned by a V-cycle over the AMG levels, H applied matrix-free (single-GPU contexts; see the multigrid block below) */
 int mgb_amg_set_solver(mgb_amg a, int solver);

@@ -1113,6 +1113,34 @@ class AMG:
              dptr(lower_vals), dptr(g), dptr(x))
         return x
 
+    # ---- the owner-local pieces of a sharded Newton step, one call each (include/mgb_hip.h: mgb_amg_f1_owner ...).  Collective:
+    # every rank calls them in the same order; sharded contexts whose factorisation keeps its values local only.
+    def f1_owner(self, l, s, t):
+        """(g, gg, kind): the gradient as the device holds it inside a sharded solve (complete where kind >= 1), |g|^2 as the
+        device summed it over the owners, and per unknown 0 = another rank's, 1 = own, 2 = top (separator)."""
+        s = f64(s)
+        N = self.level_size(l)[0]
+        g, gg, kind = np.empty(N), C.c_double(), np.empty(N, dtype=np.int32)
+        call("mgb_amg_f1_owner", self.handle, l, dptr(s), float(t), dptr(g), C.byref(gg), iptr(kind))
+        return g, gg.value, kind
+
+    def f2_local(self, l, s, t):
+        """This rank's contributions to the lower-triangle Hessian values (order of hessian_pattern(l)), before any reduction."""
+        s = f64(s)
+        vals = np.empty(self.level_size(l)[1])
+        call("mgb_amg_f2_local", self.handle, l, dptr(s), float(t), dptr(vals))
+        return vals
+
+    def solve_linear_local(self, l, local_vals, g):
+        """(x, inc, flag, vals_after) of the owner-local solve on this rank's contributions `local_vals` and a g valid where
+        kind >= 1: x is zero where kind = 0, inc = <g, x> over the owners, flag = 1 if a pivot was not positive on some rank
+        (returned, never raised), vals_after = the values buffer behind the solve (top entries <- their sums)."""
+        local_vals, g = f64(local_vals), f64(g)
+        x, inc, flag, after = np.empty_like(g), C.c_double(), C.c_int(), np.empty_like(local_vals)
+        call("mgb_amg_solve_linear_local", self.handle, l, dptr(local_vals), dptr(g), dptr(x), C.byref(inc), C.byref(flag),
+             dptr(after))
+        return x, inc.value, flag.value, after
+
     SOLVERS = {"gpu": 0, "host": 1, "pcg": 2}
 
     def set_solver(self, solver="gpu"):

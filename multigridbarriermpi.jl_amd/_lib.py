@@ -116,6 +116,9 @@ PROTOTYPES = {
                           c_dbl_p],
     "mgb_amg_solve_linear": [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_amg_solve_linear_gpu": [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p],
+    "mgb_amg_f1_owner": [H, C.c_int, c_dbl_p, C.c_double, c_dbl_p, c_dbl_p, c_i32_p],
+    "mgb_amg_f2_local": [H, C.c_int, c_dbl_p, C.c_double, c_dbl_p],
+    "mgb_amg_solve_linear_local": [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p],
     "mgb_amg_set_solver": [H, C.c_int],
     "mgb_amg_set_schedule": [H, C.c_int],
     "mgb_amg_set_stop_rule": [H, C.c_int],

@@ -455,6 +455,9 @@ Amg::Amg(Ctx& ctx, const GeometryHost& g, const AmgSpec& spec, const BarrierPara
     shard_rows(ctx_.rank, ctx_.world, ng_, g.block, &r0_, &r1);
     n_ = r1 - r0_;
     Dstack_.upload(shard_dstack(Dstack, ng_, S_, P.K, r0_, r1));
+    // lanes per row as on one GPU: a row's terms are added in the same order whatever the row partition is, so a rank's rows of
+    // D z and B s are bit for bit the rows of the unsharded product (a shard's own mean row length may pick another width)
+    Dstack_.view.group = pick_group(Dstack);
   } else {
     Dstack_.upload(Dstack);
   }
@@ -531,6 +534,7 @@ Amg::Level& Amg::level(int l) {
   const bool try_elasm = use_elasm && ctx_.world == 1 && geo_.block > 1 && n_ % geo_.block == 0;
   lv.plan = build_level_plan(geo_, spec_, dstack_host_, l, P_, /*with_T=*/!try_elasm);
   lv.T_built = !try_elasm;
+  const int group_B = pick_group(lv.plan.B);      // of the whole B: see the constructor
   if (ctx_.world > 1) {
     std::vector<unsigned long long> mask = dof_rank_masks(lv.plan.B, ng_, P_.K, ctx_.world, geo_.block);
     lv.plan = shard_level_plan(lv.plan, ng_, S_, P_.K, P_.nY(), r0_, r0_ + n_);
@@ -548,6 +552,7 @@ Amg::Level& Amg::level(int l) {
   const double t_up = now_s();
   lv.R.upload(lv.plan.R);
   lv.B.upload(lv.plan.B);
+  lv.B.view.group = group_B;
   // bandwidth-bound meshes evaluate apply_D through the element-local view of B (LDS-staged column tiles, 9 bytes per
   // nonzero); launch-bound ones (the fused objective kernel's regime) never use it
   if (n_ > fused_trial_rows_ && geo_.block > 1 && n_ % geo_.block == 0) lv.Bel.build(lv.plan.B, geo_.block * P_.K);
@@ -1452,11 +1457,7 @@ void Amg::solve(const SolveOptions& opt, SolveStats& st) {
       a->timer_.enable(false);
     }
   } live_guard{this};
-  in_solve_ = true;
-  struct SolveFlag {
-    bool& f;
-    ~SolveFlag() { f = false; }
-  } solve_flag{in_solve_};
+  SolveFlag solve_flag(in_solve_);
   const double t_begin = now_s();
   const double lam_tol = std::sqrt(w_min_) / 2;
   double t = opt.t0, kappa = opt.kappa;
@@ -1579,6 +1580,59 @@ void Amg::f2(int l, const double* s_host, double t, double* avals_host) {
   ctx_.allreduce_sum(lv.avals.p, lv.plan.Apat.nnz());
   hip_check(hipStreamSynchronize(ctx_.stream), "sync f2");
   lv.avals.download(avals_host, lv.plan.Apat.nnz());
+}
+
+// ---- the owner-local pieces of a sharded Newton step, one call each (tests): see amg.hpp.  Nothing is restated here: each
+// entry point raises in_solve_ the way solve() does and calls the function solve() calls.
+Amg::Level& Amg::owner_local_level(int l, const char* who) {
+  if (ctx_.world <= 1) throw ArgError(std::string(who) + ": sharded contexts only");
+  Level& lv = level(l);
+  if (pcg_ || !values_stay_local(lv))
+    throw ArgError(std::string(who) + ": levels whose Hessian values stay on their rank only (device Cholesky, subtrees = row blocks)");
+  return lv;
+}
+
+void Amg::f1_owner(int l, const double* s_host, double t, double* g_host, double* gg, int* kind_host) {
+  Level& lv = owner_local_level(l, "f1_owner");
+  resync_signals();
+  SolveFlag flag(in_solve_);
+  lv.s_trial.upload(s_host, lv.plan.N);
+  dev_apply(lv, lv.s_trial.p, Dz_.p);
+  dev_f1(lv, Dz_.p, t, lv.g_trial.p);
+  lv.g_trial.download(g_host, lv.plan.N);
+  if (gg) *gg = h_scal_.p[2];
+  if (kind_host)
+    hip_check(hipMemcpy(kind_host, lv.gchol.unknown_kind(), (size_t)lv.plan.N * sizeof(int), hipMemcpyDeviceToHost), "D2H kind");
+}
+
+void Amg::f2_local(int l, const double* s_host, double t, double* avals_host) {
+  (void)t;
+  Level& lv = owner_local_level(l, "f2_local");
+  resync_signals();
+  SolveFlag flag(in_solve_);
+  SolveStats st;
+  lv.s_trial.upload(s_host, lv.plan.N);
+  dev_apply(lv, lv.s_trial.p, Dz_.p);
+  enqueue_f2_assemble(lv, Dz_.p, st);
+  hip_check(hipStreamSynchronize(ctx_.stream), "sync f2_local");
+  lv.avals.download(avals_host, lv.plan.Apat.nnz());
+}
+
+void Amg::solve_linear_local(int l, const double* avals, const double* g, double* x_host, double* inc, int* flag,
+                             double* vals_after) {
+  Level& lv = owner_local_level(l, "solve_linear_local");
+  resync_signals();
+  SolveFlag solve_flag(in_solve_);
+  SolveStats st;
+  lv.avals.upload(avals, lv.plan.Apat.nnz());
+  lv.g.upload(g, lv.plan.N);
+  double acc = 0;
+  // pre_assembled == dz: the values are the caller's, nothing is assembled; no trial points
+  const bool ok = dev_f2_solve(lv, Dz_.p, 0.0, st, &acc, nullptr, Dz_.p);
+  lv.nstep.download(x_host, lv.plan.N);
+  if (inc) *inc = acc;
+  if (flag) *flag = ok ? 0 : 1;
+  if (vals_after) lv.avals.download(vals_after, lv.plan.Apat.nnz());
 }
 
 // the speculated line search on the solve's own buffers (tests): see amg.hpp

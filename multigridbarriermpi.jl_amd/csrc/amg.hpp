@@ -368,6 +368,17 @@ class Amg {
   bool solve_host(int l, const double* avals, const double* g, double* nstep);
   // the same on the device (GpuChol): host arrays in/out, for parity tests of the device solver
   bool solve_device(int l, const double* avals, const double* g, double* nstep);
+  // One call each of the owner-local pieces of a sharded Newton step, through the functions solve() itself calls (tests).
+  // Sharded contexts whose factorisation of level l keeps its values local (chol_values_local) only.
+  //   f1_owner: dev_apply + dev_f1 as inside a solve.  g_host[N]: the raw device gradient, complete where kind >= 1; *gg: |g|^2
+  //     as the device summed it; kind_host[N]: 0 = another rank's unknown, 1 = own, 2 = top (separator)
+  //   f2_local: this rank's contributions to the Hessian values (barrier_f2 + assembly), before any reduction
+  //   solve_linear_local: dev_f2_solve on the given rank-local values and owner-local g, no trial points: x_host[N] (zero where
+  //     kind = 0), *inc = <g, x> and *flag (1: a pivot was not positive on some rank; never throws for that) as the step's one
+  //     collective left them, vals_after[nnz] = the values buffer behind the solve (top entries <- their sums over the ranks)
+  void f1_owner(int l, const double* s_host, double t, double* g_host, double* gg, int* kind_host);
+  void f2_local(int l, const double* s_host, double t, double* avals_host);
+  void solve_linear_local(int l, const double* avals, const double* g, double* x_host, double* inc, int* flag, double* vals_after);
 
   // full multigrid-barrier solve from the current z; z updated in place
   void solve(const SolveOptions& opt, SolveStats& st);
@@ -453,6 +464,12 @@ class Amg {
   // the step needs none, dots are summed over the owners.
   bool owner_local(Level& lv) { return in_solve_ && values_stay_local(lv); }
   bool in_solve_ = false;
+  struct SolveFlag {      // in_solve_ for the life of a solve (or of one owner-local entry point)
+    bool& f;
+    explicit SolveFlag(bool& flag) : f(flag) { f = true; }
+    ~SolveFlag() { f = false; }
+  };
+  Level& owner_local_level(int l, const char* who);      // refuses unsharded contexts and levels whose values are summed
   DevBuf<double> gtop_;
   struct EventHolder {      // owns the event the host waits on for |g|
     hipEvent_t e = nullptr;

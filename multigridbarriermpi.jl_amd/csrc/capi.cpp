@@ -977,6 +977,25 @@ int mgb_amg_solve_linear_gpu(mgb_amg a, int level, const double* lower_vals, con
     if (!a->amg->solve_device(level, lower_vals, g, x)) throw NumericError("MfChol: matrix is not positive definite");
   });
 }
+int mgb_amg_f1_owner(mgb_amg a, int level, const double* s, double t, double* g, double* gg, int32_t* kind) {
+  return guard([&] {
+    need(a && s && g && level >= 0 && level < a->amg->L(), "f1_owner: bad arguments");
+    a->amg->f1_owner(level, s, t, g, gg, kind);
+  });
+}
+int mgb_amg_f2_local(mgb_amg a, int level, const double* s, double t, double* lower_vals) {
+  return guard([&] {
+    need(a && s && lower_vals && level >= 0 && level < a->amg->L(), "f2_local: bad arguments");
+    a->amg->f2_local(level, s, t, lower_vals);
+  });
+}
+int mgb_amg_solve_linear_local(mgb_amg a, int level, const double* local_vals, const double* g, double* x, double* inc, int* flag,
+                               double* vals_after) {
+  return guard([&] {
+    need(a && local_vals && g && x && level >= 0 && level < a->amg->L(), "solve_linear_local: bad arguments");
+    a->amg->solve_linear_local(level, local_vals, g, x, inc, flag, vals_after);
+  });
+}
 int mgb_amg_set_solver(mgb_amg a, int solver) {
   return guard([&] {
     need(a && solver >= 0 && solver <= 2, "set_solver: 0 (device Cholesky), 1 (host Cholesky) or 2 (V-cycle-preconditioned CG)");

@@ -54,7 +54,10 @@ class GpuChol {
   // contributions to the matrix entries -- the caller does not sum the values over the ranks; the entries of the top
   // nodes ride in the Schur-complement collective and their sums are written back into d_vals.
   bool values_local() const { return vals_local_; }
-  double exchange_doubles() const { return (double)xchg_doubles_ + ntop_vals_ + n_ + 1; }
+  // doubles one Newton system exchanges inside factor_solve: the subtree roots' packed Schur complements, then either the matrix
+  // entries among top unknowns that ride behind them (values_local: the Newton loop solves with x_local, no collective for x) or
+  // x and the pivot flag (n + 1)
+  double exchange_doubles() const { return (double)xchg_doubles_ + (vals_local_ ? ntop_vals_ : n_ + 1); }
   // d_x = A^{-1} d_b: d_vals = device lower-triangle values in the pattern order given to MfChol::analyze,
   // d_b / d_x device vectors in the ORIGINAL ordering (may alias).
   // flag_armed: the caller guarantees the pivot flag is zero (it re-arms it itself behind the chain): no memset launch
