@@ -467,6 +467,78 @@ int mgb_geo_field_energy_host(mgb_geo g, int B, const double* const* z /* B arra
  * does not wait on the host (there is no slack column here: the u == s rule does not apply) */
 int mgb_geo_field_flux(mgb_locator loc, mgb_vec z, int S, int u, double p, mgb_vec p_nodal_or_null, mgb_vec flux);
 
+/* ---- level sets of nodal fields: where a solution takes a given value (contours, areas, fronts in time) ---------------- *
+ * Fields as for mgb_geo_field_energy: B >= 1 vectors of n x S row-major nodal values on the geometry of a locator, column u is
+ * contoured; single-GPU contexts, fp64.  Levels: nl >= 1 finite doubles.  Row r = b nl + l of every output belongs to field b
+ * and level c = levels[l].
+ * 2-D (block 7: v1 v2 v3 m12 m23 m31 centroid).  Every element is cut into simplices ("items"); the field is taken as LINEAR
+ * on an item, from its three lattice values.
+ *   Fan.  ring = [v1, m12, v2, m23, v3, m31], C the centroid: macro triangle k = 0..5 has corners A = ring[k],
+ *     B = ring[(k+1) % 6], C.
+ *   Refinement.  refine = r in {0,1,2,3}, N = 2^r.  Lattice points P(a,b) = A + (a/N)(B-A) + (b/N)(C-A), a, b >= 0, a + b <= N.
+ *     Small triangle j = 0..N^2-1: i the largest integer with i^2 <= j, q = j - i^2, b = N-1-i;
+ *       q even, a = q/2:      corners (P(a,b), P(a+1,b), P(a,b+1));
+ *       q odd,  a = (q-1)/2:  corners (P(a+1,b), P(a+1,b+1), P(a,b+1)).
+ *   Item index.  item = (e 6 + k) N^2 + j;  6 4^r nel items per field and level (at most INT_MAX).
+ *   Lattice values.  r = 0: the nodal values of A, B, C, loaded and never recomputed, at their coordinates, loaded as well.
+ *     r > 0: the P2 + bubble function of the element at the lattice point's reference coordinates, which come from the
+ *     reference coordinates of A, B, C by the formula of P; the sum runs over the seven nodes in ascending order.  Physical
+ *     positions come from the coordinates of A, B, C in x by the formula of P.
+ *   Classification.  A corner is ABOVE when v > c, by comparison only; k_above in {0,1,2,3}.
+ *   Non-finite values.  An item with a non-finite lattice value contributes NaN to all five columns of its row and emits
+ *     nothing; other rows stay bit for bit.  A NaN is never dropped.
+ *   Crossing point.  On an edge with one corner above and one not, ALWAYS from the below corner to the above corner:
+ *     t = (c - v_lo) / (v_hi - v_lo),  Q = P_lo + t (P_hi - P_lo).  Two elements that share an edge and hold the same nodal
+ *     values there compute the same bits at r = 0: the contour is watertight.
+ *   Segments.  k_above in {1,2}: one segment (Q0, Q1) between the crossings on the two edges at the lone corner, ordered so that
+ *     the above side lies to its LEFT in physical coordinates (swapped when cross(Q1-Q0, P_above - Q0) < 0, P_above the lone
+ *     corner for k_above = 1 and the corner after it for k_above = 2), whatever the sign of the element's determinant.  It is
+ *     not emitted, and not counted, exactly when k_above = 2 and the lone corner's value == c (the zero-length case).  An item
+ *     with k_above = 1 whose two other corners lie on the level emits that whole edge; an edge on the level may so be emitted
+ *     by each of its two triangles.
+ *   Per-item terms, A_it the item's area, a_s the area of the corner triangle (P_lone, Q0, Q1):
+ *     k_above = 3:  above A_it,        excess A_it ((v0+v1+v2)/3 - c);
+ *     k_above = 1:  above a_s,         excess a_s (v_lone - c)/3;
+ *     k_above = 2:  above A_it - a_s,  excess A_it ((v0+v1+v2)/3 - c) - a_s (v_lone - c)/3;      length |Q1 - Q0|.
+ * 1-D (block 2).  One item per element, refine must be 0; classification and the below-to-above rule as above.  A crossing is a
+ *   point x with a direction, +1 when u rises through c in +x.  Above length (1-t) h or h; excess (1-t) h (v_hi - c) / 2 or
+ *   h ((v_l+v_r)/2 - c).  A node on the level between an element that rises to it and one that is above beyond it is one
+ *   crossing of the one element only; between two elements that are above on both sides it is a crossing of each.
+ * 3-D: MGB_E_ARG (isosurfaces are not covered).
+ * Per (field, level) one row of MGB_LEVELSET_COLS doubles
+ *   [0] measure of {u > c}      [1] measure of {u = c}: length in 2-D, number of crossings in 1-D      [2] int_{u>c} (u - c)
+ *   [3] max (v - c) over all lattice values      [4] max (c - v)      -- NaN-sticky maxima; a level outside the range of the
+ *                                                                        field shows as a negative entry
+ * and one long long, the number of emitted segments (1-D: crossings).
+ * Launches: the measure on a grid (ceil(items / 256), nl, B) of 256 threads, one item per thread, one partial row and one
+ * count per workgroup; then one workgroup per row, which folds the row's partials in the order of the other field reductions
+ * (but from an identity whose two maxima are both -inf: either may be negative here) and turns the row's per-workgroup counts
+ * into exclusive offsets.  The rows and the counts reach the host in ONE copy and the call waits.  With
+ * segs non-null the total is allocated exactly and a third launch on the measure's grid recomputes every item and writes
+ * [x0, y0, x1, y1] (1-D: [x, direction]) and the int32 item to slot row_offset + workgroup offset + rank in the workgroup.
+ * No atomics: the output order is ascending item index within a row, rows in ascending order; a call repeated returns the same
+ * bits, and a row does not depend on B, nl or its place in the batch.  The per-item arithmetic is compiled with fp contraction
+ * off, in the kernels and in the host restatement.
+ * MGB_E_ARG, before anything is launched: a null argument or field; B < 1, nl < 1, B or nl > 65535 (device); S < 1; u outside
+ * [0, S); refine outside 0..3 (1-D: not 0); a non-finite level; vectors of the wrong length or of another context; a sharded
+ * context; more than INT_MAX items per row; a 3-D geometry. */
+#define MGB_LEVELSET_COLS 5
+typedef struct mgb_levelset_s* mgb_levelset;   /* the emitted segments of one call, device resident */
+int mgb_geo_level_sets(mgb_locator loc, int B, const mgb_vec* z /* B vectors of n x S */, int S, int u, int nl,
+                       const double* levels_host, int refine, double* out_host /* B nl x MGB_LEVELSET_COLS */,
+                       long long* counts_host /* B nl */, mgb_levelset* segs_or_null);
+/* copies to the host, each where non-null: row_offsets (B nl + 1, the total last), seg (total x 4, 1-D: total x 2), item (total) */
+int mgb_levelset_get(mgb_levelset segs, long long* row_offsets, double* seg, int32_t* item);
+int mgb_levelset_destroy(mgb_levelset segs);
+/* host restatement (no context, no GPU): the same per-item routine on host arrays, row after row, summed serially in ascending
+ * item order; the three sums are compensated (Neumaier), because the equal item areas of a refined mesh round a plain running
+ * sum the same way every time (1e-12 of the sum near 2e5 items).  row_offsets_or_null: B nl + 1; seg_or_null and item_or_null come together and hold `capacity` rows: MGB_E_ARG
+ * when more segments are emitted (call once without them, size them by the counts, call again). */
+int mgb_geo_level_sets_host(mgb_geo g, int B, const double* const* z /* B arrays of n x S */, int S, int u, int nl,
+                            const double* levels, int refine, double* out /* B nl x MGB_LEVELSET_COLS */,
+                            long long* counts /* B nl */, long long* row_offsets_or_null, double* seg_or_null,
+                            int32_t* item_or_null, long long capacity);
+
 /* ---- boundary facets of a geometry and boundary integrals of p-Laplace solutions --------------------------------------- *
  * The elements are broken and their quadrature is nodal: every node of a boundary facet is a row of x and z already, so the
  * boundary rule of a geometry is a list of nf facets of q nodes each: q global rows, q weights omega, the outward unit normal n,

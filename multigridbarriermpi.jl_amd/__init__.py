@@ -37,7 +37,7 @@ __all__ = [
     "backend_hip", "amgb_zeros", "amgb_all_isfinite", "amgb_diag", "amgb_blockdiag", "map_rows", "map_rows_gpu",
     "_raw_array", "_to_cpu_array", "MGBError", "device_count", "AMG", "amg", "hcat", "BarrierFn", "barrier_functions",
     "interpolate", "sample_grid", "norms", "error", "convergence", "FieldNorms", "Convergence",
-    "energy", "flux", "Energy",
+    "energy", "flux", "Energy", "level_sets", "LevelSets",
     "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
     "dirichlet_on", "neumann_load", "NeumannLoad",
     "interior", "InteriorFacets", "estimate", "ErrorIndicators", "mark", "refine_triangles", "adapt",
@@ -2118,6 +2118,130 @@ def flux(obj, p, u=0, z=None, k=-1) -> HPCMatrix:
     call("mgb_geo_field_flux", loc, zv.handle, S, u, p0, pv.handle if pv is not None else None, out._v.handle)
     out._inputs = (zv, pv)      # the launch is not waited for: what it reads lives as long as what it writes
     return out
+
+
+# --------------------------------------------------------------------------- level sets of solutions
+
+
+class LevelSets:
+    """Result of level_sets(): per field and level `above` = measure of {u > c}, `length` = measure of {u = c} (2-D: the length
+    of the contour; 1-D: the number of crossings), `excess` = int_{u > c} (u - c), `count` = the number of segments (1-D:
+    crossings), `reached` = the level lies strictly inside the range of the lattice values.  Floats for one field and a scalar
+    level; an axis of len(ts) in front for a ParabolicSOL (whose `ts` is carried), an axis of len(levels) behind for an array of
+    levels.  `rows` is the (B, nl, 5) table of the C ABI.  `segments(level, step)` gives the (m, 2, 2) contour segments
+    [[x0, y0], [x1, y1]] of levels[level] in snapshot `step`, the above side on their left, in ascending item order, and
+    `elements(level, step)` the element of each; in 1-D `points(level, step)` and `directions(level, step)` take their place."""
+
+    def __init__(self, levels, rows, counts, ts, squeeze, dim, refine, offsets=None, seg=None, item=None):
+        self.levels, self.rows, self.ts, self.dim, self.refine = levels, rows, ts, dim, refine
+        self._counts, self._offsets, self._seg, self._item = counts, offsets, seg, item
+
+        def shape(a):
+            a = a[:, 0] if squeeze[1] else a
+            a = a[0] if squeeze[0] else a
+            return a if np.ndim(a) else a.item()
+
+        self.above, self.length, self.excess = (shape(rows[:, :, k].copy()) for k in range(3))
+        self.count = shape(counts.copy())
+        self.reached = shape((rows[:, :, 3] > 0.0) & (rows[:, :, 4] > 0.0))
+
+    def _row(self, level, step, who):
+        B, nl = self._counts.shape
+        if self._offsets is None:
+            raise ValueError("LevelSets.%s: level_sets was called with segments=False" % who)
+        for v, m, name in ((level, nl, "level"), (step, B, "step")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -m <= v < m:
+                raise IndexError("LevelSets.%s: %s = %r is not one of %d" % (who, name, v, m))
+        r = (int(step) % B) * nl + int(level) % nl
+        return int(self._offsets[r]), int(self._offsets[r + 1])
+
+    def _need_dim(self, dim, who, other):
+        if self.dim != dim:
+            raise ValueError("LevelSets.%s: a %d-D result has %s" % (who, self.dim, other))
+
+    def segments(self, level=0, step=0) -> np.ndarray:
+        self._need_dim(2, "segments", "points() and directions()")
+        a, b = self._row(level, step, "segments")
+        return self._seg[a:b].reshape(-1, 2, 2).copy()
+
+    def elements(self, level=0, step=0) -> np.ndarray:
+        a, b = self._row(level, step, "elements")
+        return self._item[a:b] // (6 * 4 ** self.refine if self.dim == 2 else 1)
+
+    def points(self, level=0, step=0) -> np.ndarray:
+        self._need_dim(1, "points", "segments()")
+        a, b = self._row(level, step, "points")
+        return self._seg[a:b, 0].copy()
+
+    def directions(self, level=0, step=0) -> np.ndarray:
+        self._need_dim(1, "directions", "segments()")
+        a, b = self._row(level, step, "directions")
+        return self._seg[a:b, 1].astype(np.int64)
+
+    def __repr__(self):
+        return "LevelSets(levels=%r, above=%r, length=%r, count=%r)" % (self.levels, self.above, self.length, self.count)
+
+
+def level_sets(obj, levels, u=0, z=None, refine=0, segments=True) -> LevelSets:
+    """Where a solution takes given values: the contour {u = c} of the finite-element function, its length, the area of
+    {u > c} and int_{u > c} (u - c), measured on the device (csrc/levelset.hip; the rule is in include/mgb_hip.h and DESIGN.md
+    section 4n).  `obj`: an AMGBSOL, a device Geometry with `z=` an (n,) / (n, S) array or HPCMatrix, or a ParabolicSOL, all of
+    whose snapshots are measured by ONE set of launches.  `levels`: a finite scalar or a 1-D array of them; `u`: the column
+    (negative: from the end).  `refine` = 0..3 (2-D): every element is cut into 6 * 4^refine triangles on which u is taken as
+    linear; 0 uses the nodal values alone and gives a watertight contour, each further step divides the error of a smooth
+    contour by about 4.  `segments=False` leaves out the segments -- one launch and one copy less -- for front histories.
+    1-D geometries give crossing points; 3-D ones raise NotImplementedError (isosurfaces are not covered)."""
+    ts = None
+    if isinstance(obj, ParabolicSOL):
+        if z is not None:
+            raise ValueError("level_sets: z= does not go with a ParabolicSOL (its snapshots are the fields)")
+        geometry, fields, ts = obj.geometry, list(obj.u), np.asarray(obj.ts)
+        if len(fields) != len(ts) or not fields:
+            raise ValueError("level_sets: the ParabolicSOL has %d snapshots for %d times" % (len(fields), len(ts)))
+    elif isinstance(obj, (AMGBSOL, Geometry)):
+        geometry, z = _field_of(obj, "level_sets", z)
+        fields = [z]
+    else:
+        raise TypeError("level_sets: expected an AMGBSOL, a ParabolicSOL or a Geometry")
+    if geometry._geo is None:
+        raise TypeError("level_sets: geometry must come from native_to_mpi / fem*d_mpi")
+    if geometry.x.backend.world > 1:
+        raise NotImplementedError("level_sets: sharded contexts (world > 1) are not supported")
+    dim = geometry.discretization["dim"]
+    if dim == 3:
+        raise NotImplementedError("level_sets: isosurfaces of 3-D fields are not covered")
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= refine <= (3 if dim == 2 else 0):
+        raise ValueError("level_sets: refine must be %s, got %r" % ("0, 1, 2 or 3" if dim == 2 else "0 in 1-D", refine))
+    try:
+        lv = np.asarray(levels.to_numpy() if hasattr(levels, "to_numpy") else levels, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("level_sets: levels must be a scalar or a 1-D array of them")
+    scalar = lv.ndim == 0      # before f64(): ascontiguousarray gives a 0-d array one axis
+    lv = f64(lv.reshape(-1) if scalar else lv)
+    if lv.ndim != 1 or lv.size < 1:
+        raise ValueError("level_sets: levels must be a scalar or a non-empty 1-D array, got shape %r" % (tuple(lv.shape),))
+    if not np.all(np.isfinite(lv)):
+        raise ValueError("level_sets: every level must be finite")
+    loc, backend = _locator_of(geometry)
+    vecs = [_nodal_values(geometry, zk, backend, "level_sets") for zk in fields]
+    B, S, nl = len(vecs), vecs[0][1], lv.size
+    if any(Sk != S for _, Sk in vecs):
+        raise ValueError("level_sets: the snapshots have different numbers of columns")
+    u = _energy_column(u, S, "u", "level_sets")
+    table = (C.c_void_p * B)(*[v.handle.value for v, _ in vecs])
+    rows, counts = np.empty((B, nl, 5)), np.empty((B, nl), dtype=np.int64)
+    h = C.c_void_p()
+    call("mgb_geo_level_sets", loc, B, table, S, u, nl, dptr(lv), int(refine), dptr(rows),
+         counts.ctypes.data_as(_lib.c_ll_p), C.byref(h) if segments else None)
+    offsets = seg = item = None
+    if segments:
+        try:
+            total = int(counts.sum())
+            offsets, seg, item = np.empty(B * nl + 1, dtype=np.int64), np.empty((total, 4 if dim == 2 else 2)), np.empty(total, dtype=np.int32)
+            call("mgb_levelset_get", h, offsets.ctypes.data_as(_lib.c_ll_p), dptr(seg), iptr(item))
+        finally:
+            call("mgb_levelset_destroy", h)
+    return LevelSets(lv[0].item() if scalar else lv, rows, counts, ts, (ts is None, scalar), dim, int(refine), offsets, seg, item)
 
 
 # --------------------------------------------------------------------------- boundary facets and boundary integrals

@@ -4,6 +4,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <thread>
 
@@ -12,6 +13,7 @@
 #include "interp.hpp"
 #include "energy.hpp"
 #include "estimate.hpp"
+#include "levelset.hpp"
 #include "mixed.hpp"
 #include "norms.hpp"
 
@@ -53,6 +55,16 @@ struct mgb_locator_s {
   DevBuf<long long> norm_counts;
   DevBuf<double> energy_scratch;                   // mgb_geo_field_energy: partials and results, grown on demand
   DevBuf<const double*> energy_table;              // ... and the device table of field pointers, uploaded per call
+  DevBuf<double> ls_scratch, ls_levels;            // mgb_geo_level_sets: partials, results and totals; the levels of the call
+  DevBuf<long long> ls_counts, ls_row_base;        // ... per-workgroup counts and offsets; the first slot of every row
+  DevBuf<const double*> ls_table;                  // ... and the device table of field pointers, uploaded per call
+};
+struct mgb_levelset_s {
+  mgb_ctx_s* ctx;
+  int width;                                       // doubles per segment row: 4 in 2-D, 2 in 1-D
+  std::vector<long long> row_offsets;              // B nl + 1
+  DevBuf<double> seg;
+  DevBuf<int32_t> item;
 };
 struct mgb_boundary_s {
   mgb_locator_s* loc;      // not owned: the locator (x, w, context) must outlive the boundary
@@ -1452,6 +1464,105 @@ int mgb_geo_field_flux(mgb_locator loc, mgb_vec z, int S, int u, double p, mgb_v
     A.n = L.n, A.S = S, A.u = u, A.B = 1;
     energy::launch_field_flux(loc->ctx->ctx.stream, L.dim, L.k, A, z->buf.p, flux->buf.p);
     hip_check(hipGetLastError(), "geo_field_flux launch");
+  });
+}
+
+// ---- level sets of nodal fields (levelset.hpp / levelset.hip)
+namespace {
+void need_levels(const char* who, int B, int S, int u, int nl, const double* levels, int dim, int refine) {
+  const std::string w(who);
+  if (B < 1) throw std::invalid_argument(w + ": B must be >= 1");
+  if (nl < 1) throw std::invalid_argument(w + ": nl must be >= 1");
+  if (S < 1) throw std::invalid_argument(w + ": S must be >= 1");
+  if (u < 0 || u >= S) throw std::invalid_argument(w + ": column u outside [0, S)");
+  if (dim == 3) throw std::invalid_argument(w + ": isosurfaces of 3-D fields are not covered");
+  if (refine < 0 || refine > (dim == 2 ? levelset::kMaxRefine : 0))
+    throw std::invalid_argument(w + (dim == 2 ? ": refine must be 0, 1, 2 or 3" : ": refine must be 0 in 1-D"));
+  for (int l = 0; l < nl; ++l)
+    if (!interp::finite(levels[l])) throw std::invalid_argument(w + ": every level must be finite");
+}
+}  // namespace
+int mgb_geo_level_sets(mgb_locator loc, int B, const mgb_vec* z, int S, int u, int nl, const double* levels_host, int refine,
+                       double* out_host, long long* counts_host, mgb_levelset* segs) {
+  return guard([&] {
+    need(loc && z && levels_host && out_host && counts_host, "geo_level_sets: null argument");
+    const interp::Locator& L = loc->loc;
+    need(B <= 65535 && nl <= 65535, "geo_level_sets: at most 65535 fields and 65535 levels per call");      // before any is read
+    need_levels("geo_level_sets", B, S, u, nl, levels_host, L.dim, refine);
+    need(loc->ctx->ctx.world == 1, "geo_level_sets: sharded contexts are not supported");
+    std::vector<const double*> table;
+    field_table("geo_level_sets", loc, B, z, S, table);
+    levelset::Args A;
+    A.items = levelset::items_per_row(L.dim, L.nel, refine);
+    need(A.items <= INT_MAX, "geo_level_sets: more than INT_MAX items per row");
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const size_t rows = (size_t)B * nl, nwg = (size_t)reduce::workgroups(A.items);
+    const size_t nd = levelset::scratch_words(rows, nwg), nc = levelset::count_words(rows, nwg);
+    if (loc->ls_scratch.n < nd) loc->ls_scratch.alloc(nd);
+    if (loc->ls_counts.n < nc) loc->ls_counts.alloc(nc);
+    loc->ls_table.upload(table.data(), table.size());      // every earlier launch that read these has been waited for
+    loc->ls_levels.upload(levels_host, (size_t)nl);
+    A.x = loc->x.p;
+    A.z = loc->ls_table.p;
+    A.levels = loc->ls_levels.p;
+    A.nel = L.nel, A.S = S, A.u = u, A.B = B, A.nl = nl, A.refine = refine;
+    levelset::launch_measure(st, L.dim, A, loc->ls_scratch.p, loc->ls_counts.p);
+    hip_check(hipGetLastError(), "geo_level_sets launch");
+    hip_check(hipStreamSynchronize(st), "sync geo_level_sets");
+    // the rows and the totals lie behind each other: one copy
+    std::vector<double> both(rows * (reduce::kCols + 1));
+    hip_check(hipMemcpy(both.data(), loc->ls_scratch.p + levelset::results_offset(rows, nwg), both.size() * sizeof(double),
+                        hipMemcpyDeviceToHost), "D2H");
+    std::copy(both.begin(), both.begin() + rows * reduce::kCols, out_host);
+    std::memcpy(counts_host, both.data() + rows * reduce::kCols, rows * sizeof(long long));
+    if (!segs) return;
+    std::unique_ptr<mgb_levelset_s> out(new mgb_levelset_s{loc->ctx, levelset::seg_width(L.dim), {}, {}, {}});
+    out->row_offsets.resize(rows + 1);
+    out->row_offsets[0] = 0;
+    for (size_t r = 0; r < rows; ++r) out->row_offsets[r + 1] = out->row_offsets[r] + counts_host[r];
+    const long long total = out->row_offsets[rows];
+    if (total > 0) {
+      out->seg.alloc((size_t)total * out->width);
+      out->item.alloc((size_t)total);
+      loc->ls_row_base.upload(out->row_offsets.data(), rows);
+      levelset::launch_emit(st, L.dim, A, loc->ls_counts.p + levelset::offsets_offset(rows, nwg), loc->ls_row_base.p, total,
+                            out->seg.p, out->item.p);
+      hip_check(hipGetLastError(), "geo_level_sets emit launch");
+      hip_check(hipStreamSynchronize(st), "sync geo_level_sets emit");
+    }
+    *segs = out.release();
+  });
+}
+int mgb_levelset_get(mgb_levelset segs, long long* row_offsets, double* seg, int32_t* item) {
+  return guard([&] {
+    need(segs != nullptr, "levelset_get: null argument");
+    hip_check(hipSetDevice(segs->ctx->ctx.device), "hipSetDevice");
+    if (row_offsets) std::copy(segs->row_offsets.begin(), segs->row_offsets.end(), row_offsets);
+    if (seg) segs->seg.download(seg, segs->seg.n);
+    if (item) segs->item.download(item, segs->item.n);
+  });
+}
+int mgb_levelset_destroy(mgb_levelset segs) {
+  return guard([&] { delete segs; });
+}
+int mgb_geo_level_sets_host(mgb_geo g, int B, const double* const* z, int S, int u, int nl, const double* levels, int refine,
+                            double* out, long long* counts, long long* row_offsets, double* seg, int32_t* item, long long capacity) {
+  return guard([&] {
+    need(g && z && levels && out && counts, "geo_level_sets_host: null argument");
+    need_levels("geo_level_sets_host", B, S, u, nl, levels, g->g.dim, refine);
+    for (int b = 0; b < B; ++b) need(z[b] != nullptr, "geo_level_sets_host: null field");
+    need((seg == nullptr) == (item == nullptr), "geo_level_sets_host: seg and item come together");
+    need(!seg || capacity >= 0, "geo_level_sets_host: negative capacity");
+    const interp::Locator L = interp::build_locator(g->g);
+    levelset::Args A;
+    A.items = levelset::items_per_row(L.dim, L.nel, refine);
+    need(A.items <= INT_MAX, "geo_level_sets_host: more than INT_MAX items per row");
+    A.x = g->g.x.data();
+    A.z = z;
+    A.levels = levels;
+    A.nel = L.nel, A.S = S, A.u = u, A.B = B, A.nl = nl, A.refine = refine;
+    levelset::level_sets_host(L.dim, A, out, counts, row_offsets, seg, item, capacity);
   });
 }
 

@@ -100,21 +100,34 @@ __device__ inline void block_reduce(T* v, Op op, T (*red)[N]) {
   }
 }
 
-// stage 2 of one row, for the calling workgroup: partial g of the row is the kCols doubles at partials + g * stride
-__device__ inline void run_combine(const double* __restrict__ partials, size_t stride, int nwg, double* c) {
-  identity(c);
+// stage 2 of one row, for the calling workgroup: partial g of the row is the kCols doubles at partials + g * stride.  Id sets
+// the value the fold starts from: Identity for every module whose first maximum is non-negative, the module's own otherwise.
+struct Identity {
+  MGB_HD void operator()(double* c) const { identity(c); }
+};
+template <class Id>
+__device__ inline void run_combine(const double* __restrict__ partials, size_t stride, int nwg, double* c, Id id) {
+  id(c);
   const Run r = run_of(threadIdx.x, nwg);
   for (long long g = r.b0; g < r.b1; ++g) combine(c, partials + (size_t)g * stride);
 }
+__device__ inline void run_combine(const double* __restrict__ partials, size_t stride, int nwg, double* c) {
+  run_combine(partials, stride, nwg, c, Identity{});
+}
+template <class Id>
 __device__ inline void finish_row(const double* __restrict__ partials, size_t stride, int nwg, double (*red)[kCols],
-                                  double* __restrict__ out) {
+                                  double* __restrict__ out, Id id) {
   double c[kCols];
-  run_combine(partials, stride, nwg, c);
+  run_combine(partials, stride, nwg, c, id);
   block_reduce<kCols>(c, Combine{}, red);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < kCols; ++k) out[k] = c[k];
   }
+}
+__device__ inline void finish_row(const double* __restrict__ partials, size_t stride, int nwg, double (*red)[kCols],
+                                  double* __restrict__ out) {
+  finish_row(partials, stride, nwg, red, out, Identity{});
 }
 
 // reduce.hip: the finish launch on grid (rows); row r combines its nwg partials at partials + r * row_stride + g * wg_stride
