@@ -523,11 +523,13 @@ int mgb_geo_field_flux(mgb_locator loc, mgb_vec z, int S, int u, double p, mgb_v
  * [0, S); refine outside 0..3 (1-D: not 0); a non-finite level; vectors of the wrong length or of another context; a sharded
  * context; more than INT_MAX items per row; a 3-D geometry. */
 #define MGB_LEVELSET_COLS 5
-typedef struct mgb_levelset_s* mgb_levelset;   /* the emitted segments of one call, device resident */
+typedef struct mgb_levelset_s* mgb_levelset;   /* the emitted segments of one call, device resident; a handle made by
+                                                * mgb_geo_isosurfaces (below) holds triangles instead: rows of 9 doubles */
 int mgb_geo_level_sets(mgb_locator loc, int B, const mgb_vec* z /* B vectors of n x S */, int S, int u, int nl,
                        const double* levels_host, int refine, double* out_host /* B nl x MGB_LEVELSET_COLS */,
                        long long* counts_host /* B nl */, mgb_levelset* segs_or_null);
-/* copies to the host, each where non-null: row_offsets (B nl + 1, the total last), seg (total x 4, 1-D: total x 2), item (total) */
+/* copies to the host, each where non-null: row_offsets (B nl + 1, the total last), seg (total x 4, 1-D: total x 2; a handle of
+ * mgb_geo_isosurfaces: total x 9, x0 y0 z0 x1 y1 z1 x2 y2 z2), item (total) */
 int mgb_levelset_get(mgb_levelset segs, long long* row_offsets, double* seg, int32_t* item);
 int mgb_levelset_destroy(mgb_levelset segs);
 /* host restatement (no context, no GPU): the same per-item routine on host arrays, row after row, summed serially in ascending
@@ -538,6 +540,68 @@ int mgb_geo_level_sets_host(mgb_geo g, int B, const double* const* z /* B arrays
                             const double* levels, int refine, double* out /* B nl x MGB_LEVELSET_COLS */,
                             long long* counts /* B nl */, long long* row_offsets_or_null, double* seg_or_null,
                             int32_t* item_or_null, long long capacity);
+
+/* ---- isosurfaces of 3-D nodal fields ------------------------------------------------------------------------------------ *
+ * What level_sets is in 1-D and 2-D, for 3-D geometries: per field and level the volume of {u > c}, the area of {u = c},
+ * int_{u > c} (u - c), and the surface itself as oriented triangles.  mgb_geo_level_sets keeps refusing 3-D; this is its own
+ * entry point.  (csrc/isosurface.hpp is the rule, run by the gfx950 kernels and by the host restatement.)
+ *   Geometry.  block = (k+1)^3, k = 1..3: equispaced tensor nodes, x fastest, on the axis-aligned box spanned by the element's
+ *     first node A and last node B (what mgb_geo_interpolate assumes).  Any other block: MGB_E_ARG.
+ *   Lattice.  N = 2^refine, refine = 0..2, M = k N.  An element has M^3 cells of the lattice (a, b, c), 0 <= a, b, c <= M.
+ *     refine = 0: the lattice points are the nodes, (a, b, c) is local node a + (k+1)(b + (k+1) c); values and coordinates are
+ *     loaded and never recomputed.  refine > 0: the value is the tensor Lagrange function at (a, b, c) / M,
+ *     sum_c sum_b (sum_a l_a(a/M) z_abc) (l_b(b/M) l_c(c/M)), innermost sum first, each in ascending order, the one-dimensional
+ *     bases as in mgb_geo_interpolate; the position is A_d + (index_d / M)(B_d - A_d) per axis d.  Both depend on the lattice
+ *     index alone: two items of one element that share a lattice point hold the same bits there.
+ *   Items.  Every cell is cut into the six Kuhn tetrahedra around its diagonal O = (a, b, c) -> O + (1, 1, 1), one per permutation
+ *     (p0, p1, p2) of the axes, t = 0..5 in lexicographic order (abc, acb, bac, bca, cab, cba): corners 0..3 are
+ *     O, O + e_p0, O + e_p0 + e_p1, O + (1, 1, 1).  Every cell is cut the same way, so neighbouring cells and neighbouring
+ *     elements of the structured cube agree on every face diagonal.  item = (e M^3 + cell) 6 + t, cell = a + M (b + M c);
+ *     items per row = 6 M^3 nel <= INT_MAX.  The field is taken as linear on an item, from its four lattice values v0..v3.
+ *   Classification, non-finite values and the crossing point are those of the level sets above: a corner is ABOVE when v > c;
+ *     an item with a non-finite lattice value gives NaN in all five columns of its row and emits nothing; a crossing always
+ *     runs from the below corner to the above corner, t = (c - v_lo) / (v_hi - v_lo), Q = P_lo + t (P_hi - P_lo).
+ *   Pieces.  vol(p0, p1, p2, p3) = |(p1 - p0) . ((p2 - p0) x (p3 - p0))| / 6; V = vol of the item; a piece contributes its volume
+ *     to [0] and its volume x the mean of its four corner excesses v - c (0 at a crossing) to [2].
+ *     k_above = 4: the item, V and V ((v0 + v1 + v2 + v3) / 4 - c).      k_above = 0: nothing.
+ *     k_above = 1 or 3: L = the lone corner (the one above, or the one not above), o1 < o2 < o3 the others, Q_i the crossing on
+ *       the edge between L and o_i; the corner piece (P_L, Q1, Q2, Q3) has V_s = vol and X_s = V_s ((v_L - c) / 4).
+ *       k_above = 1: V_s and X_s;      k_above = 3: V - V_s and V ((v0 + v1 + v2 + v3) / 4 - c) - X_s.      Triangle (Q1, Q2, Q3).
+ *     k_above = 2: A0 < A1 the corners above, B0 < B1 the others, Q_ij the crossing from B_j to A_i.  The wedge
+ *       (A0, Q00, Q01) - (A1, Q10, Q11) is the three tetrahedra w1 = (A0, Q00, Q01, A1), w2 = (Q00, Q01, A1, Q10),
+ *       w3 = (Q01, A1, Q10, Q11): [0] = w1 + w2 + w3, [2] = w1 ((e0 + e1) / 4) + w2 (e1 / 4) + w3 (e1 / 4), e_i = v_Ai - c.
+ *       The quadrilateral Q00 Q01 Q11 Q10 is split along its diagonal Q01 - Q10: triangles (Q00, Q01, Q10), then (Q01, Q11, Q10).
+ *   Triangles.  A triangle two of whose vertices are the same point (all three coordinates compare equal: a corner exactly on
+ *     the level) is neither emitted nor counted and adds no area.  Every other triangle (q0, q1, q2) adds |n| / 2,
+ *     n = (q1 - q0) x (q2 - q0), to [1] and is emitted as (P0, P1, P2) = (q0, q1, q2) or (q0, q2, q1), so that
+ *     (P1 - P0) x (P2 - P0) points to the BELOW side, the outward normal of {u > c}, in physical coordinates whatever the
+ *     orientation of the tetrahedron or the box: q1 and q2 are exchanged when n . (R - q0) > 0 for R = P_L (k_above = 1) or
+ *     R = P_A0 (k_above = 2), and when n . (P_L - q0) < 0 for k_above = 3.  A face of an item that lies on the level is emitted
+ *     by every tetrahedron whose fourth corner is above, so possibly twice.  An item emits 0, 1 or 2 triangles; its two
+ *     triangles are adjacent in the output, in the order above.  At refine = 0 on a mesh whose elements hold the same nodal
+ *     values at shared nodes the surface is watertight: every edge not on the boundary occurs twice, in opposite directions.
+ * Per (field, level) one row of MGB_LEVELSET_COLS doubles
+ *   [0] volume of {u > c}      [1] area of {u = c}      [2] int_{u>c} (u - c)      [3] max (v - c)      [4] max (c - v)
+ * over all lattice values, NaN-sticky, both maxima started from -inf, and one long long, the number of emitted triangles.
+ * Launches, as for the level sets: the measure on a grid (ceil(items / 256), nl, B) of 256 threads, one item per thread, one
+ * partial row and one count (0..2 per thread) per workgroup; the SAME finish launch; rows and counts in ONE copy.  With
+ * tris non-null a third launch on the measure's grid recomputes every item, ranks it by the exclusive prefix sum of the counts
+ * in its workgroup and writes its first triangle [x0 y0 z0 x1 y1 z1 x2 y2 z2] and the int32 item to slot row offset + workgroup
+ * offset + rank, its second one to the next slot.  No atomics: ascending item order within a row, rows in ascending order; a
+ * call repeated returns the same bits, a row does not depend on B, nl or its place in the batch.  The per-item arithmetic is
+ * compiled with fp contraction off on both sides.  The triangles come back through mgb_levelset_get / mgb_levelset_destroy.
+ * MGB_E_ARG, before anything is launched: a null argument or field; B < 1, nl < 1, B or nl > 65535 (device); S < 1; u outside
+ * [0, S); refine outside 0..2; a non-finite level; vectors of the wrong length or of another context; a sharded context; more
+ * than INT_MAX items per row; a 1-D or 2-D geometry (the message names level_sets). */
+int mgb_geo_isosurfaces(mgb_locator loc, int B, const mgb_vec* z /* B vectors of n x S */, int S, int u, int nl,
+                        const double* levels_host, int refine, double* out_host /* B nl x MGB_LEVELSET_COLS */,
+                        long long* counts_host /* B nl */, mgb_levelset* tris_or_null);
+/* host restatement (no context, no GPU), shaped like mgb_geo_level_sets_host: serial, ascending item order, the three sums
+ * compensated (Neumaier); tri_or_null (capacity x 9) and item_or_null come together, MGB_E_ARG when more triangles are emitted. */
+int mgb_geo_isosurfaces_host(mgb_geo g, int B, const double* const* z /* B arrays of n x S */, int S, int u, int nl,
+                             const double* levels, int refine, double* out /* B nl x MGB_LEVELSET_COLS */,
+                             long long* counts /* B nl */, long long* row_offsets_or_null, double* tri_or_null,
+                             int32_t* item_or_null, long long capacity);
 
 /* ---- boundary facets of a geometry and boundary integrals of p-Laplace solutions --------------------------------------- *
  * The elements are broken and their quadrature is nodal: every node of a boundary facet is a row of x and z already, so the

@@ -37,7 +37,7 @@ __all__ = [
     "backend_hip", "amgb_zeros", "amgb_all_isfinite", "amgb_diag", "amgb_blockdiag", "map_rows", "map_rows_gpu",
     "_raw_array", "_to_cpu_array", "MGBError", "device_count", "AMG", "amg", "hcat", "BarrierFn", "barrier_functions",
     "interpolate", "sample_grid", "norms", "error", "convergence", "FieldNorms", "Convergence",
-    "energy", "flux", "Energy", "level_sets", "LevelSets",
+    "energy", "flux", "Energy", "level_sets", "LevelSets", "isosurfaces", "Isosurfaces",
     "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
     "dirichlet_on", "neumann_load", "NeumannLoad",
     "interior", "InteriorFacets", "estimate", "ErrorIndicators", "mark", "refine_triangles", "adapt",
@@ -2182,6 +2182,43 @@ class LevelSets:
         return "LevelSets(levels=%r, above=%r, length=%r, count=%r)" % (self.levels, self.above, self.length, self.count)
 
 
+def _level_fields(who, obj, z):
+    """(geometry, fields, ts) of level_sets() and isosurfaces(): the snapshots of a ParabolicSOL with its times, or the one
+    field of an AMGBSOL or of a Geometry with z=; on one rank."""
+    ts = None
+    if isinstance(obj, ParabolicSOL):
+        if z is not None:
+            raise ValueError("%s: z= does not go with a ParabolicSOL (its snapshots are the fields)" % who)
+        geometry, fields, ts = obj.geometry, list(obj.u), np.asarray(obj.ts)
+        if len(fields) != len(ts) or not fields:
+            raise ValueError("%s: the ParabolicSOL has %d snapshots for %d times" % (who, len(fields), len(ts)))
+    elif isinstance(obj, (AMGBSOL, Geometry)):
+        geometry, z = _field_of(obj, who, z)
+        fields = [z]
+    else:
+        raise TypeError("%s: expected an AMGBSOL, a ParabolicSOL or a Geometry" % who)
+    if geometry._geo is None:
+        raise TypeError("%s: geometry must come from native_to_mpi / fem*d_mpi" % who)
+    if geometry.x.backend.world > 1:
+        raise NotImplementedError("%s: sharded contexts (world > 1) are not supported" % who)
+    return geometry, fields, ts
+
+
+def _level_values(who, levels):
+    """(levels as a contiguous 1-D float64 array, whether a scalar was given)"""
+    try:
+        lv = np.asarray(levels.to_numpy() if hasattr(levels, "to_numpy") else levels, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("%s: levels must be a scalar or a 1-D array of them" % who)
+    scalar = lv.ndim == 0      # before f64(): ascontiguousarray gives a 0-d array one axis
+    lv = f64(lv.reshape(-1) if scalar else lv)
+    if lv.ndim != 1 or lv.size < 1:
+        raise ValueError("%s: levels must be a scalar or a non-empty 1-D array, got shape %r" % (who, tuple(lv.shape)))
+    if not np.all(np.isfinite(lv)):
+        raise ValueError("%s: every level must be finite" % who)
+    return lv, scalar
+
+
 def level_sets(obj, levels, u=0, z=None, refine=0, segments=True) -> LevelSets:
     """Where a solution takes given values: the contour {u = c} of the finite-element function, its length, the area of
     {u > c} and int_{u > c} (u - c), measured on the device (csrc/levelset.hip; the rule is in include/mgb_hip.h and DESIGN.md
@@ -2190,38 +2227,14 @@ def level_sets(obj, levels, u=0, z=None, refine=0, segments=True) -> LevelSets:
     (negative: from the end).  `refine` = 0..3 (2-D): every element is cut into 6 * 4^refine triangles on which u is taken as
     linear; 0 uses the nodal values alone and gives a watertight contour, each further step divides the error of a smooth
     contour by about 4.  `segments=False` leaves out the segments -- one launch and one copy less -- for front histories.
-    1-D geometries give crossing points; 3-D ones raise NotImplementedError (isosurfaces are not covered)."""
-    ts = None
-    if isinstance(obj, ParabolicSOL):
-        if z is not None:
-            raise ValueError("level_sets: z= does not go with a ParabolicSOL (its snapshots are the fields)")
-        geometry, fields, ts = obj.geometry, list(obj.u), np.asarray(obj.ts)
-        if len(fields) != len(ts) or not fields:
-            raise ValueError("level_sets: the ParabolicSOL has %d snapshots for %d times" % (len(fields), len(ts)))
-    elif isinstance(obj, (AMGBSOL, Geometry)):
-        geometry, z = _field_of(obj, "level_sets", z)
-        fields = [z]
-    else:
-        raise TypeError("level_sets: expected an AMGBSOL, a ParabolicSOL or a Geometry")
-    if geometry._geo is None:
-        raise TypeError("level_sets: geometry must come from native_to_mpi / fem*d_mpi")
-    if geometry.x.backend.world > 1:
-        raise NotImplementedError("level_sets: sharded contexts (world > 1) are not supported")
+    1-D geometries give crossing points; 3-D ones raise NotImplementedError here: isosurfaces() is their entry point."""
+    geometry, fields, ts = _level_fields("level_sets", obj, z)
     dim = geometry.discretization["dim"]
     if dim == 3:
         raise NotImplementedError("level_sets: isosurfaces of 3-D fields are not covered")
     if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= refine <= (3 if dim == 2 else 0):
         raise ValueError("level_sets: refine must be %s, got %r" % ("0, 1, 2 or 3" if dim == 2 else "0 in 1-D", refine))
-    try:
-        lv = np.asarray(levels.to_numpy() if hasattr(levels, "to_numpy") else levels, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise TypeError("level_sets: levels must be a scalar or a 1-D array of them")
-    scalar = lv.ndim == 0      # before f64(): ascontiguousarray gives a 0-d array one axis
-    lv = f64(lv.reshape(-1) if scalar else lv)
-    if lv.ndim != 1 or lv.size < 1:
-        raise ValueError("level_sets: levels must be a scalar or a non-empty 1-D array, got shape %r" % (tuple(lv.shape),))
-    if not np.all(np.isfinite(lv)):
-        raise ValueError("level_sets: every level must be finite")
+    lv, scalar = _level_values("level_sets", levels)
     loc, backend = _locator_of(geometry)
     vecs = [_nodal_values(geometry, zk, backend, "level_sets") for zk in fields]
     B, S, nl = len(vecs), vecs[0][1], lv.size
@@ -2242,6 +2255,95 @@ def level_sets(obj, levels, u=0, z=None, refine=0, segments=True) -> LevelSets:
         finally:
             call("mgb_levelset_destroy", h)
     return LevelSets(lv[0].item() if scalar else lv, rows, counts, ts, (ts is None, scalar), dim, int(refine), offsets, seg, item)
+
+
+# --------------------------------------------------------------------------- isosurfaces of 3-D solutions
+
+
+class Isosurfaces:
+    """Result of isosurfaces(): per field and level `above` = volume of {u > c}, `area` = area of {u = c}, `excess` =
+    int_{u > c} (u - c), `count` = the number of triangles, `reached` = the level lies strictly inside the range of the lattice
+    values.  Shapes as in LevelSets: floats for one field and a scalar level, an axis of len(ts) in front for a ParabolicSOL
+    (whose `ts` is carried), an axis of len(levels) behind for an array of levels.  `rows` is the (B, nl, 5) table of the C ABI.
+    `triangles(level, field)` gives the (m, 3, 3) vertices [P0, P1, P2] of the triangles of levels[level] in snapshot `field`,
+    (P1 - P0) x (P2 - P0) pointing to the below side, in ascending item order; `items(level, field)` the item of each (an item
+    with two triangles occurs twice) and `elements(level, field)` its element."""
+
+    def __init__(self, levels, rows, counts, ts, squeeze, k, refine, offsets=None, tri=None, item=None):
+        self.levels, self.rows, self.ts, self.k, self.refine = levels, rows, ts, k, refine
+        self._counts, self._offsets, self._tri, self._item = counts, offsets, tri, item
+
+        def shape(a):
+            a = a[:, 0] if squeeze[1] else a
+            a = a[0] if squeeze[0] else a
+            return a if np.ndim(a) else a.item()
+
+        self.above, self.area, self.excess = (shape(rows[:, :, j].copy()) for j in range(3))
+        self.count = shape(counts.copy())
+        self.reached = shape((rows[:, :, 3] > 0.0) & (rows[:, :, 4] > 0.0))
+
+    def _row(self, level, field, who):
+        B, nl = self._counts.shape
+        if self._offsets is None:
+            raise ValueError("Isosurfaces.%s: isosurfaces was called with triangles=False" % who)
+        for v, m, name in ((level, nl, "level"), (field, B, "field")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -m <= v < m:
+                raise IndexError("Isosurfaces.%s: %s = %r is not one of %d" % (who, name, v, m))
+        r = (int(field) % B) * nl + int(level) % nl
+        return int(self._offsets[r]), int(self._offsets[r + 1])
+
+    def triangles(self, level=0, field=0) -> np.ndarray:
+        a, b = self._row(level, field, "triangles")
+        return self._tri[a:b].reshape(-1, 3, 3).copy()
+
+    def items(self, level=0, field=0) -> np.ndarray:
+        a, b = self._row(level, field, "items")
+        return self._item[a:b].copy()
+
+    def elements(self, level=0, field=0) -> np.ndarray:
+        a, b = self._row(level, field, "elements")
+        return self._item[a:b] // (6 * (self.k * 2 ** self.refine) ** 3)
+
+    def __repr__(self):
+        return "Isosurfaces(levels=%r, above=%r, area=%r, count=%r)" % (self.levels, self.above, self.area, self.count)
+
+
+def isosurfaces(obj, levels, u=0, z=None, refine=0, triangles=True) -> Isosurfaces:
+    """Where a 3-D solution takes given values: the surface {u = c} of the finite-element function as oriented triangles, its
+    area, the volume of {u > c} and int_{u > c} (u - c), measured on the device (csrc/isosurface.hip; the rule is in
+    include/mgb_hip.h and DESIGN.md section 4o).  `obj`, `levels`, `u` and `z` as in level_sets(); all snapshots of a
+    ParabolicSOL are measured by ONE set of launches.  `refine` = 0, 1 or 2: every element of degree k is cut into
+    6 (k 2^refine)^3 tetrahedra on which u is taken as linear; 0 uses the nodal values alone and gives a watertight surface,
+    each further step divides the error of a smooth surface by about 4.  `triangles=False` leaves out the triangles -- one
+    launch and one copy less -- for front histories.  1-D and 2-D geometries raise ValueError: level_sets() covers them."""
+    geometry, fields, ts = _level_fields("isosurfaces", obj, z)
+    dim = geometry.discretization["dim"]
+    if dim != 3:
+        raise ValueError("isosurfaces: a 3-D geometry is needed, got %d-D; level_sets() covers 1-D and 2-D" % dim)
+    if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)) or not 0 <= refine <= 2:
+        raise ValueError("isosurfaces: refine must be 0, 1 or 2, got %r" % (refine,))
+    lv, scalar = _level_values("isosurfaces", levels)
+    loc, backend = _locator_of(geometry)
+    vecs = [_nodal_values(geometry, zk, backend, "isosurfaces") for zk in fields]
+    B, S, nl = len(vecs), vecs[0][1], lv.size
+    if any(Sk != S for _, Sk in vecs):
+        raise ValueError("isosurfaces: the snapshots have different numbers of columns")
+    u = _energy_column(u, S, "u", "isosurfaces")
+    table = (C.c_void_p * B)(*[v.handle.value for v, _ in vecs])
+    rows, counts = np.empty((B, nl, 5)), np.empty((B, nl), dtype=np.int64)
+    h = C.c_void_p()
+    call("mgb_geo_isosurfaces", loc, B, table, S, u, nl, dptr(lv), int(refine), dptr(rows),
+         counts.ctypes.data_as(_lib.c_ll_p), C.byref(h) if triangles else None)
+    offsets = tri = item = None
+    if triangles:
+        try:
+            total = int(counts.sum())
+            offsets, tri, item = np.empty(B * nl + 1, dtype=np.int64), np.empty((total, 9)), np.empty(total, dtype=np.int32)
+            call("mgb_levelset_get", h, offsets.ctypes.data_as(_lib.c_ll_p), dptr(tri), iptr(item))
+        finally:
+            call("mgb_levelset_destroy", h)
+    k = round(geometry.discretization["block"] ** (1.0 / 3.0)) - 1
+    return Isosurfaces(lv[0].item() if scalar else lv, rows, counts, ts, (ts is None, scalar), k, int(refine), offsets, tri, item)
 
 
 # --------------------------------------------------------------------------- boundary facets and boundary integrals

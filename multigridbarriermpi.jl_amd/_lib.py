@@ -151,6 +151,9 @@ PROTOTYPES = {
     "mgb_levelset_destroy": [H],
     "mgb_geo_level_sets_host": [H, C.c_int, C.POINTER(c_dbl_p), C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_int, c_dbl_p, c_ll_p, c_ll_p,
                                 c_dbl_p, c_i32_p, C.c_longlong],
+    "mgb_geo_isosurfaces": [H, C.c_int, C.POINTER(H), C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_int, c_dbl_p, c_ll_p, C.POINTER(H)],
+    "mgb_geo_isosurfaces_host": [H, C.c_int, C.POINTER(c_dbl_p), C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_int, c_dbl_p, c_ll_p, c_ll_p,
+                                 c_dbl_p, c_i32_p, C.c_longlong],
     "mgb_boundary_create": [H, H, C.POINTER(H)],
     "mgb_boundary_destroy": [H],
     "mgb_boundary_dims": [H, c_int_p, c_int_p, c_int_p],

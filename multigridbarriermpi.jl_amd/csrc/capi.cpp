@@ -11,6 +11,7 @@
 #include "amg.hpp"
 #include "boundary.hpp"
 #include "interp.hpp"
+#include "isosurface.hpp"
 #include "energy.hpp"
 #include "estimate.hpp"
 #include "levelset.hpp"
@@ -61,7 +62,7 @@ struct mgb_locator_s {
 };
 struct mgb_levelset_s {
   mgb_ctx_s* ctx;
-  int width;                                       // doubles per segment row: 4 in 2-D, 2 in 1-D
+  int width;                                       // doubles per row: segments 4 in 2-D and 2 in 1-D, triangles (mgb_geo_isosurfaces) 9
   std::vector<long long> row_offsets;              // B nl + 1
   DevBuf<double> seg;
   DevBuf<int32_t> item;
@@ -1563,6 +1564,92 @@ int mgb_geo_level_sets_host(mgb_geo g, int B, const double* const* z, int S, int
     A.levels = levels;
     A.nel = L.nel, A.S = S, A.u = u, A.B = B, A.nl = nl, A.refine = refine;
     levelset::level_sets_host(L.dim, A, out, counts, row_offsets, seg, item, capacity);
+  });
+}
+
+// ---- isosurfaces of 3-D nodal fields (isosurface.hpp / isosurface.hip); the buffers and the handle are the level sets'
+namespace {
+void need_isosurfaces(const char* who, int B, int S, int u, int nl, const double* levels, int dim, int refine) {
+  const std::string w(who);
+  if (B < 1) throw std::invalid_argument(w + ": B must be >= 1");
+  if (nl < 1) throw std::invalid_argument(w + ": nl must be >= 1");
+  if (S < 1) throw std::invalid_argument(w + ": S must be >= 1");
+  if (u < 0 || u >= S) throw std::invalid_argument(w + ": column u outside [0, S)");
+  if (dim != 3) throw std::invalid_argument(w + ": a 3-D geometry is needed; 1-D and 2-D fields go to level_sets");
+  if (refine < 0 || refine > isosurface::kMaxRefine) throw std::invalid_argument(w + ": refine must be 0, 1 or 2");
+  for (int l = 0; l < nl; ++l)
+    if (!interp::finite(levels[l])) throw std::invalid_argument(w + ": every level must be finite");
+}
+}  // namespace
+int mgb_geo_isosurfaces(mgb_locator loc, int B, const mgb_vec* z, int S, int u, int nl, const double* levels_host, int refine,
+                        double* out_host, long long* counts_host, mgb_levelset* tris) {
+  return guard([&] {
+    need(loc && z && levels_host && out_host && counts_host, "geo_isosurfaces: null argument");
+    const interp::Locator& L = loc->loc;
+    need(B <= 65535 && nl <= 65535, "geo_isosurfaces: at most 65535 fields and 65535 levels per call");      // before any is read
+    need_isosurfaces("geo_isosurfaces", B, S, u, nl, levels_host, L.dim, refine);
+    need(loc->ctx->ctx.world == 1, "geo_isosurfaces: sharded contexts are not supported");
+    std::vector<const double*> table;
+    field_table("geo_isosurfaces", loc, B, z, S, table);
+    levelset::Args A;
+    A.items = isosurface::items_per_row(L.k, L.nel, refine);
+    need(A.items <= INT_MAX, "geo_isosurfaces: more than INT_MAX items per row");
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const size_t rows = (size_t)B * nl, nwg = (size_t)reduce::workgroups(A.items);
+    const size_t nd = levelset::scratch_words(rows, nwg), nc = levelset::count_words(rows, nwg);
+    if (loc->ls_scratch.n < nd) loc->ls_scratch.alloc(nd);
+    if (loc->ls_counts.n < nc) loc->ls_counts.alloc(nc);
+    loc->ls_table.upload(table.data(), table.size());      // every earlier launch that read these has been waited for
+    loc->ls_levels.upload(levels_host, (size_t)nl);
+    A.x = loc->x.p;
+    A.z = loc->ls_table.p;
+    A.levels = loc->ls_levels.p;
+    A.nel = L.nel, A.S = S, A.u = u, A.B = B, A.nl = nl, A.refine = refine;
+    isosurface::launch_measure(st, L.k, A, loc->ls_scratch.p, loc->ls_counts.p);
+    hip_check(hipGetLastError(), "geo_isosurfaces launch");
+    hip_check(hipStreamSynchronize(st), "sync geo_isosurfaces");
+    // the rows and the totals lie behind each other: one copy
+    std::vector<double> both(rows * (reduce::kCols + 1));
+    hip_check(hipMemcpy(both.data(), loc->ls_scratch.p + levelset::results_offset(rows, nwg), both.size() * sizeof(double),
+                        hipMemcpyDeviceToHost), "D2H");
+    std::copy(both.begin(), both.begin() + rows * reduce::kCols, out_host);
+    std::memcpy(counts_host, both.data() + rows * reduce::kCols, rows * sizeof(long long));
+    if (!tris) return;
+    std::unique_ptr<mgb_levelset_s> out(new mgb_levelset_s{loc->ctx, isosurface::kTriWidth, {}, {}, {}});
+    out->row_offsets.resize(rows + 1);
+    out->row_offsets[0] = 0;
+    for (size_t r = 0; r < rows; ++r) out->row_offsets[r + 1] = out->row_offsets[r] + counts_host[r];
+    const long long total = out->row_offsets[rows];
+    if (total > 0) {
+      out->seg.alloc((size_t)total * out->width);
+      out->item.alloc((size_t)total);
+      loc->ls_row_base.upload(out->row_offsets.data(), rows);
+      isosurface::launch_emit(st, L.k, A, loc->ls_counts.p + levelset::offsets_offset(rows, nwg), loc->ls_row_base.p, total,
+                              out->seg.p, out->item.p);
+      hip_check(hipGetLastError(), "geo_isosurfaces emit launch");
+      hip_check(hipStreamSynchronize(st), "sync geo_isosurfaces emit");
+    }
+    *tris = out.release();
+  });
+}
+int mgb_geo_isosurfaces_host(mgb_geo g, int B, const double* const* z, int S, int u, int nl, const double* levels, int refine,
+                             double* out, long long* counts, long long* row_offsets, double* tri, int32_t* item, long long capacity) {
+  return guard([&] {
+    need(g && z && levels && out && counts, "geo_isosurfaces_host: null argument");
+    need_isosurfaces("geo_isosurfaces_host", B, S, u, nl, levels, g->g.dim, refine);
+    for (int b = 0; b < B; ++b) need(z[b] != nullptr, "geo_isosurfaces_host: null field");
+    need((tri == nullptr) == (item == nullptr), "geo_isosurfaces_host: tri and item come together");
+    need(!tri || capacity >= 0, "geo_isosurfaces_host: negative capacity");
+    const interp::Locator L = interp::build_locator(g->g);      // validates the blocks: tensor nodes of the corner box
+    levelset::Args A;
+    A.items = isosurface::items_per_row(L.k, L.nel, refine);
+    need(A.items <= INT_MAX, "geo_isosurfaces_host: more than INT_MAX items per row");
+    A.x = g->g.x.data();
+    A.z = z;
+    A.levels = levels;
+    A.nel = L.nel, A.S = S, A.u = u, A.B = B, A.nl = nl, A.refine = refine;
+    isosurface::isosurfaces_host(L.k, A, out, counts, row_offsets, tri, item, capacity);
   });
 }
 

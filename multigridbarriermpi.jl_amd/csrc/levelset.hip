@@ -2,8 +2,8 @@
 // of plain launches on one stream:
 //   measure_kernel<DIM>: grid (workgroups(items), nl, B); one thread per item runs levelset.hpp's item(); the workgroup reduces
 //     the five contributions and the number of emitted segments and writes ONE partial row and ONE count per (row, workgroup);
-//   finish_kernel: grid (B nl); the workgroup of a row folds that row's partials into its 5 doubles with reduce.hpp's
-//     finish_row, started from the identity of these rows (both maxima may be negative), and turns the row's nwg counts
+//   finish_kernel (behind launch_finish, which isosurface.hip calls too): grid (B nl); the workgroup of a row folds that
+//     row's partials into its 5 doubles with reduce.hpp's finish_row, started from the identity of these rows (both maxima may be negative), and turns the row's nwg counts
 //     into nwg + 1 exclusive offsets, the total last.
 // Where segments are asked for, after the totals have reached the host:
 //   emit_kernel<DIM>: the measure's grid; every thread recomputes its item, ranks itself among the emitting threads of its
@@ -122,8 +122,13 @@ void launch_measure(hipStream_t stream, int dim, const Args& A, double* scratch,
   if (dim == 2) hipLaunchKernelGGL(measure_kernel<2>, grid, dim3(kThreads), 0, stream, A, scratch, counts);
   else hipLaunchKernelGGL(measure_kernel<1>, grid, dim3(kThreads), 0, stream, A, scratch, counts);
   double* results = scratch + results_offset(rows, (size_t)nwg);
-  hipLaunchKernelGGL(finish_kernel, dim3((unsigned)rows), dim3(kThreads), 0, stream, scratch, counts, (int)nwg, results,
-                     counts + offsets_offset(rows, (size_t)nwg), reinterpret_cast<long long*>(results + rows * kCols));
+  launch_finish(stream, (int)rows, scratch, counts, (int)nwg, results, counts + offsets_offset(rows, (size_t)nwg),
+                reinterpret_cast<long long*>(results + rows * kCols));
+}
+
+void launch_finish(hipStream_t stream, int rows, const double* partials, const long long* counts, int nwg, double* results,
+                   long long* offsets, long long* totals) {
+  hipLaunchKernelGGL(finish_kernel, dim3((unsigned)rows), dim3(kThreads), 0, stream, partials, counts, nwg, results, offsets, totals);
 }
 
 void launch_emit(hipStream_t stream, int dim, const Args& A, const long long* offsets, const long long* row_base, long long total,
@@ -135,18 +140,6 @@ void launch_emit(hipStream_t stream, int dim, const Args& A, const long long* of
 }
 
 namespace {
-// A serial sum whose error does not grow with the number of terms (Neumaier): the items of a refined mesh have equal areas,
-// so the roundings of a plain running sum all point the same way and reach 1e-12 of the sum near 2e5 items.
-struct SerialSum {
-  double s = 0.0, c = 0.0;
-  void add(double v) {
-    const double t = s + v;
-    c += std::fabs(s) >= std::fabs(v) ? (s - t) + v : (v - t) + s;
-    s = t;
-  }
-  double value() const { return s + c; }
-};
-
 template <int DIM>
 void host_rows(const Args& A, double* out, long long* counts, long long* row_offsets, double* seg, int32_t* item_out,
                long long capacity) {

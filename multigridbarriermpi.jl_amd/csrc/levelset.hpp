@@ -231,6 +231,18 @@ MGB_HD void item<1>(const Args& A, const double* z, double c, long long it, Term
 // doubles of a segment row: x0 y0 x1 y1, or x and the direction
 inline int seg_width(int dim) { return dim == 2 ? 4 : 2; }
 
+// A serial sum whose error does not grow with the number of terms (Neumaier), for the host restatements: the items of a refined
+// mesh have equal areas, so the roundings of a plain running sum all point the same way and reach 1e-12 of the sum near 2e5 items.
+struct SerialSum {
+  double s = 0.0, c = 0.0;
+  void add(double v) {
+    const double t = s + v;
+    c += std::fabs(s) >= std::fabs(v) ? (s - t) + v : (v - t) + s;
+    s = t;
+  }
+  double value() const { return s + c; }
+};
+
 // levelset.hip, host: the same per-item routine, serially, row after row (row = field * nl + level) in ascending item order.
 // out: B nl x kCols; counts: B nl; row_offsets (nullable): B nl + 1; seg, item (both or neither; `capacity` rows): the
 // emitted segments and their items.  Throws ArgError where the rows do not fit into capacity.
@@ -249,6 +261,11 @@ inline size_t count_words(size_t rows, size_t nwg) { return rows * nwg + rows * 
 // levelset.hip: two launches on `stream` -- the measure on grid (workgroups(items), nl, B), then one workgroup per row that
 // finishes the row's partials and scans its per-workgroup counts; all pointers of A are device pointers
 void launch_measure(hipStream_t stream, int dim, const Args& A, double* scratch, long long* counts);
+// the second of the two, on grid (rows), shared with isosurface.hip: row r folds its nwg partial rows (kCols doubles each, from
+// NoItems) into results[r kCols ..] and turns its nwg counts into the nwg + 1 exclusive offsets at offsets[r (nwg + 1) ..], the
+// total last and into totals[r]
+void launch_finish(hipStream_t stream, int rows, const double* partials, const long long* counts, int nwg, double* results,
+                   long long* offsets, long long* totals);
 // one launch on the measure's grid: segment q of workgroup g of row r goes to slot row_base[r] + offsets[r (nwg + 1) + g] + q,
 // slots beyond `total` are not written; seg: total x seg_width doubles, item_out: total int32
 void launch_emit(hipStream_t stream, int dim, const Args& A, const long long* offsets, const long long* row_base, long long total,
