@@ -268,6 +268,27 @@ int mgb_amg_set_stop_rule(mgb_amg a, int upstream);
 int mgb_amg_set_centering(mgb_amg a, int exact);
 /* amgb main phase: t-continuation x level loop x Newton; z updated in place */
 int mgb_amg_solve(mgb_amg a, double tol, double t0, double kappa, int maxit, int max_newton, int verbose);
+/* 1 (default): later solves bracket the kernels of every 8th Newton step with HIP events and time the factorisation chain on
+ * another 8th (mgb_amg_sol_kernels, time_factor); those steps go out as plain launches.  0: no timing, every eligible step is
+ * one replayed graph.  Same kernels, same arguments, same values either way. */
+int mgb_amg_set_time_kernels(mgb_amg a, int on);
+/* Newton trace of the later solves ("Newton trace"): max_steps = 0 (default) turns it off; else a solve records every
+ * newton() call and every Newton step, and one that needs more than max_steps steps fails with MGB_E_ARG (before anything is
+ * launched when max_steps is below the Newton budget of one centering, else before the step that does not fit).  keep_vectors:
+ * also the vectors, copied back behind a stream synchronisation per copy.  Tracing changes no launch and no argument.
+ * A solve that fails, for this or any other reason, leaves z partly advanced (as every failed solve does) and a partial
+ * trace: the centerings and steps recorded up to the failure.
+ * trace_info: centerings and steps recorded by the last solve, doubles in `vectors`.
+ * trace_get (each pointer nullable): centerings = ncentering rows of 9 doubles: level, t, finest, final, Newton budget, k reached,
+ *   converged, index of its first step, its steps; steps = nsteps rows of 14 doubles: centering, y, |g|, ymin, gmin before the
+ *   step, inc = <g, n>, accepted step length (0: rejected), y and |g| after, pivot flag, launch mode (0 graph replay, 1 graph
+ *   capture, 2 plain sampled, 3 plain timed chain, 4 pcg, 5 pcg fallback, 6 host solver, 7 sharded, 8 plain untimed), bit mask of
+ *   the speculated results (steps 1, 1/2, 1/4) consumed, further objective evaluations launched, reason the loop ended (0 none,
+ *   1 inc <= 0, 2 decrement rule, 3 stagnation rule, 4 budget, 5 pivot failure, 6 non-finite decrement); vectors, in the order of
+ *   recording: per centering Dz0 (n x K), then per step s before it (N), nstep (N), s (N) and Dz (n x K) after it. */
+int mgb_amg_set_trace(mgb_amg a, int max_steps, int keep_vectors);
+int mgb_amg_trace_info(mgb_amg a, int* ncentering, int* nsteps, long long* nvec);
+int mgb_amg_trace_get(mgb_amg a, double* centerings, double* steps, double* vectors);
 /* feasibility phases (SOL_feasibility, src:428-455): make mgb_amg_solve return after the first centering at which row `col`
  * of D z -- the slack of a relaxed problem -- is negative at every node, instead of following the path to t = 1/tol.
  * col = -1 (default): off. */

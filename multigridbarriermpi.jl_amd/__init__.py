@@ -1274,6 +1274,68 @@ class AMG:
                     time_factor=tf.value, n_f0=counts[0], n_f1=counts[1], n_f2=counts[2], n_factor=counts[3],
                     kernels=kernels, pcg=dict(solves=pc[0], iterations=pc[1], fallbacks=pc[2], gave_up_at=pc[3], seconds=tp.value))
 
+    def set_exponents(self, term, p_nodes):
+        """Per-node exponents p(x) >= 1 of power-cone term `term` for the later evaluations and solves (mgb_amg_set_exponents)."""
+        pn = f64(p_nodes).reshape(-1)
+        if pn.size != self.n:
+            raise ValueError("p_nodes must give one value per node")
+        call("mgb_amg_set_exponents", self.handle, int(term), dptr(pn))
+
+    def set_term_mask(self, mask):
+        """mask[q, c] != 0 iff barrier term c is active at node q (mgb_amg_set_term_mask)."""
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.shape != (self.n, len(self.cones)):
+            raise ValueError("mask must be n x terms")
+        call("mgb_amg_set_term_mask", self.handle, m.ctypes.data_as(C.POINTER(C.c_ubyte)))
+
+    def set_time_kernels(self, on=True):
+        """Live kernel timing of the later solves (every 8th Newton step as plain launches); off: every eligible step is a graph."""
+        call("mgb_amg_set_time_kernels", self.handle, int(bool(on)))
+
+    TRACE_CENTERING = ("level", "t", "finest", "final", "budget", "k", "converged", "first_step", "steps")
+    TRACE_STEP = ("centering", "y", "g", "ymin", "gmin", "inc", "step", "y_next", "g_next", "pivot", "mode", "consumed", "evals",
+                  "reason")
+    TRACE_MODES = ("graph_replay", "graph_capture", "plain_sampled", "plain_chain", "pcg", "pcg_fallback", "host", "sharded", "plain")
+    TRACE_REASONS = ("none", "inc_nonpositive", "decrement", "stagnation", "budget", "pivot", "nonfinite")
+
+    def set_trace(self, max_steps=0, keep_vectors=False):
+        """Record the Newton loop of the later solves (mgb_amg_set_trace): 0 turns it off."""
+        call("mgb_amg_set_trace", self.handle, int(max_steps), int(bool(keep_vectors)))
+        self._trace_vectors = bool(keep_vectors) and max_steps > 0
+
+    def trace(self):
+        """The last solve's records: dict(centerings = (nc, 9) array in TRACE_CENTERING order, steps = (ns, 14) array in TRACE_STEP
+        order and, with keep_vectors, Dz0 = one (n, K) array per centering and s, nstep, s_next, Dz_next = one array per step).
+        After a solve that failed the trace is partial: what was recorded up to the failure."""
+        nc, ns, nv = C.c_int(), C.c_int(), C.c_longlong()
+        call("mgb_amg_trace_info", self.handle, C.byref(nc), C.byref(ns), C.byref(nv))
+        cen = np.empty((nc.value, len(self.TRACE_CENTERING)))
+        stp = np.empty((ns.value, len(self.TRACE_STEP)))
+        vec = np.empty(nv.value)
+        call("mgb_amg_trace_get", self.handle, dptr(cen), dptr(stp), dptr(vec))
+        out = dict(centerings=cen, steps=stp)
+        if nv.value:
+            nK = self.n_local * self.K
+            out.update(Dz0=[], s=[], nstep=[], s_next=[], Dz_next=[])
+            at = 0
+            for c in cen:
+                N = self.level_size(int(c[0]))[0]
+                out["Dz0"].append(vec[at:at + nK].reshape(self.n_local, self.K))
+                at += nK
+                for _ in range(int(c[8])):
+                    if at + 3 * N + nK > nv.value:
+                        break
+                    for name in ("s", "nstep", "s_next"):
+                        out[name].append(vec[at:at + N])
+                        at += N
+                    out["Dz_next"].append(vec[at:at + nK].reshape(self.n_local, self.K))
+                    at += nK
+            if at != nv.value:      # a solve that failed inside a step: keep the complete steps only
+                m = min(len(out[k]) for k in ("s", "nstep", "s_next", "Dz_next"))
+                for k in ("s", "nstep", "s_next", "Dz_next"):
+                    del out[k][m:]
+        return out
+
     KERNEL_NAMES = ("apply_D", "barrier_f2", "hessian_assemble", "barrier_f1", "restrict", "barrier_f0",
                     "chol_front_start", "chol_front_step", "chol_backward_rect", "chol_backward", "chol_front_single")
 

@@ -180,6 +180,10 @@ PROTOTYPES = {
     "mgb_amg_add_cost_rows": [H, H, H, C.c_int, C.c_double, C.c_int],
     "mgb_plan_prolongation": [H, H, c_int_p, c_int_p, c_int_p, c_i32_p, c_i32_p, c_dbl_p],
     "mgb_amg_solve": [H, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int],
+    "mgb_amg_set_time_kernels": [H, C.c_int],
+    "mgb_amg_set_trace": [H, C.c_int, C.c_int],
+    "mgb_amg_trace_info": [H, c_int_p, c_int_p, c_ll_p],
+    "mgb_amg_trace_get": [H, c_dbl_p, c_dbl_p, c_dbl_p],
     "mgb_amg_sol_info": [H, c_int_p, c_dbl_p, c_dbl_p, c_ll_p],
     "mgb_amg_sol_get": [H, c_ll_p, c_dbl_p, c_dbl_p],
     "mgb_amg_sol_kernels": [H, c_dbl_p, c_dbl_p, c_ll_p],

@@ -712,6 +712,32 @@ void Amg::set_exponents(int term, const double* p_nodes) {
   mu_node_.upload(mu.data(), mu.size());
   P_.a_node = a_node_.p;
   P_.mu_node = mu_node_.p;
+  drop_step_graphs();      // they hold the P_ of their capture
+}
+
+// A captured step graph holds the kernel arguments of its capture, BarrierParams by value among them: the next step after a
+// change of P_ must capture again.  No solve is running here; the stream is drained before the graphs go.
+void Amg::drop_step_graphs() {
+  hip_check(hipStreamSynchronize(ctx_.stream), "sync");
+  for (auto& lp : levels_)
+    if (lp) {
+      for (auto& g : lp->step_graphs) (void)hipGraphExecDestroy(g.exec);
+      lp->step_graphs.clear();
+    }
+}
+
+void Amg::set_trace(int max_steps, bool keep_vectors) {
+  if (max_steps < 0) throw ArgError("set_trace: max_steps must be >= 0");
+  trace_ = NewtonTrace();
+  trace_.max_steps = max_steps;
+  trace_.keep_vectors = max_steps > 0 && keep_vectors;
+}
+
+void Amg::trace_vector(const double* dev, size_t count) {
+  const size_t at = trace_.vectors.size();
+  trace_.vectors.resize(at + count);
+  hip_check(hipMemcpyAsync(trace_.vectors.data() + at, dev, count * sizeof(double), hipMemcpyDeviceToHost, ctx_.stream), "D2H trace");
+  hip_check(hipStreamSynchronize(ctx_.stream), "sync trace");
 }
 
 void Amg::set_term_mask(const unsigned char* mask) {
@@ -727,6 +753,7 @@ void Amg::set_term_mask(const unsigned char* mask) {
   }
   term_mask_.upload(m.data(), m.size());
   P_.term_mask = term_mask_.p;
+  drop_step_graphs();
 }
 
 // c, z arrive / leave in the GLOBAL layout on every rank; a sharded Amg keeps its own rows
@@ -1063,6 +1090,14 @@ void Amg::enqueue_spec_trials(Level& lv, Trial* spec, HostSignal sig) {
   }
 }
 
+// The key holds every pointer among the captured kernel arguments that rotates during a solve.  What else the capture bakes in
+// and why it holds for the life of the graphs:
+//   P_ (BarrierParams by value: a_node, mu_node, term_mask): changed only by set_exponents / set_term_mask, which drop the graphs;
+//   w_, c_, partials_, scal_, h_scal_, seq_dev_, h_seq_, h_flag_: allocated once by the constructor; set_c and add_cost_rows
+//     rewrite the values of c_ in place (DevBuf::upload allocates only when the count grows, and set_c keeps it);
+//   lv.B, lv.plan.N, n_: fixed once the level is built;
+//   the Cholesky chain's slabs, tables and fail flag: allocated by ensure_chol, which runs once per level before the first capture;
+//   kFracToBoundary, kSpecSteps, spec_count(): constants of the build and of the Amg.
 void Amg::launch_step_graph(Level& lv, Trial* spec) {
   const void* key[15] = {lv.avals.p, lv.g.p, lv.nstep.p, lv.s.p, spec[0].s, spec[0].phi, spec[0].dz, spec[1].s, spec[1].phi,
                          spec[1].dz, spec[2].s,  spec[2].phi, spec[2].dz, phi_cur_.p, Dz0_.p};
@@ -1070,6 +1105,7 @@ void Amg::launch_step_graph(Level& lv, Trial* spec) {
     if (std::equal(key, key + 15, g.key)) {
       hip_check(hipGraphLaunch(g.exec, ctx_.stream), "hipGraphLaunch");
       ++seq_expected_;      // the last trial launch of the graph signals
+      trace_mode_ = TM_GRAPH_REPLAY;
       for (int q = 0; q < spec_count(); ++q) spec[q].step = kSpecSteps[q];
       return;
     }
@@ -1097,6 +1133,7 @@ void Amg::launch_step_graph(Level& lv, Trial* spec) {
   lv.step_graphs.push_back(sg);
   hip_check(hipGraphLaunch(sg.exec, ctx_.stream), "hipGraphLaunch");
   ++seq_expected_;
+  trace_mode_ = TM_GRAPH_CAPTURE;
 }
 
 bool Amg::dev_f2_solve(Level& lv, const double* dz, double t, SolveStats& st, double* inc, Trial* spec,
@@ -1121,6 +1158,7 @@ bool Amg::dev_f2_solve(Level& lv, const double* dz, double t, SolveStats& st, do
       ok = pcg_run(lv, top, lv.g.p, lv.nstep.p, &st, nullptr, nullptr);
     }
     h_flag_.p[0] = 0;
+    trace_mode_ = ok ? TM_PCG : TM_PCG_FALLBACK;
     if (ok) pcg_bad_streak_ = 0;
     if (!ok) {
       if (!pcg_opt.fallback) return false;
@@ -1167,6 +1205,7 @@ bool Amg::dev_f2_solve(Level& lv, const double* dz, double t, SolveStats& st, do
       launch_step_graph(lv, spec);
       st.n_f0 += spec_count();
     } else {
+      trace_mode_ = !flag_rides ? TM_SHARDED : tm ? TM_PLAIN_SAMPLED : time_chain ? TM_PLAIN_CHAIN : TM_PLAIN;
       if (time_chain) {
         hip_check(hipEventCreate(&e0), "event");
         hip_check(hipEventCreate(&e1), "event");
@@ -1223,6 +1262,7 @@ bool Amg::dev_f2_solve(Level& lv, const double* dz, double t, SolveStats& st, do
   hip_check(hipMemcpyAsync(lv.h_avals.p, lv.avals.p, (size_t)nnzA * sizeof(double), hipMemcpyDeviceToHost, ctx_.stream),
             "D2H avals");
   sync_collect("sync f2");
+  trace_mode_ = TM_HOST;
   const double t0 = now_s();
   bool ok = lv.chol.factor(lv.h_avals.p);
   double acc = 0;
@@ -1300,6 +1340,31 @@ Amg::NewtonResult Amg::newton(int l, double t, bool finest, bool final, double l
   T[0].dz = DzA_.p;      // every trial keeps its own Dz: the accepted one becomes the iterate's, nothing is re-evaluated
   T[1].dz = DzB_.p;
   T[2].dz = DzC_.p;
+  // trace (NewtonTrace): the step's record is filled as the step goes and stored by tr_store, exactly once per step
+  NewtonTrace* const tr = trace_.max_steps > 0 ? &trace_ : nullptr;
+  int tr_speculated = 0, tr_consumed = 0, tr_evals = 0;
+  size_t tr_cent = 0;
+  if (tr) {
+    tr_cent = tr->centerings.size();
+    const double row[NewtonTrace::kCenteringCols] = {(double)l, t, (double)finest, (double)final, (double)maxit, 0, 0, (double)tr->nsteps(), 0};
+    tr->centerings.insert(tr->centerings.end(), row, row + NewtonTrace::kCenteringCols);
+    if (tr->keep_vectors) trace_vector(Dz0_.p, (size_t)n_ * P_.K);
+  }
+  auto tr_store = [&](double y0, double g0, double ymin0, double gmin0, double inc, double step, double y1, double g1, bool pivot,
+                      int reason) {
+    const double row[NewtonTrace::kStepCols] = {(double)(tr_cent / NewtonTrace::kCenteringCols), y0, g0, ymin0, gmin0, inc, step, y1, g1,
+                                                (double)pivot, (double)trace_mode_, (double)tr_consumed, (double)tr_evals, (double)reason};
+    tr->steps.insert(tr->steps.end(), row, row + NewtonTrace::kStepCols);
+    if (tr->keep_vectors) {      // behind the pointer rotation: the vectors the next step reads
+      trace_vector(lv.s.p, (size_t)N);
+      trace_vector(Dz_.p, (size_t)n_ * P_.K);
+    }
+  };
+  auto tr_close = [&](int k, bool converged) {      // the centering's row, once its steps are known
+    tr->centerings[tr_cent + 5] = k;
+    tr->centerings[tr_cent + 6] = converged;
+    tr->centerings[tr_cent + 8] = tr->nsteps() - tr->centerings[tr_cent + 7];
+  };
   // objective at s - step * nstep in slot `pos` (0: the oracle's "current trial", 1: its "next halving"; slot 2 only ever holds
   // a speculated result).  A speculated evaluation of that very step, wherever it sits, is moved into the slot and served.
   auto eval = [&](int pos, double step) {
@@ -1310,12 +1375,29 @@ Amg::NewtonResult Amg::newton(int l, double t, bool finest, bool final, double l
           break;
         }
     Trial& X = T[pos];
-    if (X.valid && X.step == step) return X.y;
+    if (X.valid && X.step == step) {
+      for (int q = 0; q < 3; ++q)
+        if (step == kSpecSteps[q]) tr_consumed |= tr_speculated & (1 << q);
+      return X.y;
+    }
     X.y = dev_f0(lv, lv.s.p, t, nullptr, phi_cur_.p, X.phi, X.dz, -step, lv.nstep.p, X.s);
     st.n_f0++;
+    tr_evals++;
     X.step = step;
     X.valid = true;
     return X.y;
+  };
+  // hand the scratch buffers back (pointer identities may have rotated)
+  auto hand_back = [&] {
+    lv.s_trial.p = T[0].s;
+    lv.s_trial2.p = T[1].s;
+    lv.s_trial3.p = T[2].s;
+    phi_trial_.p = T[0].phi;
+    phi_trial2_.p = T[1].phi;
+    phi_trial3_.p = T[2].phi;
+    DzA_.p = T[0].dz;
+    DzB_.p = T[1].dz;
+    DzC_.p = T[2].dz;
   };
   const double* pre = nullptr;      // Dz buffer whose Hessian values were assembled behind its gradient
   const bool speculate = !host_solve_;
@@ -1325,16 +1407,33 @@ Amg::NewtonResult Amg::newton(int l, double t, bool finest, bool final, double l
     T[0].valid = T[1].valid = T[2].valid = false;
     const double* have = pre;      // Hessian values already assembled for this Dz buffer?
     pre = nullptr;
-    if (!dev_f2_solve(lv, Dz_.p, t, st, &inc, speculate ? T : nullptr, have)) {
+    if (tr) {
+      if (tr->nsteps() >= tr->max_steps) {
+        hand_back();      // every buffer keeps one owner
+        tr_close(res.k - 1, false);      // the steps recorded so far stay readable
+        throw ArgError("newton trace: the solve takes more than the max_steps given to set_trace");
+      }
+      tr_consumed = tr_evals = 0;
+      if (tr->keep_vectors) trace_vector(lv.s.p, (size_t)N);
+    }
+    const bool spd = dev_f2_solve(lv, Dz_.p, t, st, &inc, speculate ? T : nullptr, have);
+    if (tr) {
+      tr_speculated = (T[0].valid ? 1 : 0) | (T[1].valid ? 2 : 0) | (T[2].valid ? 4 : 0);
+      if (tr->keep_vectors) trace_vector(lv.nstep.p, (size_t)N);
+    }
+    if (!spd) {
       if (verbose > 1) fprintf(stderr, "    [mgb] level %d k=%d: Hessian not numerically SPD (pivot flag %d)\n", l, res.k, h_flag_.p[0]);
+      if (tr) tr_store(y, gnorm, ymin, gmin, inc, 0.0, y, gnorm, true, TR_PIVOT);
       break;
     }
     if (!std::isfinite(inc)) {
       if (verbose > 1) fprintf(stderr, "    [mgb] level %d k=%d: non-finite Newton decrement\n", l, res.k);
+      if (tr) tr_store(y, gnorm, ymin, gmin, inc, 0.0, y, gnorm, false, TR_NONFINITE);
       break;
     }
     if (inc <= 0) {
       res.converged = true;
+      if (tr) tr_store(y, gnorm, ymin, gmin, inc, 0.0, y, gnorm, false, TR_INC_NONPOS);
       break;
     }
     // backtracking line search: the trial must be finite (amgb_all_isfinite, src:121), respect the
@@ -1376,7 +1475,11 @@ Amg::NewtonResult Amg::newton(int l, double t, bool finest, bool final, double l
     // the decrement rule everywhere but on the finest level at the last t (oracle amgb_step: stopping_inexact / stopping_exact)
     // finest level: w F is self-concordant only after division by w, so the threshold is a fraction of min w (oracle DECREMENT_FRAC)
     const double dec_tol = finest ? kDecrementFrac * w_min_ : lam_tol;
-    if ((!(finest && final) && inc < dec_tol) || exact) res.converged = true;
+    const bool small = !(finest && final) && inc < dec_tol;
+    if (small || exact) res.converged = true;
+    if (tr)
+      tr_store(y, gnorm, ymin, gmin, inc, step, ynext, gnext, false,
+               small ? TR_DECREMENT : exact ? TR_STAGNATION : res.k >= maxit ? TR_BUDGET : TR_NONE);
     y = ynext;
     gnorm = gnext;
     ymin = std::min(ymin, y);
@@ -1385,16 +1488,8 @@ Amg::NewtonResult Amg::newton(int l, double t, bool finest, bool final, double l
     if (verbose > 1)
       fprintf(stderr, "    [mgb] level %d k=%d y=%.12g |g|=%.3g inc=%.3g step=%.3g\n", l, res.k, y, gnorm, inc, step);
   }
-  // hand the scratch buffers back (pointer identities may have rotated)
-  lv.s_trial.p = T[0].s;
-  lv.s_trial2.p = T[1].s;
-  lv.s_trial3.p = T[2].s;
-  phi_trial_.p = T[0].phi;
-  phi_trial2_.p = T[1].phi;
-  phi_trial3_.p = T[2].phi;
-  DzA_.p = T[0].dz;
-  DzB_.p = T[1].dz;
-  DzC_.p = T[2].dz;
+  hand_back();
+  if (tr) tr_close(res.k, res.converged);
   return res;
 }
 
@@ -1446,6 +1541,12 @@ bool Amg::slack_negative() {
 void Amg::solve(const SolveOptions& opt, SolveStats& st) {
   hip_check(hipSetDevice(ctx_.device), "hipSetDevice");
   const int L = (int)levels_.size();
+  if (trace_.max_steps > 0) {      // the records of the last solve only; a trace that cannot hold one Newton budget is refused here
+    if (trace_.max_steps < opt.max_newton) throw ArgError("amgb: set_trace max_steps is below the Newton budget of one centering");
+    trace_.centerings.clear();
+    trace_.steps.clear();
+    trace_.vectors.clear();
+  }
   st = SolveStats();
   st.L = L;
   live_ = &st;

@@ -263,6 +263,25 @@ struct SolveStats {
   long long kern_launches[KC_COUNT] = {};
 };
 
+// Newton trace (Amg::set_trace; off by default): what every newton() call and every Newton step of the last solve decided, as
+// doubles.  DESIGN.md section "Newton trace" names the columns; tests/newton_reference.py replays them.
+enum TraceMode {      // how the linear solve + <g, n> + speculated trials of a step were launched
+  TM_GRAPH_REPLAY = 0, TM_GRAPH_CAPTURE = 1, TM_PLAIN_SAMPLED = 2, TM_PLAIN_CHAIN = 3, TM_PCG = 4, TM_PCG_FALLBACK = 5, TM_HOST = 6,
+  TM_SHARDED = 7, TM_PLAIN = 8      // plain launches with no timing: the first step of a level (pivot flag not armed yet), MGB_CHOL_GRAPH=0
+};
+enum TraceReason {      // why the Newton loop ended at this step (0: it did not)
+  TR_NONE = 0, TR_INC_NONPOS = 1, TR_DECREMENT = 2, TR_STAGNATION = 3, TR_BUDGET = 4, TR_PIVOT = 5, TR_NONFINITE = 6
+};
+struct NewtonTrace {
+  static constexpr int kCenteringCols = 9;      // level, t, finest, final, budget, k, converged, first step, steps
+  static constexpr int kStepCols = 14;          // centering, y, |g|, ymin, gmin, inc, step, y', |g|', pivot, mode, consumed, evals, reason
+  int max_steps = 0;      // 0: off
+  bool keep_vectors = false;
+  std::vector<double> centerings, steps, vectors;
+  int nsteps() const { return (int)(steps.size() / kStepCols); }
+  int ncenterings() const { return (int)(centerings.size() / kCenteringCols); }
+};
+
 // Event-pair pool: brackets single kernel launches on the context stream; resolved at host syncs.
 class KernelTimer {
  public:
@@ -382,6 +401,11 @@ class Amg {
 
   // full multigrid-barrier solve from the current z; z updated in place
   void solve(const SolveOptions& opt, SolveStats& st);
+  // record the next solves (max_steps > 0: at most that many Newton steps, ArgError beyond; 0: off).  keep_vectors: also Dz0 of
+  // every newton() call and per step s, nstep before it and s, Dz behind the pointer rotation, copied D2H behind a stream
+  // synchronisation of their own.  Nothing else about a solve changes: the same launches with the same arguments.
+  void set_trace(int max_steps, bool keep_vectors);
+  const NewtonTrace& trace() const { return trace_; }
 
   // raw pieces for benchmarking: run the device part of one F2 evaluation `reps` times
   struct KernelTimes {
@@ -437,6 +461,10 @@ class Amg {
     bool converged = false;
   };
   Level& level(int l);            // lazily built
+  NewtonTrace trace_;
+  int trace_mode_ = TM_PLAIN;      // launch mode of the last dev_f2_solve
+  void trace_vector(const double* dev, size_t count);
+  void drop_step_graphs();      // every captured Newton-step graph of every built level
   int level_index(const Level& lv) const;
   void ensure_chol(Level& lv);    // factorisation structures, built on first solve
   void analyze_chol(Level& lv);   // its host-only symbolic part (runs in Level::chol_analysis beside the uploads)

@@ -46,6 +46,7 @@ struct mgb_amg_s {
   bool pcg = false;
   bool upstream_stop = false;
   bool exact_centering = true;
+  bool time_kernels = true;
 };
 struct mgb_locator_s {
   mgb_ctx_s* ctx;
@@ -1158,6 +1159,7 @@ int mgb_amg_solve(mgb_amg a, double tol, double t0, double kappa, int maxit, int
     o.pcg = a->pcg;
     o.upstream_stop = a->upstream_stop;
     o.exact_centering = a->exact_centering;
+    o.time_kernels = a->time_kernels;
     if (tol > 0) o.tol = tol;
     if (t0 > 0) o.t0 = t0;
     if (kappa > 1) o.kappa = kappa;
@@ -1167,6 +1169,36 @@ int mgb_amg_solve(mgb_amg a, double tol, double t0, double kappa, int maxit, int
     const double ts = a->stats.t_setup;
     a->amg->solve(o, a->stats);
     a->stats.t_setup = ts;
+  });
+}
+int mgb_amg_set_time_kernels(mgb_amg a, int on) {
+  return guard([&] {
+    need(a, "null amg");
+    a->time_kernels = on != 0;
+  });
+}
+int mgb_amg_set_trace(mgb_amg a, int max_steps, int keep_vectors) {
+  return guard([&] {
+    need(a && max_steps >= 0, "set_trace: bad arguments");
+    a->amg->set_trace(max_steps, keep_vectors != 0);
+  });
+}
+int mgb_amg_trace_info(mgb_amg a, int* ncentering, int* nsteps, long long* nvec) {
+  return guard([&] {
+    need(a, "null amg");
+    const NewtonTrace& t = a->amg->trace();
+    if (ncentering) *ncentering = t.ncenterings();
+    if (nsteps) *nsteps = t.nsteps();
+    if (nvec) *nvec = (long long)t.vectors.size();
+  });
+}
+int mgb_amg_trace_get(mgb_amg a, double* centerings, double* steps, double* vectors) {
+  return guard([&] {
+    need(a, "null amg");
+    const NewtonTrace& t = a->amg->trace();
+    if (centerings) std::copy(t.centerings.begin(), t.centerings.end(), centerings);
+    if (steps) std::copy(t.steps.begin(), t.steps.end(), steps);
+    if (vectors) std::copy(t.vectors.begin(), t.vectors.end(), vectors);
   });
 }
 int mgb_amg_sol_info(mgb_amg a, int* nt, double* t_elapsed, double* time_factor, long long* counts4) {
