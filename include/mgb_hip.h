@@ -195,7 +195,9 @@ int mgb_amg_chol_info(mgb_amg a, int level, int* split_world, double* exchange_d
  *   0 Leaf  1 Single  2 SingleNarrow  3 SingleDense  4 SingleDenseNarrow  5 Start  6 Step  7 Step2  8 Panel2  9 Update2
  *   10 BwdRect  11 Bwd256  12 Bwd1024  13 BwdFused
  * unknown_node / unknown_col (nullable, N entries each): per unknown of the original ordering its tree node (postorder, as
- * mgb_amg_chol_tree) and its column among that node's own columns (0 .. ns - 1).  kind / workgroups may be null. */
+ * mgb_amg_chol_tree) and its column among that node's own columns (0 .. ns - 1).  kind / workgroups may be null.  A launch
+ * listed with no workgroup (the first launch of a height whose fronts have no row: the root of a disconnected domain) is never
+ * issued. */
 int mgb_amg_chol_schedule(mgb_amg a, int level, int cap, int* nlaunch, int* kind, int* workgroups, int* unknown_node,
                           int* unknown_col);
 /* pre-mapped child contributions of that chain (MGB_CHOL_PREMAP; nullable outputs), per launch of the first

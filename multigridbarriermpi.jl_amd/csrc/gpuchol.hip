@@ -2168,6 +2168,9 @@ int timer_class(Kind k) {      // KernelTimer class of a launch kind
 void GpuChol::run(hipStream_t st, int begin, int end, const double* d_vals, const double* d_b, double* d_x, KernelTimer* tm) {
   for (int i = begin; i < end; ++i) {
     const Launch& L = chain_[i];
+    // a height whose fronts have neither own columns nor rows (the empty-separator root of a disconnected domain: ns = nf = 0)
+    // has a first launch without a job; a grid of zero workgroups is not a valid launch, and there is nothing to do
+    if (L.cnt == 0) continue;
     long long* prof = d_prof_ ? d_prof_ + (size_t)kProfSlots * i : nullptr;
     const dim3 grid(L.cnt), block(L.block);
     const bool narrow = L.kind == Kind::SingleNarrow || L.kind == Kind::SingleDenseNarrow;

@@ -30,6 +30,8 @@ import numpy as np
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
+from mesh_cases import MESHES
+
 U = 2.0 ** -53
 MARGIN = 16.0
 LD = np.longdouble
@@ -170,6 +172,7 @@ KNOB_NAMES = ("MGB_LEAF",)
 
 _DEF_SMALL = ("Leaf", "Single", "SingleNarrow", "BwdFused")
 _DEF_MID = _DEF_SMALL + ("Start", "Step2")
+_G4_DEF = ("Start", "Step2", "Step", "Single", "Bwd256", "BwdRect", "Bwd1024", "BwdFused")      # fem2d L = 4 on graded4
 _MID = {      # fem2d L = 6, 7: variant -> (kinds the schedule must contain, kinds it must not)
     "default": (_DEF_MID, ()),
     "STEP2=0": (("Step",), ("Step2",)),
@@ -183,35 +186,71 @@ _MID = {      # fem2d L = 6, 7: variant -> (kinds the schedule must contain, kin
     "MGB_LEAF=8": (("Leaf", "SingleNarrow"), ()),
     "MGB_LEAF=160": (("Start", "Step", "Step2"), ()),
 }
-# (kind, L) -> variant -> (must contain, must not contain), in run order (default first: the bitwise yardstick)
+# (kind, L, mesh) -> variant -> (must contain, must not contain), in run order (default first: the bitwise yardstick); mesh: a
+# name of mesh_cases.MESHES, None for the default interval, square and cube
 CASES = {
-    ("fem1d", 8): {"default": (("Leaf", "SingleNarrow", "BwdFused"), ()),
+    ("fem1d", 8, None): {"default": (("Leaf", "SingleNarrow", "BwdFused"), ()),
                    "DENSE_TILES=0": (("SingleDenseNarrow",), ()),
                    "LEAF=0 SINGLE=0": (("Start", "Step", "Step2"), ())},
-    ("fem2d", 4): {"default": (_DEF_SMALL, ()),
+    ("fem2d", 4, None): {"default": (_DEF_SMALL, ()),
                    "DENSE_TILES=0": (("SingleDense", "SingleDenseNarrow"), ())},
-    ("fem2d", 6): dict(_MID),
-    ("fem2d", 7): dict(_MID, **{"MGB_LEAF=8": (("Bwd256", "SingleDenseNarrow"), ("BwdFused",))}),
-    ("fem3d", 2): {"default": (("Start", "Step2"), ()),
+    ("fem2d", 6, None): dict(_MID),
+    ("fem2d", 7, None): dict(_MID, **{"MGB_LEAF=8": (("Bwd256", "SingleDenseNarrow"), ("BwdFused",))}),
+    ("fem3d", 2, None): {"default": (("Start", "Step2"), ()),
                    "STEP2_TILES=0": (("Panel2", "Update2"), ()),
                    "MGB_LEAF=8": (("Start",), ())},
-    ("fem3d", 3): {"default": (("Start", "Step2"), ()),
+    ("fem3d", 3, None): {"default": (("Start", "Step2"), ()),
                    "STEP2_TILES=0": (("Panel2", "Update2"), ()),
                    "MGB_LEAF=8": (("Start",), ())},
+    # the trees of graded and L-shaped coarse meshes (mesh_cases): the kinds that the default meshes reach only at fem2d L = 8
+    # or under forced knobs run here in the default schedule, at sizes where the refined reference is exact
+    ("fem2d", 4, "graded4"): {          # N = 11 522, largest ns / nf 228 / 394; no Leaf launch
+        "default": (_G4_DEF, ("Leaf",)),
+        "STEP2=0": (("Step",), ("Step2",)),
+        "STEP2_TILES=0": (("Panel2", "Update2"), ()),
+        "DENSE_TILES=0": (("SingleDense",), ()),
+        "LEAF=0 SINGLE=0": (("Start", "Step", "Step2"), ("Single", "Leaf")),
+        "BWD_FUSED=0 SPLIT_NF=0": (("Bwd256", "BwdRect", "Bwd1024"), ("BwdFused",)),
+        "BWD_FUSED=0": (("Bwd256", "BwdRect", "Bwd1024"), ("BwdFused",)),
+        "MGB_LEAF=8": (("Leaf",) + _G4_DEF, ()),
+        "MGB_LEAF=160": (("Panel2", "Update2"), ()),
+        "GRAPH=0": (_G4_DEF, ("Leaf",)),
+        "START_PIVOT=0": (_G4_DEF, ("Leaf",))},
+    ("fem2d", 3, "graded4"): {          # N = 2 882, 112 / 197
+        "default": (("Start", "Step2", "Step", "Single", "BwdFused"), ("Leaf",)),
+        "MGB_LEAF=8": (("Leaf", "Start", "Step", "Step2", "Single", "BwdFused"), ())},
+    ("fem2d", 4, "graded7"): {          # N = 18 434, 498 / 671: five Bwd1024 heights above the fused launch
+        "default": (("Start", "Panel2", "Update2", "Single", "Step2", "Step", "Bwd1024", "BwdRect", "BwdFused"), ("Leaf",)),
+        "STEP2_TILES=0": (("Panel2", "Update2"), ("Step2",))},
+    ("fem2d", 5, "lshape"): {           # N = 9 218, 127 / 243
+        "default": (("Leaf", "Single", "Start", "Step2", "Step", "BwdFused"), ()),
+        "BWD_FUSED=0 SPLIT_NF=0": (("Bwd256", "BwdRect"), ("BwdFused",))},
+    ("fem2d", 4, "two_squares"): {      # N = 1 540, 43 / 64: the root has no own column and two children, a Start launch
+        "default": (("Leaf", "SingleNarrow", "Single", "Start", "BwdFused"), ())},
 }
 # the two largest sizes: matrix (a) alone, eta alone (no splu reference), eta <= 16 u
 LARGE = {
-    ("fem2d", 8): {"default": (("Panel2", "Update2", "SingleDense", "SingleDenseNarrow", "BwdRect", "Bwd1024", "BwdFused"), ()),
+    ("fem2d", 8, None): {"default": (("Panel2", "Update2", "SingleDense", "SingleDenseNarrow", "BwdRect", "Bwd1024", "BwdFused"), ()),
                    "BWD_FUSED=0": (("Panel2", "Update2", "SingleDense", "SingleDenseNarrow", "BwdRect", "Bwd1024", "Bwd256"),
                                    ("BwdFused",))},
-    ("fem3d", 4): {"default": (("Panel2", "Update2", "Step2", "SingleDense", "BwdRect", "Bwd1024", "BwdFused"), ())},
+    ("fem3d", 4, None): {"default": (("Panel2", "Update2", "Step2", "SingleDense", "BwdRect", "Bwd1024", "BwdFused"), ())},
 }
-# replay with new values and pivot failures: (kind, L, variant)
-REPLAY = (("fem2d", 6, "default"), ("fem2d", 6, "STEP2_TILES=0"), ("fem2d", 6, "DENSE_TILES=0"), ("fem3d", 3, "MGB_LEAF=8"))
-# the tree shapes at the tile edges, and where they occur (test_tree_shapes_cover_the_tile_edges)
-SHAPE_TREES = (("fem1d", 8, None), ("fem1d", 8, "160"), ("fem2d", 4, None), ("fem2d", 6, None), ("fem2d", 7, None),
-               ("fem2d", 8, None), ("fem2d", 6, "8"), ("fem2d", 7, "8"), ("fem2d", 6, "160"), ("fem2d", 7, "160"),
-               ("fem3d", 2, None), ("fem3d", 3, None), ("fem3d", 2, "8"), ("fem3d", 3, "8"))
+# the workloads of CASES on coarse meshes of mesh_cases, main case first (test_chol_reference.py pins N and the largest ns / nf)
+NEW_TREES = (("fem2d", 4, "graded4"), ("fem2d", 3, "graded4"), ("fem2d", 4, "graded7"), ("fem2d", 5, "lshape"),
+             ("fem2d", 4, "two_squares"))
+# replay with new values and pivot failures: (kind, L, mesh, variant)
+REPLAY = (("fem2d", 6, None, "default"), ("fem2d", 6, None, "STEP2_TILES=0"), ("fem2d", 6, None, "DENSE_TILES=0"),
+          ("fem3d", 3, None, "MGB_LEAF=8"), ("fem2d", 4, "graded4", "default"))
+# the tree shapes at the tile edges, and where they occur (test_tree_shapes_cover_the_tile_edges): (kind, L, mesh, MGB_LEAF)
+SHAPE_TREES = (("fem1d", 8, None, None), ("fem1d", 8, None, "160"), ("fem2d", 4, None, None), ("fem2d", 6, None, None),
+               ("fem2d", 7, None, None), ("fem2d", 8, None, None), ("fem2d", 6, None, "8"), ("fem2d", 7, None, "8"),
+               ("fem2d", 6, None, "160"), ("fem2d", 7, None, "160"), ("fem3d", 2, None, None), ("fem3d", 3, None, None),
+               ("fem3d", 2, None, "8"), ("fem3d", 3, None, "8")) + tuple((k, L, m, None) for k, L, m in NEW_TREES)
+
+
+def case_id(kind, L, mesh, *rest):
+    """pytest id of a case: the default meshes keep the ids they had before the mesh name joined the key"""
+    return "-".join([kind, str(L)] + ([] if mesh is None else [mesh]) + [str(r) for r in rest])
 
 
 def child_env(base, variant):
@@ -222,12 +261,15 @@ def child_env(base, variant):
 
 
 # ---------------------------------------------------------------------------------------------------------- host plans
-def plan(kind, L):
-    """(geometry handle, plan handle, dim, N, nnz) of the finest level of the default problem, host-only"""
+def plan(kind, L, mesh=None):
+    """(geometry handle, plan handle, dim, N, nnz) of the finest level of the default problem, host-only; mesh: a name of
+    mesh_cases.MESHES (fem2d alone), None for the default mesh"""
     import mgb_amd as M
     from mgb_amd import _lib
     call, dptr, iptr, f64, i32 = _lib.call, _lib.dptr, _lib.iptr, _lib.f64, _lib.i32
-    g = getattr(M, kind)(L) if kind != "fem3d" else M.fem3d(L, 3)
+    if mesh is not None and kind != "fem2d":
+        raise ValueError("a coarse mesh needs fem2d")
+    g = M.fem3d(L, 3) if kind == "fem3d" else (M.fem2d(L, MESHES[mesh]) if mesh is not None else getattr(M, kind)(L))
     dim = {"fem1d": 1, "fem2d": 2, "fem3d": 3}[kind]
     x = f64(np.asarray(g.x).reshape(np.asarray(g.x).shape[0], -1))
     Lv = len(g.refine)

@@ -12,7 +12,8 @@ R_{l+1} P_l = R_l, and which `nodal_prolongation` restates here for the CPU test
 
   cheb    one Chebyshev-Jacobi sweep (Saad, Iterative Methods, Alg. 12.1) on [lo_frac, hi_frac] * lam
   Vcycle  x = cheb(0); r = b - H x; x += P Vcycle(P' r); x = cheb(x); an exact solve on the coarsest level c0, the largest
-          level with 0 < N <= 128 unknowns
+          level with 0 < N <= 128 unknowns (level 0 where there is none: the coarse meshes of mesh_cases.py, where the
+          device's coarse solve is its sparse Cholesky and the dense factor here restates that too)
   pcg     the textbook recurrence with the stop rule of pcg_dot_kernel, every iterate kept
 
 The long-double run of the same code is the reference; its distance to the float64 run is what rounding alone does to
@@ -23,6 +24,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 import mgb_oracle as O
+from mesh_cases import MESHES
 
 LD = np.longdouble
 assert np.finfo(LD).nmant >= 63, "mg_reference needs an extended-precision long double (x87); there is no fallback"
@@ -40,8 +42,13 @@ SHAPES = (("fem2d", 4),      # 1 .. 3: N = 50, 194, 770, one intermediate level
           ("fem3d", 3),      # 0 .. 2: N = 72, 468, 3528
           ("fem1d", 7),      # 5 .. 6: N = 128, 256: the largest dense inverse
           ("fem1d", 6),      # 5 .. 5: N = 128, top == c0
-          ("fem2d", 2))      # 1 .. 1: N = 50, top == c0
-CASES = tuple((k, L, p) for k, L in SHAPES for p in ((1.0, 1.5, 2.0) if k == "fem2d" else (1.0, 1.5)))
+          ("fem2d", 2),      # 1 .. 1: N = 50, top == c0
+          # coarse meshes of mesh_cases (a case then carries the mesh name: (kind, L, p, mesh)), p = 1 and 1.5
+          ("fem2d", 3, "graded4"),      # 0 .. 2: N = 182, 722, 2882: no level has N <= 128, so c0 = 0 and the coarse solve is
+                                        # the device Cholesky (mg_prepare), not the dense inverse
+          ("fem2d", 4, "lshape"))       # 0 .. 3: N = 38, 146, 578, 2306: the dense inverse under an irregular hierarchy
+CASES = tuple((k, L, p) for k, L in SHAPES[:6] for p in ((1.0, 1.5, 2.0) if k == "fem2d" else (1.0, 1.5))) + \
+    tuple((k, L, p, m) for k, L, m in SHAPES[6:] for p in (1.0, 1.5))
 # test 5 (iteration count at rtol = 1e-11): (kind, L, p, degree) -> seed of `count_rhs`.  The seed is chosen on the long-double
 # restatement so that <r, V r> / (rtol^2 <r0, V r0>) is above 4 at the last iteration but one and below 0.25 at the last: rounding
 # cannot move the count then.  Convergence per iteration is about a factor 8 in <r, V r> at degree 1 on the 2-D and 3-D
@@ -221,7 +228,8 @@ def pcg(H, V, g, rtol, maxit):
 
 # ------------------------------------------------------------------------------------------------ the systems, from the oracle
 def coarsest(sizes, top):
-    """Amg::mg_coarsest: the largest level <= top with 0 < N <= 128 (level 0, or the first non-empty one, if there is none)."""
+    """Amg::mg_coarsest: the largest level <= top with 0 < N <= 128 (level 0, or the first non-empty one, if there is none; the
+    device then solves that level with its sparse Cholesky, the restatement with the same dense factor as ever)."""
     c0 = 0
     for l in range(top + 1):
         if 0 < sizes[l] <= DENSE_MAX:
@@ -258,9 +266,9 @@ class System:
     """One Newton system of the oracle in the oracle's numbering: levels c0 .. top = L - 1, s = S_SCALE randn(seed), the
     Hessians H_l at z0 + R_top s with t = T, the gradient g of the top level, lam_l and the transfers P_l."""
 
-    def __init__(self, kind, L, p, seed=SEED):
-        self.kind, self.L, self.p, self.top = kind, L, p, L - 1
-        go = getattr(O, kind)(L)
+    def __init__(self, kind, L, p, mesh=None, seed=SEED):
+        self.kind, self.L, self.p, self.top, self.mesh = kind, L, p, L - 1, mesh
+        go = getattr(O, kind)(L) if mesh is None else O.fem2d(L, MESHES[mesh])
         dim = go.discretization["dim"]
         self.Mo = Mo = O.amg(go)
         self.z0 = z0 = O.map_rows(lambda xi: O.DEFAULT_G[dim](xi), Mo.x).reshape(-1, order="F")
@@ -334,9 +342,13 @@ def count_margins(res, rtol=COUNT_RTOL):
 _systems = {}
 
 
-def system(kind, L, p):
+def system(kind, L, p, mesh=None):
     """The shared System of a case: computed once per process and left unchanged."""
-    key = (kind, L, float(p))
+    key = (kind, L, float(p), mesh)
     if key not in _systems:
-        _systems[key] = System(kind, L, float(p))
+        _systems[key] = System(kind, L, float(p), mesh)
     return _systems[key]
+
+
+def case_id(c):
+    return "%s-L%d-p%g" % c[:3] + ("" if len(c) == 3 else "-" + c[3])

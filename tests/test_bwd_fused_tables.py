@@ -1,6 +1,6 @@
 """Host-only checks of the tables behind the fused backward sweep of the device Cholesky (csrc/bwd_fused.hpp), through
-mgb_plan_chol_bwd_fused: no GPU needed.  For the trees of fem1d / fem2d / fem3d at several L and several cuts (and a
-front-size threshold that puts h_top below the root):
+mgb_plan_chol_bwd_fused: no GPU needed.  For the trees of fem1d / fem2d / fem3d at several L, of fem2d on the coarse meshes of
+mesh_cases.py, and several cuts (and a front-size threshold that puts h_top below the root):
 
   * every front at or below h_top is stored by exactly one workgroup, nothing above h_top is stored;
   * a workgroup's ancestors come in top-down order: the fronts above h_top first (read, not solved), then its path, one
@@ -15,6 +15,8 @@ import sys
 import numpy as np
 import pytest
 
+from mesh_cases import MESHES
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
@@ -22,13 +24,14 @@ HDR, LEVEL_INTS, JOB_INTS = 8, 4, 16
 OFF, LOFF, FIRST, NF, NS, SOFS, BASE, LSOFS, NSL, NT, FLAGS, NODE = 0, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13
 
 
-def _plan_handles(kind, L):
-    """(geometry handle, plan handle, dim) of the finest level, as tools/tree_stats.py builds them"""
+def _plan_handles(kind, L, mesh=None):
+    """(geometry handle, plan handle, dim) of the finest level, as tools/tree_stats.py builds them; mesh: a name of
+    mesh_cases.MESHES, the coarse mesh of fem2d"""
     import scipy.sparse as sp
     import mgb_amd as M
     from mgb_amd import _lib
     call, dptr, iptr, f64, i32 = _lib.call, _lib.dptr, _lib.iptr, _lib.f64, _lib.i32
-    g = getattr(M, kind)(L) if kind != "fem3d" else M.fem3d(L, 3)
+    g = M.fem3d(L, 3) if kind == "fem3d" else (M.fem2d(L, MESHES[mesh]) if mesh is not None else getattr(M, kind)(L))
     dim = {"fem1d": 1, "fem2d": 2, "fem3d": 3}[kind]
     x = f64(np.asarray(g.x).reshape(np.asarray(g.x).shape[0], -1))
     w = f64(g.w)
@@ -54,22 +57,22 @@ def _plan_handles(kind, L):
 _TREES = {}
 
 
-def _tree(kind, L):
-    if (kind, L) not in _TREES:
+def _tree(kind, L, mesh=None):
+    if (kind, L, mesh) not in _TREES:
         from mgb_amd import _lib
-        h, p, dim = _plan_handles(kind, L)
+        h, p, dim = _plan_handles(kind, L, mesh)
         nn = C.c_int()
         _lib.call("mgb_plan_chol_tree", p, dim, 0, C.byref(nn), None, None, None)
         ns, nf, par = (np.zeros(nn.value, dtype=np.int32) for _ in range(3))
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
         _lib.call("mgb_plan_chol_tree", p, dim, nn.value, C.byref(nn), ip(ns), ip(nf), ip(par))
-        _TREES[(kind, L)] = (h, p, dim, ns, nf, par)
-    return _TREES[(kind, L)]
+        _TREES[(kind, L, mesh)] = (h, p, dim, ns, nf, par)
+    return _TREES[(kind, L, mesh)]
 
 
-def _fused(kind, L, cut, top_nf, threads):
+def _fused(kind, L, cut, top_nf, threads, mesh=None):
     from mgb_amd import _lib
-    h, p, dim, ns, nf, par = _tree(kind, L)
+    h, p, dim, ns, nf, par = _tree(kind, L, mesh)
     ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
     info = np.zeros(12, dtype=np.int32)
     _lib.call("mgb_plan_chol_bwd_fused", p, dim, cut, top_nf, threads, ip(info), 0, None, 0, None, None, 0, None, None)
@@ -85,12 +88,33 @@ def _fused(kind, L, cut, top_nf, threads):
 
 CASES = [("fem1d", 3), ("fem1d", 7), ("fem2d", 2), ("fem2d", 4), ("fem2d", 5), ("fem2d", 6), ("fem2d", 7), ("fem3d", 2), ("fem3d", 3)]
 SETTINGS = [(4, 384, 512), (3, 384, 512), (2, 0, 256), (0, 0, 64), (4, 150, 512), (1, 100, 128), (9, 0, 512)]
+# the trees of the coarse meshes of mesh_cases (chol_reference.NEW_TREES): fronts above the default threshold of 384 on top of
+# a fused launch (graded4 and graded7 at L = 4), and a root without own columns (two_squares)
+MESH_CASES = [("fem2d", 4, "graded4"), ("fem2d", 3, "graded4"), ("fem2d", 4, "graded7"), ("fem2d", 5, "lshape"),
+              ("fem2d", 4, "two_squares")]
 
 
 @pytest.mark.parametrize("kind,L", CASES)
 @pytest.mark.parametrize("cut,top_nf,threads", SETTINGS)
 def test_fused_backward_tables(kind, L, cut, top_nf, threads):
-    P = _fused(kind, L, cut, top_nf, threads)
+    _check(_fused(kind, L, cut, top_nf, threads), cut, top_nf, threads)
+
+
+@pytest.mark.parametrize("kind,L,mesh", MESH_CASES, ids=["%s-%d-%s" % c for c in MESH_CASES])
+@pytest.mark.parametrize("cut,top_nf,threads", SETTINGS)
+def test_fused_backward_tables_of_coarse_meshes(kind, L, mesh, cut, top_nf, threads):
+    _check(_fused(kind, L, cut, top_nf, threads, mesh), cut, top_nf, threads)
+
+
+def test_default_plans_of_the_graded_meshes_stop_below_the_large_fronts():
+    """graded4 and graded7 at L = 4: the heights with a front above 384 rows stay with the per-height launches (Bwd1024), the
+    fused launch takes the heights below; the other coarse-mesh trees are fused up to the root"""
+    for (kind, L, mesh), above in zip(MESH_CASES, (1, 0, 5, 0, 0)):
+        P = _fused(kind, L, 2, 384, 512, mesh)
+        assert P["nwg"] >= 1 and P["nheights"] - 1 - P["h_top"] >= above and (above > 0) == (P["h_top"] < P["nheights"] - 1), (mesh, L)
+
+
+def _check(P, cut, top_nf, threads):
     ns, nf, par, first = P["ns"], P["nf"], P["par"], P["first"]
     n = len(ns)
     height = np.zeros(n, dtype=int)

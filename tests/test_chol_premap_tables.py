@@ -1,5 +1,6 @@
 """Host-only checks of the tables behind the pre-mapped child contributions of the device Cholesky (csrc/chol_premap.hpp),
-through mgb_plan_chol_premap: no GPU needed.  Over the trees of fem1d L=8, fem2d L=4 / 6 / 7 and fem3d L=2 / 3, with the
+through mgb_plan_chol_premap: no GPU needed.  Over the trees of fem1d L=8, fem2d L=4 / 6 / 7 and fem3d L=2 / 3, and of the
+coarse meshes of mesh_cases.py (chol_reference.NEW_TREES: graded and L-shaped meshes, a domain of two components), with the
 leaf and single kinds on and off, both consumer modes and a tile limit that bites:
 
   * for every consumer front and slot the positions (fwd[i], fwd[j]), i >= j, over the child's boundary including its
@@ -18,6 +19,7 @@ import chol_reference as R
 
 LEAF, SINGLE, START = 0, 1, 2
 TREES = [("fem1d", 8), ("fem2d", 4), ("fem2d", 6), ("fem2d", 7), ("fem3d", 2), ("fem3d", 3)]
+MESH_TREES = list(R.NEW_TREES)      # the trees of the coarse meshes of mesh_cases: (kind, L, mesh)
 # (leaf, single, mode, tiles)
 SETTINGS = [(1, 1, 2, 512), (1, 1, 1, 512), (0, 1, 2, 512), (1, 0, 2, 512), (0, 0, 2, 512), (1, 1, 2, 40), (1, 1, 0, 512),
             (1, 1, 2, 1 << 30)]
@@ -25,17 +27,17 @@ SETTINGS = [(1, 1, 2, 512), (1, 1, 1, 512), (0, 1, 2, 512), (1, 0, 2, 512), (0, 
 _PLANS = {}
 
 
-def _handles(kind, L):
-    if (kind, L) not in _PLANS:
-        h, p, dim, N, nz = R.plan(kind, L)
+def _handles(kind, L, mesh=None):
+    if (kind, L, mesh) not in _PLANS:
+        h, p, dim, N, nz = R.plan(kind, L, mesh)
         ns, nf, par = R.plan_tree(p, dim)
-        _PLANS[(kind, L)] = (h, p, dim, ns, nf, par)
-    return _PLANS[(kind, L)]
+        _PLANS[(kind, L, mesh)] = (h, p, dim, ns, nf, par)
+    return _PLANS[(kind, L, mesh)]
 
 
-def _premap(kind, L, leaf, single, mode, tiles):
+def _premap(kind, L, leaf, single, mode, tiles, mesh=None):
     from mgb_amd import _lib
-    h, p, dim, ns, nf, par = _handles(kind, L)
+    h, p, dim, ns, nf, par = _handles(kind, L, mesh)
     ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
     lp = lambda a: a.ctypes.data_as(C.POINTER(C.c_longlong))
     info = np.zeros(5, dtype=np.int64)
@@ -109,7 +111,8 @@ def _check(P, mode, tiles):
             i, j = fw[a[keep]], fw[q[keep]]
             assert np.all(i >= j) and np.all(j < nf[t]) and np.all(i <= nf[t])     # lower part, row nf included
             pos = ld * j + i
-            assert pos.min(initial=0) >= 0 and pos.max(initial=0) < size           # inside the slab
+            assert len(pos) == 0 or (pos.min() >= 0 and pos.max() < size)          # inside the slab (a child without a
+                                                                                   # boundary stores nothing: two_squares' root)
             assert len(np.unique(pos)) == len(pos)                                 # distinct
     # forward o inverse = identity, and the inverse maps nothing else
     for t in range(n):
@@ -147,6 +150,17 @@ def test_premap_tables(kind, L, leaf, single, mode, tiles):
         assert not P["hcons"][1]      # children from front_start + panel launches: the gather stays
 
 
+@pytest.mark.parametrize("kind,L,mesh", MESH_TREES, ids=[R.case_id(*c) for c in MESH_TREES])
+@pytest.mark.parametrize("leaf,single,mode,tiles", SETTINGS)
+def test_premap_tables_of_coarse_meshes(kind, L, mesh, leaf, single, mode, tiles):
+    P = _premap(kind, L, leaf, single, mode, tiles, mesh)
+    _check(P, mode, tiles)
+    if mode == 0 or (not single and mode < 2):
+        assert P["slab"] == 0 and not P["hcons"].any() and not P["producer"].any()
+    if not leaf and P["hkind"][0] == START and len(P["hkind"]) > 1:
+        assert not P["hcons"][1]
+
+
 def test_expected_consumers_of_the_default_schedules():
     """the launches the GPU cases rely on (tests/test_gpu_chol_premap.py) are consumers in the host plan too"""
     P = _premap("fem2d", 4, 1, 1, 2, 512)
@@ -158,6 +172,15 @@ def test_expected_consumers_of_the_default_schedules():
     assert P["hkind"][0] == START and list(P["hcons"][:6]) == [0, 0, 1, 1, 1, 1]
     P = _premap("fem2d", 7, 1, 1, 2, 512)
     assert list(P["hcons"][:7]) == [0, 1, 1, 1, 1, 1, 1] and not P["hcons"][7:].any()
+    # the coarse meshes: graded4 has no Leaf height and one Single height above a Start height, so nothing is pre-mapped; the L
+    # shape is the square's picture; the two squares' root (no row at all) is a consumer of two children without a boundary
+    P = _premap("fem2d", 4, 1, 1, 2, 512, "graded4")
+    assert list(P["hkind"]) == [START, SINGLE] + [START] * 7 and not P["hcons"].any() and P["slab"] == 0
+    P = _premap("fem2d", 5, 1, 1, 2, 512, "lshape")
+    assert list(P["hkind"]) == [LEAF] + [SINGLE] * 4 + [START] * 4 and list(P["hcons"]) == [0, 1, 1, 1, 1, 1, 0, 0, 0]
+    P = _premap("fem2d", 4, 1, 1, 2, 512, "two_squares")
+    assert list(P["hkind"]) == [LEAF] + [SINGLE] * 4 + [START] and list(P["hcons"]) == [0, 1, 1, 1, 1, 1]
+    assert P["ns"][-1] == 0 and P["nf"][-1] == 0 and P["hwg"][-1] == 0
     for L in (2, 3):      # no Leaf / Single* launch at all: nothing is pre-mapped
         P = _premap("fem3d", L, 0, 0, 2, 512)
         assert not (P["hkind"] != START).any() and P["slab"] == 0 and not P["hcons"].any()

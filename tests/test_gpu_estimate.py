@@ -18,6 +18,7 @@ import pytest
 import boundary_reference as BR
 import energy_reference as ER
 import estimate_reference as XR
+import mgb_oracle as O
 import mixed_reference as MR
 
 pytestmark = pytest.mark.gpu
@@ -316,9 +317,10 @@ def test_sharded_contexts_are_refused(M, lib):
     assert (eta.to_numpy() == 7.0).all() and (out == 7.0).all()
 
 
-def solve_yardstick(M, sol, p, f=0.5, h=None, free=None, r=2.0):
+def solve_yardstick(M, sol, p, f=0.5, h=None, free=None, r=2.0, z=None):
+    """the yardstick on the solution's own z, or on another z of the same geometry"""
     g = sol.geometry
-    z = M.mpi_to_native(sol).z
+    z = M.mpi_to_native(sol).z if z is None else z
     F = BR.facets(g)
     I = XR.interior_facets(g, F)
     w = g.w.to_numpy() if hasattr(g.w, "to_numpy") else np.asarray(g.w)
@@ -357,7 +359,8 @@ def test_mixed_solve(M):
 
 def test_adapt_on_the_l_shape(M):
     """On the CPU oracle's solves the same loop gives 6, 10, 14 triangles (168, 280, 392 rows) and totals 1.891, 1.462, 1.252;
-    the marked sets are ties of the symmetric L shape and are not compared."""
+    the marked sets are ties of the symmetric L shape and are not compared.  Every step's z is held to the oracle's solve on the
+    mesh the device loop produced, and its total to the yardstick on that oracle z."""
     L, p, theta = 2, 2.0, 0.5
     steps = M.adapt(BR.L_SHAPE, L, p, 2, theta=theta)
     assert len(steps) == 3
@@ -370,6 +373,16 @@ def test_adapt_on_the_l_shape(M):
         Y, _ = solve_yardstick(M, sol, p)
         XR.check("adapt step %d" % k, Y, ind.parts, columns(ind))
         print("adapt step %d: %d triangles, %d rows, total %.6f" % (k, counts[-1], len(sol.geometry.w), ind.total))
+        # the oracle on the mesh the device loop produced (the marked sets are ties): z at the bound of every whole solve, and
+        # the total within the yardstick's own bar of the yardstick on the oracle's z
+        zo = O.fem2d_solve(L=L, K=K, p=p).z
+        z = M.mpi_to_native(sol).z
+        err = np.linalg.norm(z - zo) / np.linalg.norm(zo)
+        Yo, _ = solve_yardstick(M, sol, p, z=zo)
+        total_o = math.fsum(Yo["totals"][:3]) ** 0.5
+        print("adapt step %d: z against the oracle %.3e, total on the oracle's z %.6f (device %.6f)" % (k, err, total_o, ind.total))
+        assert z.shape == zo.shape and err < 1e-10
+        assert abs(ind.total ** 2 - math.fsum(Yo["totals"][:3])) <= 4 * KTOL * math.fsum(Yo["totals_mag"])
         values = ind.coarse(L)
         marked = M.mark(values, theta)
         assert XR.dorfler_ok(values, marked, theta)

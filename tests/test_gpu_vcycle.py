@@ -8,6 +8,10 @@ level the lambda_max(D^-1 H_l) that scipy's eigsh computes from the reference H_
 differs from call to call), and AMG.vcycle returns V(b) itself and the lambda each level used.  P_l of the library is held to
 the reference's own nodal restatement here, on top of R_{l+1} P_l = R_l in test_gpu_mg.py.
 
+Two hierarchies come from coarse meshes of tests/mesh_cases.py: fem2d L=3 on graded4 (N = 182, 722, 2882: no level fits the dense
+inverse, so mg_coarsest is level 0 and the coarse solve of the V-cycle is the device Cholesky) and fem2d L=4 on the L shape (N = 38
+.. 2306: the dense inverse under an irregular hierarchy).
+
 Tolerances, none from the code under test (figures: profiles/vcycle_reference.txt, from test_mg_reference.py -s and a run of
 this file with -s):
   V(b)                    1e-11 relative, what test_gpu_mg.py gives the same recurrences on one level; the float64 and long-double
@@ -41,8 +45,7 @@ def M(gpu_required):
     return mgb_amd
 
 
-def _id(c):
-    return "%s-L%d-p%g" % c
+_id = R.case_id
 
 
 class Dev:
@@ -50,10 +53,11 @@ class Dev:
     the library's; every level of the V-cycle pinned to the reference's lambda_max."""
 
     def __init__(self, M, case):
-        kind, L, p = case
+        kind, L, p = case[:3]
+        mesh = case[3] if len(case) > 3 else None      # a name of mesh_cases.MESHES: fem2d_mpi(L, K)
         self.S = S = R.system(*case)
         assert S.inside and S.is_spd()      # strictly inside the cone, and the top Hessian has a Cholesky factor
-        self.A = A = M.AMG(getattr(M, kind + "_mpi")(L), p=p)
+        self.A = A = M.AMG(getattr(M, kind + "_mpi")(L) if mesh is None else M.fem2d_mpi(L, R.MESHES[mesh]), p=p)
         A.set_c(S.c)
         A.set_z(S.z0)
         sub = A.geometry.subspaces
@@ -63,6 +67,8 @@ class Dev:
             self.pi[l] = _match_columns(S.Mo.R[l], Rg)
             assert A.level_size(l)[0] == S.sizes[l]
         assert A.mg_coarsest(S.top) == S.c0
+        if mesh == "graded4":      # the case of the Cholesky coarse solve: level 0, too large for the dense inverse
+            assert A.mg_coarsest(S.top) == 0 and A.level_size(0)[0] == S.sizes[0] > R.DENSE_MAX
         for l in range(S.c0, S.top):
             Pg = A.prolongation(l).tocsr()
             assert abs(Pg[self.pi[l + 1]][:, self.pi[l]] - S.P[l]).max() < 1e-13

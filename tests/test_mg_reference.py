@@ -13,8 +13,7 @@ LD = R.LD
 DEGREES = (1, 2, 3, 4)
 
 
-def _id(c):
-    return "%s-L%d-p%g" % c
+_id = R.case_id
 
 
 @pytest.mark.parametrize("case", R.CASES, ids=_id)
@@ -24,8 +23,11 @@ def test_inputs_are_inside_the_cone_and_positive_definite(case):
     S = R.system(*case)
     assert S.inside and S.is_spd()
     want = {("fem2d", 4): (1, [50, 194, 770]), ("fem2d", 5): (1, [50, 194, 770, 3074]), ("fem3d", 3): (0, [72, 468, 3528]),
-            ("fem1d", 7): (5, [128, 256]), ("fem1d", 6): (5, [128]), ("fem2d", 2): (1, [50])}[case[:2]]
+            ("fem1d", 7): (5, [128, 256]), ("fem1d", 6): (5, [128]), ("fem2d", 2): (1, [50]),
+            ("fem2d", 3, "graded4"): (0, [182, 722, 2882]), ("fem2d", 4, "lshape"): (0, [38, 146, 578, 2306])}[case[:2] + case[3:]]
     assert (S.c0, S.sizes[S.c0:]) == want
+    if case[3:] == ("graded4",):      # no level is small enough for the dense inverse: level 0 it is, above kDenseMax
+        assert S.c0 == 0 and min(S.sizes) > R.DENSE_MAX
     for l in range(S.c0, S.top):
         assert abs(S.Mo.R[l + 1] @ S.P[l] - S.Mo.R[l]).max() < 1e-12
         # Galerkin: the oracle's H_l is P_l' H_{l+1} P_l
