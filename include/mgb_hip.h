@@ -626,6 +626,67 @@ int mgb_geo_isosurfaces_host(mgb_geo g, int B, const double* const* z /* B array
                              long long* counts /* B nl */, long long* row_offsets_or_null, double* tri_or_null,
                              int32_t* item_or_null, long long capacity);
 
+/* ---- flow lines of nodal fields: paths, lengths, travel times ------------------------------------------------------------ *
+ * The curves that follow grad u through the broken polynomial field of column u of B fields (n x S, row-major) on one 2-D
+ * (block 7) or 3-D (block (k+1)^3, k = 1..3) geometry, from m seeds, by the explicit midpoint rule in ARC LENGTH: the
+ * exponent p of sigma = |grad u|^(p-2) grad u enters the travel time int ds / |sigma| only, never the geometry.
+ * Notation.  val(e, q), grad(e, q): value and physical gradient of element e's polynomial at q by the bases of
+ *   mgb_interpolate; q need not lie in e.  locate(e, q) = e if q is inside e by the containment rule above (tau = 1e-12), else
+ *   the lowest element that contains q, -1 when none does or a coordinate is not finite.  sgn = direction, +1 (up the
+ *   gradient) or -1.  |.| = the square root of the sum of squares taken in index order.
+ * For seed x_0: e_0 = the lowest element that contains x_0; if there is none the status is OUTSIDE, the count 0, the end element
+ * -1 and every double of the row NaN.  Otherwise the seed is recorded and for k = 0, 1, ...:
+ *   1. v = val(e_k, x_k), g = grad(e_k, x_k); at k = 0 v is u_start.  Any of them non-finite: stop, NONFINITE.
+ *   2. a = |g|.  Not a > gmin: stop, STALLED (a NaN cannot pass this comparison).
+ *   3. k == max_steps: stop, MAXSTEPS.
+ *   4. d = sgn g / a, q_m = x_k + (ds / 2) d, e_m = locate(e_k, q_m).  e_m < 0: exit along x_k -> q_m.
+ *   5. g_m = grad(e_m, q_m).  Non-finite: stop, NONFINITE, at x_k.  a_m = |g_m|.  Not a_m > gmin: stop, STALLED, at x_k.
+ *   6. d_m = sgn g_m / a_m, q_n = x_k + ds d_m, e_n = locate(e_m, q_n).  e_n < 0: exit along x_k -> q_n.
+ *   7. length += ds; time += ds a_m^(1-p) (exactly 1 for p = 1 and 1 / a_m for p = 2, pow otherwise); x_{k+1} = q_n,
+ *      e_{k+1} = e_n, and the point is recorded.
+ * Exit along x_k -> q: lo = 0, hi = 1, the remembered element e_k; forty times th = (lo + hi) / 2, r = x_k + th (q - x_k),
+ *   e = locate(e_k, r); e >= 0: lo = th and e is remembered, else hi = th.  The end point x_k + lo (q - x_k), in the remembered
+ *   element, is recorded only if lo > 0; length += lo |q - x_k|, time += lo |q - x_k| a^(1-p) with the a of step 2; EXIT.
+ * u_end = val at the end point in its element.  Every sum runs serially in step order.  A line that slides along an edge whose
+ * two sides both point at it zigzags until MAXSTEPS: documented behaviour, not an error.
+ * Per row r = b m + i (field b, seed i): MGB_FLOW_COLS doubles [length, time, u_start, u_end]; the end point (dim doubles);
+ * int32 status, count (the points recorded, the seed included, at most max_steps + 1) and end element.
+ * ds_or_null: the step; null takes a quarter of the smallest element extent (the extent of an element is the largest side of
+ * its bounding box; computed from x once per geometry and kept with the locator); ds_used_or_null receives the step taken.
+ * workgroup: 0 (the default, 64), 64, 128 or 256 threads; the result does not depend on it.
+ * Launches: ONE, a grid (ceil(m / workgroup), B), one thread per (seed, field), no atomics, no LDS, no barrier; with
+ * paths_or_null non-null every thread also records its points and their elements in its own row of max_steps + 2 slots (a slot
+ * beyond that is never written), and after the counts have reached the host a second launch, one workgroup per row, gathers the
+ * rows into CSR arrays behind the handle: offsets (B m + 1), points (total x dim), elements (total).  A call repeated returns
+ * the same bits; a row does not depend on B, m or its place in the batch.  The rule is compiled with fp contraction off on both
+ * sides: device and host restatement agree bit for bit except in `time` for p other than 1 and 2 (pow).
+ * MGB_E_ARG, before anything is launched or written: a null argument or field; a 1-D geometry; ds not finite or <= 0;
+ * max_steps < 1; gmin not finite or < 0; direction not +1 or -1; p not finite or < 1; S < 1; u outside [0, S); B < 1 or
+ * B > 65535; m < 0; more than INT_MAX rows; vectors of the wrong length or of another context; a sharded context; another
+ * workgroup size; with paths, B m (max_steps + 2) dim beyond 2^31 - 1.  m = 0 returns at once (an empty handle with paths). */
+#define MGB_FLOW_COLS 4
+#define MGB_FLOW_EXIT 0
+#define MGB_FLOW_STALLED 1
+#define MGB_FLOW_MAXSTEPS 2
+#define MGB_FLOW_OUTSIDE 3
+#define MGB_FLOW_NONFINITE 4
+typedef struct mgb_flowpath_s* mgb_flowpath;   /* the recorded points of one call, device resident, in CSR form */
+int mgb_geo_flow_lines(mgb_locator loc, int B, const mgb_vec* z /* B vectors of n x S */, int S, int u, int m,
+                       const double* seeds_host /* m x dim */, double p, int direction, const double* ds_or_null, int max_steps,
+                       double gmin, int workgroup, double* rows_host /* B m x MGB_FLOW_COLS */, double* end_host /* B m x dim */,
+                       int32_t* status_host /* B m */, int32_t* count_host /* B m */, int32_t* end_element_host /* B m */,
+                       double* ds_used_or_null, mgb_flowpath* paths_or_null);
+/* copies out what is asked for (null: skipped): offsets (B m + 1), pts (total x dim), elem (total) */
+int mgb_flowpath_get(mgb_flowpath paths, long long* offsets, double* pts, int32_t* elem);
+int mgb_flowpath_destroy(mgb_flowpath paths);
+/* host restatement (no context, no GPU): the same routine, row after row.  offsets_or_null (B m + 1), pts_or_null
+ * (capacity x dim) and elem_or_null (capacity) come together; MGB_E_ARG when more points are recorded than they hold. */
+int mgb_geo_flow_lines_host(mgb_geo g, int B, const double* const* z /* B arrays of n x S */, int S, int u, int m,
+                            const double* seeds /* m x dim */, double p, int direction, const double* ds_or_null, int max_steps,
+                            double gmin, double* rows /* B m x MGB_FLOW_COLS */, double* end /* B m x dim */, int32_t* status,
+                            int32_t* count, int32_t* end_element, double* ds_used_or_null, long long* offsets_or_null,
+                            double* pts_or_null, int32_t* elem_or_null, long long capacity);
+
 /* ---- boundary facets of a geometry and boundary integrals of p-Laplace solutions --------------------------------------- *
  * The elements are broken and their quadrature is nodal: every node of a boundary facet is a row of x and z already, so the
  * boundary rule of a geometry is a list of nf facets of q nodes each: q global rows, q weights omega, the outward unit normal n,

@@ -37,7 +37,7 @@ __all__ = [
     "backend_hip", "amgb_zeros", "amgb_all_isfinite", "amgb_diag", "amgb_blockdiag", "map_rows", "map_rows_gpu",
     "_raw_array", "_to_cpu_array", "MGBError", "device_count", "AMG", "amg", "hcat", "BarrierFn", "barrier_functions",
     "interpolate", "sample_grid", "norms", "error", "convergence", "FieldNorms", "Convergence",
-    "energy", "flux", "Energy", "level_sets", "LevelSets", "isosurfaces", "Isosurfaces",
+    "energy", "flux", "Energy", "level_sets", "LevelSets", "isosurfaces", "Isosurfaces", "flow_lines", "FlowLines",
     "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
     "dirichlet_on", "neumann_load", "NeumannLoad",
     "interior", "InteriorFacets", "estimate", "ErrorIndicators", "mark", "refine_triangles", "adapt",
@@ -2406,6 +2406,119 @@ def isosurfaces(obj, levels, u=0, z=None, refine=0, triangles=True) -> Isosurfac
             call("mgb_levelset_destroy", h)
     k = round(geometry.discretization["block"] ** (1.0 / 3.0)) - 1
     return Isosurfaces(lv[0].item() if scalar else lv, rows, counts, ts, (ts is None, scalar), k, int(refine), offsets, tri, item)
+
+
+# --------------------------------------------------------------------------- flow lines of solutions
+
+
+class FlowLines:
+    """Result of flow_lines(): per seed `status` (one of EXIT, STALLED, MAXSTEPS, OUTSIDE, NONFINITE), `count` = the points
+    recorded (the seed included), `length` = the arc length, `time` = int ds / |sigma| along the line, `start_value` and
+    `end_value` = u at the seed and at the end point, `end` (dim) the end point and `end_element` its element.  Shapes (m,) and
+    (m, dim) for one field; an axis of len(ts) in front for a ParabolicSOL (whose `ts` is carried).  `rows` is the (B, m, 4) table
+    of the C ABI, `ds` the step that was taken.  `path(i, b)` gives the (count, dim) points of seed i in field b and
+    `elements(i, b)` the element of each."""
+
+    EXIT, STALLED, MAXSTEPS, OUTSIDE, NONFINITE = 0, 1, 2, 3, 4
+
+    def __init__(self, rows, end, status, count, end_element, ts, ds, offsets=None, pts=None, elem=None):
+        self.rows, self.ts, self.ds = rows, ts, ds
+        self._offsets, self._pts, self._elem = offsets, pts, elem
+        self._shape = status.shape      # (B, m)
+        shape = (lambda a: a[0]) if ts is None else (lambda a: a)
+        self.status, self.count, self.end_element, self.end = shape(status), shape(count), shape(end_element), shape(end)
+        self.length, self.time, self.start_value, self.end_value = (shape(rows[:, :, k].copy()) for k in range(4))
+
+    def _row(self, i, b, who):
+        B, m = self._shape
+        if self._offsets is None:
+            raise ValueError("FlowLines.%s: flow_lines was called with paths=False" % who)
+        for v, n, name in ((i, m, "seed"), (b, B, "field")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -n <= v < n:
+                raise IndexError("FlowLines.%s: %s = %r is not one of %d" % (who, name, v, n))
+        r = (int(b) % B) * m + int(i) % m
+        return int(self._offsets[r]), int(self._offsets[r + 1])
+
+    def path(self, i, b=0) -> np.ndarray:
+        a, e = self._row(i, b, "path")
+        return self._pts[a:e].copy()
+
+    def elements(self, i, b=0) -> np.ndarray:
+        a, e = self._row(i, b, "elements")
+        return self._elem[a:e].copy()
+
+    def __repr__(self):
+        return "FlowLines(m=%d, ds=%r, status=%r, length=%r)" % (self._shape[1], self.ds, self.status, self.length)
+
+
+def flow_lines(obj, seeds, p=2.0, u=0, z=None, direction=+1, ds=None, max_steps=1024, gmin=1e-12, paths=True,
+               workgroup=None) -> FlowLines:
+    """The curves that the flux sigma = |grad u|^(p-2) grad u of a solution follows, traced on the device from `seeds` (m, dim)
+    by the midpoint rule in arc length (csrc/flowline.hip; the rule is in include/mgb_hip.h and DESIGN.md section 4q): where a
+    particle released at a seed leaves the domain, what it passes through, the length of its path and its travel time
+    int ds / |sigma|.  `obj`, `u` and `z` as in level_sets(); all snapshots of a ParabolicSOL are traced by ONE launch.  `p`: a
+    finite scalar >= 1, it enters the time only.  `direction`: +1 up the gradient, -1 down.  `ds`: the step (None: a quarter of
+    the smallest element extent); a line stops after `max_steps` steps, where |grad u| <= gmin, at a non-finite value, or where
+    it leaves the mesh (the exit point is found by bisection).  `paths=False` leaves out the points -- no path buffer, one launch
+    and one copy less.  `workgroup`: 64, 128 or 256 threads (None: the measured default); the result does not depend on it.
+    2-D and 3-D geometries; a 1-D one raises ValueError."""
+    geometry, fields, ts = _level_fields("flow_lines", obj, z)
+    dim = geometry.discretization["dim"]
+    if dim == 1:
+        raise ValueError("flow_lines: a 2-D or 3-D geometry is needed, got 1-D")
+    if callable(p):
+        raise TypeError("flow_lines: p must be a scalar (a variable exponent is not covered)")
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        raise TypeError("flow_lines: p must be a scalar, got %r" % (p,))
+    if not (math.isfinite(p) and p >= 1.0):
+        raise ValueError("flow_lines: p must be finite and >= 1, got %r" % (p,))
+    if isinstance(direction, bool) or direction not in (1, -1):
+        raise ValueError("flow_lines: direction must be +1 or -1, got %r" % (direction,))
+    if isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or max_steps < 1:
+        raise ValueError("flow_lines: max_steps must be an int >= 1, got %r" % (max_steps,))
+    gmin = float(gmin)
+    if not (math.isfinite(gmin) and gmin >= 0.0):
+        raise ValueError("flow_lines: gmin must be finite and >= 0, got %r" % (gmin,))
+    if ds is not None:
+        ds = float(ds)
+        if not (math.isfinite(ds) and ds > 0.0):
+            raise ValueError("flow_lines: ds must be finite and > 0, got %r" % (ds,))
+    if workgroup not in (None, 64, 128, 256):
+        raise ValueError("flow_lines: workgroup must be 64, 128 or 256, got %r" % (workgroup,))
+    pts = f64(np.asarray(_to_cpu_array(seeds)))
+    if pts.ndim != 2 or pts.shape[1] != dim:
+        raise ValueError("flow_lines: seeds must have shape (m, %d), got %r" % (dim, tuple(pts.shape)))
+    m = pts.shape[0]
+    loc, backend = _locator_of(geometry)
+    vecs = [_nodal_values(geometry, zk, backend, "flow_lines") for zk in fields]
+    B, S = len(vecs), vecs[0][1]
+    if any(Sk != S for _, Sk in vecs):
+        raise ValueError("flow_lines: the snapshots have different numbers of columns")
+    if B > 65535:
+        raise ValueError("flow_lines: at most 65535 fields per call")
+    u = _energy_column(u, S, "u", "flow_lines")
+    if B * m > 2 ** 31 - 1 or (paths and B * m * (int(max_steps) + 2) * dim > 2 ** 31 - 1):
+        raise ValueError("flow_lines: the path buffer of B m (max_steps + 2) dim doubles has more than 2^31 - 1 entries")
+    table = (C.c_void_p * B)(*[v.handle.value for v, _ in vecs])
+    rows, end = np.empty((B, m, 4)), np.empty((B, m, dim))
+    status, count, end_element = (np.empty((B, m), dtype=np.int32) for _ in range(3))
+    ds_in, ds_used = (None if ds is None else C.c_double(ds)), C.c_double(0.0)
+    h = C.c_void_p()
+    call("mgb_geo_flow_lines", loc, B, table, S, u, m, dptr(pts), p, int(direction),
+         None if ds_in is None else C.cast(C.byref(ds_in), _lib.c_dbl_p), int(max_steps), gmin, int(workgroup or 0), dptr(rows),
+         dptr(end), iptr(status), iptr(count), iptr(end_element), C.cast(C.byref(ds_used), _lib.c_dbl_p),
+         C.byref(h) if paths else None)
+    offsets = ppts = pelem = None
+    if paths:
+        try:
+            total = int(count.sum())
+            offsets, ppts, pelem = np.empty(B * m + 1, dtype=np.int64), np.empty((total, dim)), np.empty(total, dtype=np.int32)
+            call("mgb_flowpath_get", h, offsets.ctypes.data_as(_lib.c_ll_p), dptr(ppts), iptr(pelem))
+        finally:
+            call("mgb_flowpath_destroy", h)
+    return FlowLines(rows, end, status, count, end_element, ts, ds_used.value, offsets, ppts, pelem)
 
 
 # --------------------------------------------------------------------------- boundary facets and boundary integrals

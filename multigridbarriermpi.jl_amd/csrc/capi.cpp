@@ -14,6 +14,7 @@
 #include "isosurface.hpp"
 #include "energy.hpp"
 #include "estimate.hpp"
+#include "flowline.hpp"
 #include "levelset.hpp"
 #include "mixed.hpp"
 #include "norms.hpp"
@@ -60,6 +61,17 @@ struct mgb_locator_s {
   DevBuf<double> ls_scratch, ls_levels;            // mgb_geo_level_sets: partials, results and totals; the levels of the call
   DevBuf<long long> ls_counts, ls_row_base;        // ... per-workgroup counts and offsets; the first slot of every row
   DevBuf<const double*> ls_table;                  // ... and the device table of field pointers, uploaded per call
+  DevBuf<double> fl_seeds, fl_out, fl_pts;         // mgb_geo_flow_lines: seeds; rows and end points; the fixed-stride paths
+  DevBuf<int32_t> fl_int, fl_pelem;                // ... status, count, end element; the elements of the path points
+  DevBuf<long long> fl_offsets;                    // ... the first point of every row in the compacted paths
+  DevBuf<const double*> fl_table;                  // ... and the device table of field pointers, uploaded per call
+};
+struct mgb_flowpath_s {
+  mgb_ctx_s* ctx;
+  int dim;
+  std::vector<long long> offsets;                  // B m + 1
+  DevBuf<double> pts;                              // total x dim
+  DevBuf<int32_t> elem;                            // total
 };
 struct mgb_levelset_s {
   mgb_ctx_s* ctx;
@@ -1596,6 +1608,137 @@ int mgb_geo_level_sets_host(mgb_geo g, int B, const double* const* z, int S, int
     A.levels = levels;
     A.nel = L.nel, A.S = S, A.u = u, A.B = B, A.nl = nl, A.refine = refine;
     levelset::level_sets_host(L.dim, A, out, counts, row_offsets, seg, item, capacity);
+  });
+}
+
+// ---- flow lines of nodal fields (flowline.hpp / flowline.hip)
+namespace {
+// the arguments both entry points take alike, checked by flowline::check before anything is launched or written
+void flow_args(flowline::Args& A, const char* who, int dim, int B, int S, int u, int m, double p, int direction,
+               const double* ds_or_null, double min_extent, int max_steps, double gmin, bool paths) {
+  if (dim == 1) throw std::invalid_argument(std::string(who) + ": flow lines need a 2-D or 3-D geometry");
+  A.p = p, A.gmin = gmin;
+  A.ds = ds_or_null ? *ds_or_null : 0.25 * min_extent;
+  A.sgn = direction == 1 ? 1.0 : direction == -1 ? -1.0 : 0.0;
+  A.m = m, A.S = S, A.u = u, A.B = B, A.max_steps = max_steps;
+  A.stride = (long long)max_steps + 2;
+  flowline::check(A, dim, paths);
+}
+}  // namespace
+int mgb_geo_flow_lines(mgb_locator loc, int B, const mgb_vec* z, int S, int u, int m, const double* seeds_host, double p,
+                       int direction, const double* ds_or_null, int max_steps, double gmin, int workgroup, double* rows_host,
+                       double* end_host, int32_t* status_host, int32_t* count_host, int32_t* end_element_host, double* ds_used,
+                       mgb_flowpath* paths) {
+  return guard([&] {
+    need(loc && z, "geo_flow_lines: null argument");
+    const interp::Locator& L = loc->loc;
+    flowline::Args A{};
+    flow_args(A, "geo_flow_lines", L.dim, B, S, u, m, p, direction, ds_or_null, L.min_extent, max_steps, gmin,
+              paths != nullptr);
+    need(workgroup == 0 || workgroup == 64 || workgroup == 128 || workgroup == 256,
+         "geo_flow_lines: the workgroup size is 0 (default), 64, 128 or 256");
+    need(loc->ctx->ctx.world == 1, "geo_flow_lines: sharded contexts are not supported");
+    std::vector<const double*> table;
+    field_table("geo_flow_lines", loc, B, z, S, table);
+    need(m == 0 || (seeds_host && rows_host && end_host && status_host && count_host && end_element_host),
+         "geo_flow_lines: null array");
+    if (ds_used) *ds_used = A.ds;
+    const int dim = L.dim;
+    const size_t rows = (size_t)B * m;
+    std::unique_ptr<mgb_flowpath_s> out;
+    if (paths) {
+      out.reset(new mgb_flowpath_s{loc->ctx, dim, {}, {}, {}});
+      out->offsets.assign(rows + 1, 0);
+    }
+    if (m == 0) {
+      if (paths) *paths = out.release();
+      return;
+    }
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const size_t nout = rows * (flowline::kRowCols + dim);
+    if (loc->fl_out.n < nout) loc->fl_out.alloc(nout);
+    if (loc->fl_int.n < 3 * rows) loc->fl_int.alloc(3 * rows);
+    if (paths) {
+      const size_t slots = rows * (size_t)A.stride;
+      if (loc->fl_pts.n < slots * dim) loc->fl_pts.alloc(slots * dim);
+      if (loc->fl_pelem.n < slots) loc->fl_pelem.alloc(slots);
+    }
+    loc->fl_table.upload(table.data(), table.size());      // every earlier launch that read these has been waited for
+    loc->fl_seeds.upload(seeds_host, (size_t)m * dim);
+    A.own = L.view(loc->cellptr.p, loc->cellelem.p, loc->x.p);
+    A.z = loc->fl_table.p;
+    A.seeds = loc->fl_seeds.p;
+    A.rows = loc->fl_out.p;
+    A.end = loc->fl_out.p + rows * flowline::kRowCols;
+    A.status = loc->fl_int.p;
+    A.count = loc->fl_int.p + rows;
+    A.end_element = loc->fl_int.p + 2 * rows;
+    A.pts = paths ? loc->fl_pts.p : nullptr;
+    A.pelem = paths ? loc->fl_pelem.p : nullptr;
+    flowline::launch_trace(st, dim, L.k, A, workgroup ? workgroup : flowline::kDefaultWorkgroup);
+    hip_check(hipGetLastError(), "geo_flow_lines launch");
+    hip_check(hipStreamSynchronize(st), "sync geo_flow_lines");
+    std::vector<double> dbl(nout);
+    std::vector<int32_t> ints(3 * rows);
+    hip_check(hipMemcpy(dbl.data(), loc->fl_out.p, nout * sizeof(double), hipMemcpyDeviceToHost), "D2H");
+    hip_check(hipMemcpy(ints.data(), loc->fl_int.p, 3 * rows * sizeof(int32_t), hipMemcpyDeviceToHost), "D2H");
+    std::copy(dbl.begin(), dbl.begin() + rows * flowline::kRowCols, rows_host);
+    std::copy(dbl.begin() + rows * flowline::kRowCols, dbl.end(), end_host);
+    std::copy(ints.begin(), ints.begin() + rows, status_host);
+    std::copy(ints.begin() + rows, ints.begin() + 2 * rows, count_host);
+    std::copy(ints.begin() + 2 * rows, ints.end(), end_element_host);
+    if (!paths) return;
+    for (size_t r = 0; r < rows; ++r) {
+      if (count_host[r] < 0 || count_host[r] > A.stride) throw InternalError("geo_flow_lines: a count outside its row");
+      out->offsets[r + 1] = out->offsets[r] + count_host[r];
+    }
+    const long long total = out->offsets[rows];
+    if (total > 0) {
+      out->pts.alloc((size_t)total * dim);
+      out->elem.alloc((size_t)total);
+      loc->fl_offsets.upload(out->offsets.data(), rows + 1);
+      flowline::launch_compact(st, dim, A, loc->fl_offsets.p, out->pts.p, out->elem.p);
+      hip_check(hipGetLastError(), "geo_flow_lines compact launch");
+      hip_check(hipStreamSynchronize(st), "sync geo_flow_lines compact");
+    }
+    *paths = out.release();
+  });
+}
+int mgb_flowpath_get(mgb_flowpath paths, long long* offsets, double* pts, int32_t* elem) {
+  return guard([&] {
+    need(paths != nullptr, "flowpath_get: null argument");
+    hip_check(hipSetDevice(paths->ctx->ctx.device), "hipSetDevice");
+    if (offsets) std::copy(paths->offsets.begin(), paths->offsets.end(), offsets);
+    if (pts) paths->pts.download(pts, paths->pts.n);
+    if (elem) paths->elem.download(elem, paths->elem.n);
+  });
+}
+int mgb_flowpath_destroy(mgb_flowpath paths) {
+  return guard([&] { delete paths; });
+}
+int mgb_geo_flow_lines_host(mgb_geo g, int B, const double* const* z, int S, int u, int m, const double* seeds, double p,
+                            int direction, const double* ds_or_null, int max_steps, double gmin, double* rows, double* end,
+                            int32_t* status, int32_t* count, int32_t* end_element, double* ds_used, long long* offsets,
+                            double* pts, int32_t* elem, long long capacity) {
+  return guard([&] {
+    need(g && z, "geo_flow_lines_host: null argument");
+    need(g->g.dim != 1, "geo_flow_lines_host: flow lines need a 2-D or 3-D geometry");
+    const interp::Locator L = interp::build_locator(g->g);
+    flowline::Args A{};
+    flow_args(A, "geo_flow_lines_host", L.dim, B, S, u, m, p, direction, ds_or_null, L.min_extent, max_steps, gmin,
+              offsets != nullptr);
+    for (int b = 0; b < B; ++b) need(z[b] != nullptr, "geo_flow_lines_host: null field");
+    need(m == 0 || (seeds && rows && end && status && count && end_element), "geo_flow_lines_host: null array");
+    need((offsets == nullptr) == (pts == nullptr) && (offsets == nullptr) == (elem == nullptr),
+         "geo_flow_lines_host: offsets, points and elements come together");
+    need(!offsets || capacity >= 0, "geo_flow_lines_host: negative capacity");
+    if (ds_used) *ds_used = A.ds;
+    A.own = L.view(L.cellptr.data(), L.cellelem.data(), g->g.x.data());
+    A.z = z;
+    A.seeds = seeds;
+    A.rows = rows, A.end = end, A.status = status, A.count = count, A.end_element = end_element;
+    flowline::flow_lines_host(L.dim, L.k, A, offsets, pts, elem, capacity);
   });
 }
 

@@ -277,6 +277,7 @@ struct Locator {
   int dim = 0, block = 0, n = 0, nel = 0, k = 0;      // k: degree of the tensor elements (0 in 2-D)
   int nc[3] = {1, 1, 1};
   double lo[3] = {0, 0, 0}, inv[3] = {0, 0, 0};
+  double min_extent = 0.0;      // the smallest element extent: the largest side of an element's bounding box (flowline.hpp's default step)
   std::vector<int> cellptr, cellelem;
   BinsView view(const int* ptr, const int* el, const double* x) const {
     BinsView B;
@@ -355,6 +356,20 @@ inline Locator build_locator(const GeometryHost& g) {
   L.nel = g.n / g.block;
   L.k = k;
   validate_elements(g, k);
+  L.min_extent = std::numeric_limits<double>::infinity();
+  for (int e = 0; e < L.nel; ++e) {
+    const double* v = x + (size_t)e * L.block * dim;
+    double ext = 0.0;
+    for (int d = 0; d < dim; ++d) {
+      double bl = v[d], bh = v[d];
+      for (int q = 1; q < L.block; ++q) {
+        bl = std::min(bl, v[(size_t)q * dim + d]);
+        bh = std::max(bh, v[(size_t)q * dim + d]);
+      }
+      ext = std::max(ext, bh - bl);
+    }
+    L.min_extent = std::min(L.min_extent, ext);
+  }
   double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, amax = 0.0;
   for (int d = 0; d < dim; ++d) lo[d] = hi[d] = x[d];
   for (int q = 0; q < g.n; ++q)
