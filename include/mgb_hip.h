@@ -547,12 +547,14 @@ int mgb_geo_field_flux(mgb_locator loc, mgb_vec z, int S, int u, double p, mgb_v
  * context; more than INT_MAX items per row; a 3-D geometry. */
 #define MGB_LEVELSET_COLS 5
 typedef struct mgb_levelset_s* mgb_levelset;   /* the emitted segments of one call, device resident; a handle made by
-                                                * mgb_geo_isosurfaces (below) holds triangles instead: rows of 9 doubles */
+                                                * mgb_geo_isosurfaces (below) holds triangles instead: rows of 9 doubles;
+                                                * one made by mgb_geo_sections the pieces of cuts: rows of 6 or 12 doubles */
 int mgb_geo_level_sets(mgb_locator loc, int B, const mgb_vec* z /* B vectors of n x S */, int S, int u, int nl,
                        const double* levels_host, int refine, double* out_host /* B nl x MGB_LEVELSET_COLS */,
                        long long* counts_host /* B nl */, mgb_levelset* segs_or_null);
 /* copies to the host, each where non-null: row_offsets (B nl + 1, the total last), seg (total x 4, 1-D: total x 2; a handle of
- * mgb_geo_isosurfaces: total x 9, x0 y0 z0 x1 y1 z1 x2 y2 z2), item (total) */
+ * mgb_geo_isosurfaces: total x 9, x0 y0 z0 x1 y1 z1 x2 y2 z2; a handle of mgb_geo_sections: total x 6 or total x 12), item
+ * (total) */
 int mgb_levelset_get(mgb_levelset segs, long long* row_offsets, double* seg, int32_t* item);
 int mgb_levelset_destroy(mgb_levelset segs);
 /* host restatement (no context, no GPU): the same per-item routine on host arrays, row after row, summed serially in ascending
@@ -625,6 +627,82 @@ int mgb_geo_isosurfaces_host(mgb_geo g, int B, const double* const* z /* B array
                              const double* levels, int refine, double* out /* B nl x MGB_LEVELSET_COLS */,
                              long long* counts /* B nl */, long long* row_offsets_or_null, double* tri_or_null,
                              int32_t* item_or_null, long long capacity);
+
+/* ---- plane sections of nodal fields: cuts, means, flow rates -------------------------------------------------------------- *
+ * What a field looks like on the cut of the domain by a plane n . x = c (a line in 2-D), and how much flows through it: per
+ * field and plane the measure of the cut, int u over it, the flow rate int sigma . nu with sigma = |grad u|^(p-2) grad u and
+ * nu = n / |n|, the extrema of u over the quadrature points, and the cut itself as oriented pieces with the values of u at
+ * their vertices.  B fields (n x S, row-major, column u) on one 2-D (block 7) or 3-D (block (k+1)^3, k = 1..3) geometry, nc
+ * planes, one exponent p per call; single-GPU contexts, fp64.  Row r = b nc + l of every output belongs to field b and
+ * plane l.  (csrc/section.hpp is the rule, run by the gfx950 kernels and by the host restatement.)
+ *   Planes.  Row l of planes is (n_0 .. n_{dim-1}, c): dim + 1 doubles.  The side function is
+ *     d(x) = (n_0 x_0 + n_1 x_1 [+ n_2 x_2]) - c, the products summed in that order, then c subtracted.  A corner is ABOVE
+ *     when d > 0, by comparison only.  nu_a = n_a / sqrt(n_0^2 + n_1^2 [+ n_2^2]).  A crossing is the level sets': on an edge
+ *     with one corner above and one not, ALWAYS from the below corner to the above corner, t = (0 - d_lo) / (d_hi - d_lo),
+ *     Q = P_lo + t (P_hi - P_lo): the elements on both sides of an edge or a face compute the same bits.
+ *   The elements are straight-sided triangles and axis-aligned boxes (what mgb_geo_interpolate assumes), so the plane cuts an
+ *     element in an exact segment or polygon and u on the cut is a polynomial: no refinement exists here.
+ *   2-D.  One item per element, item = e; corners: the local rows 0, 1, 2, coordinates loaded.  With 0 or 3 corners above the
+ *     item contributes nothing.  Else L = the lone corner (the one above, or the one not above), o1 = (L + 1) % 3,
+ *     o2 = (o1 + 1) % 3, Q0 and Q1 the crossings on the edges L - o1 and L - o2.  Where Q0 and Q1 are the same point (both
+ *     coordinates compare equal) the item contributes nothing.  The segment is (Q0, Q1), exchanged when
+ *     cross(Q1 - Q0, P_above - Q0) < 0 (P_above = P_L for one corner above, P_o1 for two): the above side lies to its LEFT.
+ *     An element edge that lies in the line is so cut by the element on its above side alone.
+ *     Quadrature: 4-point Gauss-Legendre, x_q = S0 + s_q (S1 - S0) per coordinate, weight w_q |S1 - S0|, in ascending q; u on
+ *     a line through a P2 + bubble element is a cubic, so int u is exact up to rounding.
+ *   3-D.  item = e 6 + t.  The box of element e is spanned by its eight corner nodes (local node K a + (K+1)(K b + (K+1) K c)
+ *     for the corner (a, b, c) in {0,1}^3), loaded and never recomputed; it is cut into the six Kuhn tetrahedra of
+ *     mgb_geo_isosurfaces (corners O, O + e_p0, O + e_p0 + e_p1, O + (1,1,1) for the t-th permutation of the axes).  Every box
+ *     is cut the same way, so neighbours agree on every face diagonal.  Cases and orientation are those of the isosurfaces,
+ *     applied to d with the level 0: one or three corners above give the triangle (Q1, Q2, Q3) of the crossings at the lone
+ *     corner; two above give the quadrilateral Q00 Q01 Q11 Q10 split along Q01 - Q10 into (Q00, Q01, Q10) and (Q01, Q11, Q10).
+ *     A triangle two of whose vertices are the same point is dropped: it contributes nothing.  Every other triangle is
+ *     oriented so that (P1 - P0) x (P2 - P0) points to the BELOW side (towards -n).  A face of a tetrahedron that lies exactly
+ *     in the plane is emitted by the tetrahedron whose fourth corner is above, so exactly once; values and gradients on such
+ *     a face therefore come from the element on the ABOVE side (for a broken field the two sides differ).
+ *     Quadrature on each emitted triangle (P0, P1, P2): the collapsed tensor Gauss-Legendre rule with n_K x n_K points,
+ *     n_K = 3, 4, 6 for k = 1, 2, 3; point (i, j), i outer, both ascending: b0 = 1 - s_i, b1 = s_i (1 - s_j), b2 = s_i s_j,
+ *     x = (b0 P0 + b1 P1) + b2 P2 per coordinate, weight ((w_i w_j) s_i) (2 area), area = |(P1 - P0) x (P2 - P0)| / 2.  The
+ *     rule is exact for total degree 2 n_K - 2 >= 3 k, the degree of a Q_k function on a plane.
+ *   Gauss nodes and weights on [0, 1] are the 17-digit constants of csrc/section.hpp.
+ *   At a quadrature point x_q of an item of element e: v and g = value and physical gradient of column u of e's own polynomial
+ *     (the bases and the operations of mgb_geo_flow_lines' val and grad; no locator is involved).  sigma = a^(p-2) g with
+ *     a = |g|_2: g itself (bit for bit) at p = 2, g / a at p = 1, pow(a, p - 2) g otherwise, exactly 0 where a = 0.
+ *     sigma . nu is summed over the axes in ascending order.
+ * Per (field, plane) one row of MGB_LEVELSET_COLS doubles
+ *   [0] sum w: the measure of the cut      [1] sum w v: int u      [2] sum w (sigma . nu): the flow rate in the direction of n
+ *   [3] max v      [4] max (-v)      -- over the quadrature points; NaN-sticky, both started from -inf
+ * and one long long, the number of emitted pieces.  The sums of a piece run in ascending point order from 0, those of an item
+ * in piece order.  An item the plane does not cut reads no field value: a NaN in an uncut element is not seen.  A cut item
+ * with a non-finite v or g at any quadrature point gives NaN in all five columns of its row and emits nothing; other rows stay
+ * bit for bit.  A plane that cuts nothing gives 0, 0, 0, -inf, -inf and the count 0.
+ * Pieces.  One row per emitted piece, in ascending item order within a row (the two triangles of an item adjacent), rows in
+ * ascending order: 2-D 6 doubles x0 y0 x1 y1 | u0 u1, 3-D 12 doubles x0 y0 z0 x1 y1 z1 x2 y2 z2 | u0 u1 u2, u_m = the value
+ * of the element's polynomial at vertex m (what a slice plot colours by), and the int32 item.  They come back through the
+ * level sets' handle: mgb_levelset carries its row width, mgb_levelset_get copies total x 6 or total x 12 doubles for a handle
+ * made here and keeps its behaviour for every other handle; mgb_levelset_destroy frees it.
+ * Launches, as for the isosurfaces: the measure on a grid (ceil(items / 256), nc, B) of 256 threads, one item per thread, one
+ * partial row and one count (0..2 per thread) per workgroup; the SAME finish launch; rows and counts in ONE copy.  With
+ * pieces non-null a third launch on the measure's grid recomputes every item, ranks it by the exclusive prefix sum of the
+ * counts in its workgroup and writes its pieces to slot row offset + workgroup offset + rank (and the next).  No atomics: a
+ * call repeated returns the same bits, a row does not depend on B, nc or its place in the batch.  The per-item arithmetic is
+ * compiled with fp contraction off on both sides; device and host restatement differ in the order of the three sums and, for
+ * p other than 1 and 2, in pow.
+ * MGB_E_ARG, before anything is launched: a null argument or field; a 1-D geometry (the message names interpolate); 3-D
+ * elements other than (k+1)^3 nodes, k = 1..3; B < 1, nc < 1, B or nc > 65535 (device); B nc or the items per row beyond
+ * INT_MAX; S < 1; u outside [0, S); a plane whose normal is zero or not finite or whose c is not finite; p not a finite real
+ * >= 1 (one scalar per call: an exponent field p(x) is not supported); vectors of the wrong length or of another context; a
+ * sharded context. */
+int mgb_geo_sections(mgb_locator loc, int B, const mgb_vec* z /* B vectors of n x S */, int S, int u, int nc,
+                     const double* planes_host /* nc x (dim + 1) */, double p, double* out_host /* B nc x MGB_LEVELSET_COLS */,
+                     long long* counts_host /* B nc */, mgb_levelset* pieces_or_null);
+/* host restatement (no context, no GPU), shaped like mgb_geo_isosurfaces_host: serial, ascending item order, the three sums
+ * compensated (Neumaier); piece_or_null (capacity x 6 or 12) and item_or_null come together, MGB_E_ARG when more pieces are
+ * emitted (call once without them, size them by the counts, call again). */
+int mgb_geo_sections_host(mgb_geo g, int B, const double* const* z /* B arrays of n x S */, int S, int u, int nc,
+                          const double* planes /* nc x (dim + 1) */, double p, double* out /* B nc x MGB_LEVELSET_COLS */,
+                          long long* counts /* B nc */, long long* row_offsets_or_null, double* piece_or_null,
+                          int32_t* item_or_null, long long capacity);
 
 /* ---- flow lines of nodal fields: paths, lengths, travel times ------------------------------------------------------------ *
  * The curves that follow grad u through the broken polynomial field of column u of B fields (n x S, row-major) on one 2-D

@@ -38,7 +38,7 @@ __all__ = [
     "_raw_array", "_to_cpu_array", "MGBError", "device_count", "AMG", "amg", "hcat", "BarrierFn", "barrier_functions",
     "interpolate", "sample_grid", "norms", "error", "convergence", "FieldNorms", "Convergence",
     "energy", "flux", "Energy", "level_sets", "LevelSets", "isosurfaces", "Isosurfaces", "flow_lines", "FlowLines",
-    "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
+    "sections", "Sections", "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
     "dirichlet_on", "neumann_load", "NeumannLoad",
     "interior", "InteriorFacets", "estimate", "ErrorIndicators", "mark", "refine_triangles", "adapt",
     "estimate_steps", "StepIndicators", "refine_times", "adapt_time",
@@ -2519,6 +2519,122 @@ def flow_lines(obj, seeds, p=2.0, u=0, z=None, direction=+1, ds=None, max_steps=
         finally:
             call("mgb_flowpath_destroy", h)
     return FlowLines(rows, end, status, count, end_element, ts, ds_used.value, offsets, ppts, pelem)
+
+
+# --------------------------------------------------------------------------- plane sections of solutions
+
+
+class Sections:
+    """Result of sections(): per field and plane `measure` = the length (2-D) or area (3-D) of the cut, `integral` = int u over
+    it, `mean` = integral / measure (NaN for an empty cut), `flux` = int sigma . nu, the flow rate in the direction of n, `max`
+    and `min` = the extrema of u over the quadrature points (-inf and +inf for an empty cut), `count` = the number of pieces,
+    `hit` = the plane cuts something (true also where every cut item holds a non-finite value: the row is NaN, `count` 0).  Floats for one field and one plane; an axis of len(ts) in front for a ParabolicSOL
+    (whose `ts` is carried), an axis of len(planes) behind for an array of planes.  `rows` is the (B, nc, 5) table of the C ABI.
+    `pieces(plane, field)` gives the (m, 2, 2) segments (the side n points to on their left) or the (m, 3, 3) triangles
+    ((P1 - P0) x (P2 - P0) pointing against n) of planes[plane] in snapshot `field`, in ascending item order, `values(plane,
+    field)` the (m, 2) or (m, 3) values of u at their vertices, `items(plane, field)` the item of each piece (an item with two
+    triangles occurs twice) and `elements(plane, field)` its element."""
+
+    def __init__(self, planes, rows, counts, ts, squeeze, dim, offsets=None, piece=None, item=None):
+        self.planes, self.rows, self.ts, self.dim = planes, rows, ts, dim
+        self._counts, self._offsets, self._piece, self._item = counts, offsets, piece, item
+
+        def shape(a):
+            a = a[:, 0] if squeeze[1] else a
+            a = a[0] if squeeze[0] else a
+            return a if np.ndim(a) else a.item()
+
+        self.measure, self.integral, self.flux, self.max = (shape(rows[:, :, j].copy()) for j in range(4))
+        self.min = shape(-rows[:, :, 4])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.mean = shape(np.where(counts > 0, rows[:, :, 1] / rows[:, :, 0], np.nan))
+        self.count = shape(counts.copy())
+        self.hit = shape((counts > 0) | np.isnan(rows[:, :, 0]))      # a row poisoned by a non-finite node was cut, whatever it emitted
+
+    def _row(self, plane, field, who):
+        B, nc = self._counts.shape
+        if self._offsets is None:
+            raise ValueError("Sections.%s: sections was called with pieces=False" % who)
+        for v, m, name in ((plane, nc, "plane"), (field, B, "field")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -m <= v < m:
+                raise IndexError("Sections.%s: %s = %r is not one of %d" % (who, name, v, m))
+        r = (int(field) % B) * nc + int(plane) % nc
+        return int(self._offsets[r]), int(self._offsets[r + 1])
+
+    def pieces(self, plane=0, field=0) -> np.ndarray:
+        a, b = self._row(plane, field, "pieces")
+        d = self.dim
+        return self._piece[a:b, :d * d].reshape(-1, d, d).copy()
+
+    def values(self, plane=0, field=0) -> np.ndarray:
+        a, b = self._row(plane, field, "values")
+        return self._piece[a:b, self.dim * self.dim:].copy()
+
+    def items(self, plane=0, field=0) -> np.ndarray:
+        a, b = self._row(plane, field, "items")
+        return self._item[a:b].copy()
+
+    def elements(self, plane=0, field=0) -> np.ndarray:
+        a, b = self._row(plane, field, "elements")
+        return self._item[a:b] // (6 if self.dim == 3 else 1)
+
+    def __repr__(self):
+        return "Sections(measure=%r, integral=%r, flux=%r, count=%r)" % (self.measure, self.integral, self.flux, self.count)
+
+
+def sections(obj, planes, p=2.0, u=0, z=None, pieces=True) -> Sections:
+    """What a solution looks like on the cut of the domain by a plane n . x = c (a line in 2-D) and how much flows through it:
+    the exact cut of every element, its measure, int u, the mean, the flow rate int sigma . nu with sigma = |grad u|^(p-2)
+    grad u and nu = n / |n|, and the extrema of u, by a fixed Gauss rule that integrates the element polynomials exactly,
+    on the device (csrc/section.hip; the rule is in include/mgb_hip.h and DESIGN.md section 4r).  `obj`, `u` and `z` as in
+    level_sets(); all snapshots of a ParabolicSOL are cut by ONE set of launches.  `planes`: one row (n_0 .. n_{dim-1}, c) or
+    an (nc, dim + 1) array of them, n finite and not zero.  `p`: ONE finite scalar >= 1 (a callable or nodal p(x) is refused).
+    `pieces=False` leaves out the pieces -- one launch and one copy less -- for flow-rate histories.  A 1-D geometry raises
+    ValueError: interpolate() gives the value at a point."""
+    geometry, fields, ts = _level_fields("sections", obj, z)
+    dim = geometry.discretization["dim"]
+    if dim == 1:
+        raise ValueError("sections: a 2-D or 3-D geometry is needed, got 1-D; interpolate() gives the value at a point")
+    if callable(p) or isinstance(p, (HPCVector, HPCMatrix)) or np.ndim(p) != 0:
+        raise TypeError("sections: p must be one scalar per call (a callable or nodal exponent p(x) is not supported)")
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        raise TypeError("sections: p must be one scalar per call, got %r" % (p,))
+    if not (np.isfinite(p) and p >= 1.0):
+        raise ValueError("sections: p must be finite and >= 1, got %r" % (p,))
+    try:
+        pl = np.asarray(planes.to_numpy() if hasattr(planes, "to_numpy") else planes, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("sections: planes must be one row (n, c) or an (nc, %d) array of them" % (dim + 1))
+    single = pl.ndim == 1
+    pl = f64(pl.reshape(1, -1) if single else pl)
+    if pl.ndim != 2 or pl.shape[0] < 1 or pl.shape[1] != dim + 1:
+        raise ValueError("sections: planes must be one row (n, c) or an (nc, %d) array of them, got shape %r" % (dim + 1, tuple(pl.shape)))
+    if not np.all(np.isfinite(pl)) or not np.all(np.any(pl[:, :dim] != 0.0, axis=1)):
+        raise ValueError("sections: every plane needs a finite normal that is not zero and a finite c")
+    loc, backend = _locator_of(geometry)
+    vecs = [_nodal_values(geometry, zk, backend, "sections") for zk in fields]
+    B, S, nc = len(vecs), vecs[0][1], pl.shape[0]
+    if any(Sk != S for _, Sk in vecs):
+        raise ValueError("sections: the snapshots have different numbers of columns")
+    if B > 65535 or nc > 65535:
+        raise ValueError("sections: at most 65535 fields and 65535 planes per call")
+    u = _energy_column(u, S, "u", "sections")
+    table = (C.c_void_p * B)(*[v.handle.value for v, _ in vecs])
+    rows, counts = np.empty((B, nc, 5)), np.empty((B, nc), dtype=np.int64)
+    h = C.c_void_p()
+    call("mgb_geo_sections", loc, B, table, S, u, nc, dptr(pl), p, dptr(rows), counts.ctypes.data_as(_lib.c_ll_p),
+         C.byref(h) if pieces else None)
+    offsets = piece = item = None
+    if pieces:
+        try:
+            total = int(counts.sum())
+            offsets, piece, item = np.empty(B * nc + 1, dtype=np.int64), np.empty((total, 6 if dim == 2 else 12)), np.empty(total, dtype=np.int32)
+            call("mgb_levelset_get", h, offsets.ctypes.data_as(_lib.c_ll_p), dptr(piece), iptr(item))
+        finally:
+            call("mgb_levelset_destroy", h)
+    return Sections(pl[0].copy() if single else pl, rows, counts, ts, (ts is None, single), dim, offsets, piece, item)
 
 
 # --------------------------------------------------------------------------- boundary facets and boundary integrals

@@ -154,6 +154,9 @@ PROTOTYPES = {
     "mgb_geo_isosurfaces": [H, C.c_int, C.POINTER(H), C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_int, c_dbl_p, c_ll_p, C.POINTER(H)],
     "mgb_geo_isosurfaces_host": [H, C.c_int, C.POINTER(c_dbl_p), C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_int, c_dbl_p, c_ll_p, c_ll_p,
                                  c_dbl_p, c_i32_p, C.c_longlong],
+    "mgb_geo_sections": [H, C.c_int, C.POINTER(H), C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_double, c_dbl_p, c_ll_p, C.POINTER(H)],
+    "mgb_geo_sections_host": [H, C.c_int, C.POINTER(c_dbl_p), C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_double, c_dbl_p, c_ll_p, c_ll_p,
+                              c_dbl_p, c_i32_p, C.c_longlong],
     "mgb_geo_flow_lines": [H, C.c_int, C.POINTER(H), C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_double, C.c_int, c_dbl_p, C.c_int,
                            C.c_double, C.c_int, c_dbl_p, c_dbl_p, c_i32_p, c_i32_p, c_i32_p, c_dbl_p, C.POINTER(H)],
     "mgb_flowpath_get": [H, c_ll_p, c_dbl_p, c_i32_p],

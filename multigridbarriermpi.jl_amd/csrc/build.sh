@@ -45,6 +45,8 @@ compile "$HERE/_obj/levelset.o" "$HERE/levelset.hip" "$HIPCC" --offload-arch=gfx
 compile "$HERE/_obj/isosurface.o" "$HERE/isosurface.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS -ffp-contract=off
 # flowline.hip: the same for the flow lines (flowline.hpp on top of interp.hpp's locator and bases)
 compile "$HERE/_obj/flowline.o" "$HERE/flowline.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS -ffp-contract=off
+# section.hip: the same for the plane sections (section.hpp on top of levelset.hpp, isosurface.hpp and flowline.hpp)
+compile "$HERE/_obj/section.o" "$HERE/section.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS -ffp-contract=off
 compile "$HERE/_obj/boundary.o" "$HERE/boundary.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/estimate.o" "$HERE/estimate.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/parabolic.o" "$HERE/parabolic.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
@@ -57,5 +59,5 @@ for pid in "${pids[@]}"; do
   wait "$pid" || { echo "build.sh: a compile job failed" >&2; exit 1; }
 done
 rm -f "$OUT/libmgb_hip.so"
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,chol_premap,chol_plan,kernels,kernels_f32,mg,interp,reduce,norms,energy,levelset,isosurface,boundary,estimate,parabolic,gpuchol,amg,amg_mg,comm,capi,flowline}.o -lpthread -ldl
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,chol_premap,chol_plan,kernels,kernels_f32,mg,interp,reduce,norms,energy,levelset,isosurface,boundary,estimate,parabolic,gpuchol,amg,amg_mg,comm,capi,flowline,section}.o -lpthread -ldl
 echo "built $OUT/libmgb_hip.so"

@@ -18,6 +18,7 @@
 #include "levelset.hpp"
 #include "mixed.hpp"
 #include "norms.hpp"
+#include "section.hpp"
 
 using namespace mgb;
 
@@ -75,7 +76,8 @@ struct mgb_flowpath_s {
 };
 struct mgb_levelset_s {
   mgb_ctx_s* ctx;
-  int width;                                       // doubles per row: segments 4 in 2-D and 2 in 1-D, triangles (mgb_geo_isosurfaces) 9
+  int width;                                       // doubles per row: segments 4 in 2-D and 2 in 1-D, triangles (mgb_geo_isosurfaces) 9,
+                                                   // pieces of a cut (mgb_geo_sections) 6 in 2-D and 12 in 3-D
   std::vector<long long> row_offsets;              // B nl + 1
   DevBuf<double> seg;
   DevBuf<int32_t> item;
@@ -1825,6 +1827,83 @@ int mgb_geo_isosurfaces_host(mgb_geo g, int B, const double* const* z, int S, in
     A.levels = levels;
     A.nel = L.nel, A.S = S, A.u = u, A.B = B, A.nl = nl, A.refine = refine;
     isosurface::isosurfaces_host(L.k, A, out, counts, row_offsets, tri, item, capacity);
+  });
+}
+
+// ---- plane sections of nodal fields (section.hpp / section.hip); the buffers and the handle are the level sets'
+namespace {
+// what both entry points fill alike; section::check, the one place where these arguments are judged, runs on it at once
+void section_args(section::Args& A, const char* who, const interp::Locator& L, const double* x, int B, int S, int u, int nc, double p) {
+  A.own = L.view(nullptr, nullptr, x);
+  A.items = section::items_per_row(L.dim, L.nel);
+  A.p = p;
+  A.nel = L.nel, A.S = S, A.u = u, A.B = B, A.nc = nc;
+  section::check(who, A, L.dim, L.k);
+}
+}  // namespace
+int mgb_geo_sections(mgb_locator loc, int B, const mgb_vec* z, int S, int u, int nc, const double* planes_host, double p,
+                     double* out_host, long long* counts_host, mgb_levelset* pieces) {
+  return guard([&] {
+    need(loc && z && planes_host && out_host && counts_host, "geo_sections: null argument");
+    const interp::Locator& L = loc->loc;
+    need(B <= 65535 && nc <= 65535, "geo_sections: at most 65535 fields and 65535 planes per call");      // before any is read
+    section::Args A;
+    section_args(A, "geo_sections", L, loc->x.p, B, S, u, nc, p);
+    section::check_planes("geo_sections", L.dim, nc, planes_host);
+    need(loc->ctx->ctx.world == 1, "geo_sections: sharded contexts are not supported");
+    std::vector<const double*> table;
+    field_table("geo_sections", loc, B, z, S, table);
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const size_t rows = (size_t)B * nc, nwg = (size_t)reduce::workgroups(A.items);
+    const size_t nd = levelset::scratch_words(rows, nwg), nw = levelset::count_words(rows, nwg);
+    if (loc->ls_scratch.n < nd) loc->ls_scratch.alloc(nd);
+    if (loc->ls_counts.n < nw) loc->ls_counts.alloc(nw);
+    loc->ls_table.upload(table.data(), table.size());      // every earlier launch that read these has been waited for
+    loc->ls_levels.upload(planes_host, (size_t)nc * (L.dim + 1));
+    A.z = loc->ls_table.p;
+    A.planes = loc->ls_levels.p;
+    section::launch_measure(st, L.dim, L.k, A, loc->ls_scratch.p, loc->ls_counts.p);
+    hip_check(hipGetLastError(), "geo_sections launch");
+    hip_check(hipStreamSynchronize(st), "sync geo_sections");
+    // the rows and the totals lie behind each other: one copy
+    std::vector<double> both(rows * (reduce::kCols + 1));
+    hip_check(hipMemcpy(both.data(), loc->ls_scratch.p + levelset::results_offset(rows, nwg), both.size() * sizeof(double),
+                        hipMemcpyDeviceToHost), "D2H");
+    std::copy(both.begin(), both.begin() + rows * reduce::kCols, out_host);
+    std::memcpy(counts_host, both.data() + rows * reduce::kCols, rows * sizeof(long long));
+    if (!pieces) return;
+    std::unique_ptr<mgb_levelset_s> out(new mgb_levelset_s{loc->ctx, section::piece_width(L.dim), {}, {}, {}});
+    out->row_offsets.resize(rows + 1);
+    out->row_offsets[0] = 0;
+    for (size_t r = 0; r < rows; ++r) out->row_offsets[r + 1] = out->row_offsets[r] + counts_host[r];
+    const long long total = out->row_offsets[rows];
+    if (total > 0) {
+      out->seg.alloc((size_t)total * out->width);
+      out->item.alloc((size_t)total);
+      loc->ls_row_base.upload(out->row_offsets.data(), rows);
+      section::launch_emit(st, L.dim, L.k, A, loc->ls_counts.p + levelset::offsets_offset(rows, nwg), loc->ls_row_base.p, total,
+                           out->seg.p, out->item.p);
+      hip_check(hipGetLastError(), "geo_sections emit launch");
+      hip_check(hipStreamSynchronize(st), "sync geo_sections emit");
+    }
+    *pieces = out.release();
+  });
+}
+int mgb_geo_sections_host(mgb_geo g, int B, const double* const* z, int S, int u, int nc, const double* planes, double p,
+                          double* out, long long* counts, long long* row_offsets, double* piece, int32_t* item, long long capacity) {
+  return guard([&] {
+    need(g && z && planes && out && counts, "geo_sections_host: null argument");
+    const interp::Locator L = interp::build_locator(g->g);      // validates the blocks: straight triangles, tensor nodes of the corner box
+    section::Args A;
+    section_args(A, "geo_sections_host", L, g->g.x.data(), B, S, u, nc, p);
+    section::check_planes("geo_sections_host", L.dim, nc, planes);
+    for (int b = 0; b < B; ++b) need(z[b] != nullptr, "geo_sections_host: null field");
+    need((piece == nullptr) == (item == nullptr), "geo_sections_host: piece and item come together");
+    need(!piece || capacity >= 0, "geo_sections_host: negative capacity");
+    A.z = z;
+    A.planes = planes;
+    section::sections_host(L.dim, L.k, A, out, counts, row_offsets, piece, item, capacity);
   });
 }
 
