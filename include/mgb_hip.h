@@ -765,6 +765,64 @@ int mgb_geo_flow_lines_host(mgb_geo g, int B, const double* const* z /* B arrays
                             int32_t* count, int32_t* end_element, double* ds_used_or_null, long long* offsets_or_null,
                             double* pts_or_null, int32_t* elem_or_null, long long capacity);
 
+/* ---- path lines through a field that changes in time: tracers, streaklines ------------------------------------------------ *
+ * Where a particle released at a seed at snapshot time ts[release] is at ts[stop], what it passes through and when it leaves
+ * the domain: m particles carried through B >= 2 snapshots z_0 .. z_{B-1} (n x S, column u) of one 2-D or 3-D geometry at
+ * strictly increasing finite times ts[0 .. B-1], by the explicit midpoint rule in TIME.  (csrc/pathline.hpp is the rule, run
+ * by the gfx950 kernel and by the host restatement.)  Notation (val, grad, locate, |.|, sgn) as for mgb_geo_flow_lines.
+ * Field in time.  In slab j, [ts[j], ts[j+1]], at the fraction th, in element e at q: (v_a, g_a) = (val, grad) of z_j and
+ *   (v_b, g_b) of z_{j+1}, both at (e, q); v = v_a + th (v_b - v_a), g[d] = g_a[d] + th (g_b[d] - g_a[d]), as written.  Two
+ *   equal snapshots give bit for bit the stationary field; th = 0 gives snapshot j.  th is never formed from times: with
+ *   n = substeps it is (double) i / n at the start of step i of a slab and (double) (2 i + 1) / (2 n) at its midpoint.
+ * Velocity w(g), a = |g|: not a > gmin: w = 0, the particle rests (a NaN cannot pass this comparison).  Else
+ *   p == 1: w[d] = speed (sgn g[d] / a);  p == 2: w[d] = speed (sgn g[d]);  p == 1.5: w[d] = speed (sgn g[d] / sqrt(a));
+ *   otherwise w[d] = speed (sgn g[d] pow(a, p - 2)).  The first three use IEEE operations only.
+ * For seed x_0 with release index rel: e_0 = the lowest element that contains x_0; if there is none the status is OUTSIDE, the
+ * count 0, the end element -1, rested 0 and every double of the row NaN.  Otherwise the seed is recorded and for the slabs
+ * j = rel .. stop - 1, with dt = (ts[j+1] - ts[j]) / n, for i = 0 .. n - 1, t_k = ts[j] + i dt:
+ *   1. v, g at (x_k, e_k, th_i); at the very first step v is u_start.  Any of them non-finite: stop, NONFINITE.
+ *   2. q_m = x_k + (0.5 dt) w(g), e_m = locate(e_k, q_m).  e_m < 0: exit along x_k -> q_m with the time span 0.5 dt.
+ *   3. g_m at (q_m, e_m, th_mid).  Non-finite: stop, NONFINITE, at x_k.
+ *   4. q_n = x_k + dt w(g_m), e_n = locate(e_m, q_n).  e_n < 0: exit along x_k -> q_n with the time span dt.
+ *   5. s = dt |w(g_m)|; length += s; max_step = max(max_step, s); rested += 1 when w(g_m) was the zero of the rest rule;
+ *      x_{k+1} = q_n, e_{k+1} = e_n, and the point is recorded, a resting one too: the path is a time series.
+ * Exit along x_k -> q with span: the forty bisections of mgb_geo_flow_lines with locate from e_k; the end point
+ *   x_k + lo (q - x_k), in the remembered element, is recorded only if lo > 0; length += lo |q - x_k|; time = t_k + lo span;
+ *   u_end = the blended value there at th_i + lo span / (ts[j+1] - ts[j]); EXIT.
+ * After the last step: DONE, time = ts[stop], u_end = val(z_stop) at the end point, from that snapshot alone.  On NONFINITE
+ * time = t_k and u_end is the non-finite v, or NaN where only a gradient was non-finite.
+ * Per seed: MGB_PATH_COLS doubles [length, time, u_start, u_end, max_step]; the end point (dim doubles); int32 status, count
+ * (the points recorded, the seed included), end element and rested.  Every sum runs serially in step order; a row depends on its
+ * seed, its release index and the fields alone, not on m, the workgroup size or its place in the batch.
+ * workgroup: 0 (the default, 64), 64, 128 or 256 threads.  Launches: ONE, a grid ceil(m / workgroup), one thread per seed, no
+ * atomics, no LDS, no barrier; with paths_or_null non-null every thread records into its own row of
+ * (stop - min release) substeps + 2 slots, and the gather launch of mgb_geo_flow_lines fills the handle (mgb_flowpath_get /
+ * mgb_flowpath_destroy; offsets m + 1).  The rule is compiled with fp contraction off on both sides: device and host
+ * restatement agree bit for bit for p = 1, 1.5 and 2; for another p they differ by pow.
+ * MGB_E_ARG, before anything is allocated, launched or written: a null argument or field; a 1-D geometry; B < 2 or B > 65535;
+ * ts not finite or not strictly increasing; stop outside [1, B - 1]; a release index outside [0, stop); substeps < 1; p not
+ * finite or < 1; speed not finite or <= 0; gmin not finite or < 0; direction not +1 or -1; S < 1; u outside [0, S); m < 0;
+ * another workgroup size; vectors of the wrong length or of another context; a sharded context; with paths, m slots dim beyond
+ * 2^31 - 1.  m = 0 returns at once (an empty handle with paths). */
+#define MGB_PATH_COLS 5
+#define MGB_PATH_DONE 0
+#define MGB_PATH_EXIT 1
+#define MGB_PATH_OUTSIDE 2
+#define MGB_PATH_NONFINITE 3
+int mgb_geo_path_lines(mgb_locator loc, int B, const mgb_vec* z /* B vectors of n x S */, const double* ts_host /* B */, int S,
+                       int u, int m, const double* seeds_host /* m x dim */, const int32_t* release_host /* m */, int stop,
+                       int substeps, double p, int direction, double speed, double gmin, int workgroup,
+                       double* rows_host /* m x MGB_PATH_COLS */, double* end_host /* m x dim */, int32_t* status_host /* m */,
+                       int32_t* count_host /* m */, int32_t* end_element_host /* m */, int32_t* rested_host /* m */,
+                       mgb_flowpath* paths_or_null);
+/* host restatement (no context, no GPU): the same routine, row after row.  offsets_or_null (m + 1), pts_or_null
+ * (capacity x dim) and elem_or_null (capacity) come together; MGB_E_ARG when more points are recorded than they hold. */
+int mgb_geo_path_lines_host(mgb_geo g, int B, const double* const* z /* B arrays of n x S */, const double* ts /* B */, int S,
+                            int u, int m, const double* seeds /* m x dim */, const int32_t* release /* m */, int stop,
+                            int substeps, double p, int direction, double speed, double gmin, double* rows /* m x MGB_PATH_COLS */,
+                            double* end /* m x dim */, int32_t* status, int32_t* count, int32_t* end_element, int32_t* rested,
+                            long long* offsets_or_null, double* pts_or_null, int32_t* elem_or_null, long long capacity);
+
 /* ---- boundary facets of a geometry and boundary integrals of p-Laplace solutions --------------------------------------- *
  * The elements are broken and their quadrature is nodal: every node of a boundary facet is a row of x and z already, so the
  * boundary rule of a geometry is a list of nf facets of q nodes each: q global rows, q weights omega, the outward unit normal n,

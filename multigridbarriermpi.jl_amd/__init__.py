@@ -38,7 +38,7 @@ __all__ = [
     "_raw_array", "_to_cpu_array", "MGBError", "device_count", "AMG", "amg", "hcat", "BarrierFn", "barrier_functions",
     "interpolate", "sample_grid", "norms", "error", "convergence", "FieldNorms", "Convergence",
     "energy", "flux", "Energy", "level_sets", "LevelSets", "isosurfaces", "Isosurfaces", "flow_lines", "FlowLines",
-    "sections", "Sections", "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
+    "path_lines", "PathLines", "sections", "Sections", "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
     "dirichlet_on", "neumann_load", "NeumannLoad",
     "interior", "InteriorFacets", "estimate", "ErrorIndicators", "mark", "refine_triangles", "adapt",
     "estimate_steps", "StepIndicators", "refine_times", "adapt_time",
@@ -2519,6 +2519,178 @@ def flow_lines(obj, seeds, p=2.0, u=0, z=None, direction=+1, ds=None, max_steps=
         finally:
             call("mgb_flowpath_destroy", h)
     return FlowLines(rows, end, status, count, end_element, ts, ds_used.value, offsets, ppts, pelem)
+
+
+# --------------------------------------------------------------------------- path lines through parabolic runs
+
+
+class PathLines:
+    """Result of path_lines(): per seed `status` (one of DONE, EXIT, OUTSIDE, NONFINITE), `count` = the points recorded (the seed
+    included), `rested` = the accepted steps on which the particle did not move, `end` (dim) the end point, `end_element` its
+    element, `length` = the length of the path, `time` = the time at which it ended (ts[stop] for DONE), `start_value` and
+    `end_value` = u at the seed at its release time and at the end, `max_step` = the longest accepted step.  `rows` is the (m, 5)
+    table of the C ABI; `ts`, `release` (m,), `stop` and `substeps` are those of the call.  `path(i)` gives the (count, dim)
+    points of seed i, `elements(i)` the element of each, `times(i)` the time of each (the last one `time` on EXIT) and
+    `positions(j)` the (m, dim) positions of all particles at the snapshot time ts[j], NaN where a particle is not yet released or
+    no longer alive: the tracer cloud, and with one seed repeated and release=arange the streakline."""
+
+    DONE, EXIT, OUTSIDE, NONFINITE = 0, 1, 2, 3
+
+    def __init__(self, rows, end, status, count, end_element, rested, ts, release, stop, substeps, offsets=None, pts=None,
+                 elem=None):
+        self.rows, self.end, self.status, self.count, self.end_element, self.rested = rows, end, status, count, end_element, rested
+        self.ts, self.release, self.stop, self.substeps = ts, release, stop, substeps
+        self._offsets, self._pts, self._elem = offsets, pts, elem
+        self.length, self.time, self.start_value, self.end_value, self.max_step = (rows[:, k].copy() for k in range(5))
+
+    def _row(self, i, who):
+        m = len(self.status)
+        if self._offsets is None:
+            raise ValueError("PathLines.%s: path_lines was called with paths=False" % who)
+        if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not -m <= i < m:
+            raise IndexError("PathLines.%s: seed = %r is not one of %d" % (who, i, m))
+        r = int(i) % m
+        return r, int(self._offsets[r]), int(self._offsets[r + 1])
+
+    def path(self, i) -> np.ndarray:
+        _, a, e = self._row(i, "path")
+        return self._pts[a:e].copy()
+
+    def elements(self, i) -> np.ndarray:
+        _, a, e = self._row(i, "elements")
+        return self._elem[a:e].copy()
+
+    def _step_time(self, rel, k):
+        """the time after k accepted steps of a particle released at ts[rel]: ts[j] + i dt with k = (j - rel) substeps + i and dt
+        formed as the rule forms it; ts[stop] at the end of the last slab"""
+        n, ts = self.substeps, self.ts
+        k = np.asarray(k, dtype=np.int64)
+        j = np.minimum(rel + k // n, self.stop - 1)
+        t = ts[j] + (k - (j - rel) * n) * ((ts[j + 1] - ts[j]) / n)
+        return np.where(k >= (self.stop - rel) * n, ts[self.stop], t)
+
+    def _accepted(self):
+        """(m,) the accepted steps of every row (-1 for OUTSIDE): the recorded points but the seed and, on EXIT, the exit point,
+        which is recorded unless the bisection ended at lo = 0; then `time` is the time of the last accepted step itself"""
+        rel = self.release.astype(np.int64)
+        c = self.count.astype(np.int64) - 1
+        at = self._step_time(rel, np.maximum(c, 0))
+        own = (self.status == self.EXIT) & ~(self.time == at)
+        return np.where(own, c - 1, c)
+
+    def times(self, i) -> np.ndarray:
+        r, a, e = self._row(i, "times")
+        t = self._step_time(int(self.release[r]), np.arange(e - a))
+        if e - a == int(self._accepted()[r]) + 2:      # the last point is the exit point
+            t[-1] = self.time[r]
+        return t
+
+    def positions(self, j) -> np.ndarray:
+        B = len(self.ts)
+        if self._offsets is None:
+            raise ValueError("PathLines.positions: path_lines was called with paths=False")
+        if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or not -B <= j < B:
+            raise IndexError("PathLines.positions: snapshot = %r is not one of %d" % (j, B))
+        j = int(j) % B
+        m, dim = self.end.shape
+        out = np.full((m, dim), np.nan)
+        if j > self.stop:
+            return out
+        k = (j - self.release.astype(np.int64)) * self.substeps      # the accepted steps a particle needs to be there
+        ok = (k >= 0) & (k <= self._accepted())
+        out[ok] = self._pts[self._offsets[:-1][ok] + k[ok]]
+        return out
+
+    def __repr__(self):
+        return "PathLines(m=%d, stop=%d, substeps=%d, status=%r, time=%r)" % (len(self.status), self.stop, self.substeps,
+                                                                             self.status, self.time)
+
+
+def path_lines(par, seeds, p=2.0, u=0, direction=-1, speed=1.0, substeps=4, release=0, stop=None, gmin=1e-12, paths=True,
+               workgroup=None) -> PathLines:
+    """Where particles released into a time-dependent solution go: each seed (m, dim) is released at the snapshot time
+    ts[release] and carried to ts[stop] by w = speed direction |grad u|^(p-2) grad u of the field blended linearly in time
+    between the snapshots of the ParabolicSOL `par`, by the midpoint rule with `substeps` steps per snapshot interval
+    (csrc/pathline.hip; the rule is in include/mgb_hip.h and DESIGN.md section 4s).  The whole trajectory of every particle is
+    ONE launch.  `direction=-1` (the default) follows the flux of the parabolic equation, -sigma.  `release`: an int or an (m,)
+    int array in [0, stop); `stop=None` is the last snapshot.  Where |grad u| <= gmin a particle rests and goes on when the
+    field moves again; it stops where it leaves the mesh (the exit point and time are found by bisection) or at a non-finite
+    value.  `paths=False` leaves out the points -- no path buffer, one launch and one copy less.  `workgroup`: 64, 128 or 256
+    threads (None: the measured default); the result does not depend on it.  2-D and 3-D geometries."""
+    who = "path_lines"
+    if not isinstance(par, ParabolicSOL):
+        raise TypeError("path_lines: expected a ParabolicSOL (its snapshots are the field in time); flow_lines() follows ONE field")
+    geometry, fields, ts = _level_fields(who, par, None)
+    dim = geometry.discretization["dim"]
+    if dim == 1:
+        raise ValueError("path_lines: a 2-D or 3-D geometry is needed, got 1-D")
+    if callable(p):
+        raise TypeError("path_lines: p must be a scalar (a variable exponent is not covered)")
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        raise TypeError("path_lines: p must be a scalar, got %r" % (p,))
+    if not (math.isfinite(p) and p >= 1.0):
+        raise ValueError("path_lines: p must be finite and >= 1, got %r" % (p,))
+    if isinstance(direction, bool) or direction not in (1, -1):
+        raise ValueError("path_lines: direction must be +1 or -1, got %r" % (direction,))
+    speed, gmin = float(speed), float(gmin)
+    if not (math.isfinite(speed) and speed > 0.0):
+        raise ValueError("path_lines: speed must be finite and > 0, got %r" % (speed,))
+    if not (math.isfinite(gmin) and gmin >= 0.0):
+        raise ValueError("path_lines: gmin must be finite and >= 0, got %r" % (gmin,))
+    if isinstance(substeps, bool) or not isinstance(substeps, (int, np.integer)) or substeps < 1:
+        raise ValueError("path_lines: substeps must be an int >= 1, got %r" % (substeps,))
+    if workgroup not in (None, 64, 128, 256):
+        raise ValueError("path_lines: workgroup must be 64, 128 or 256, got %r" % (workgroup,))
+    ts = f64(ts)
+    B = len(fields)
+    if B < 2 or B > 65535:
+        raise ValueError("path_lines: the ParabolicSOL must have 2..65535 snapshots, got %d" % B)
+    if not np.all(np.isfinite(ts)) or not np.all(np.diff(ts) > 0):
+        raise ValueError("path_lines: ts must be finite and strictly increasing")
+    if stop is None:
+        stop = B - 1
+    if isinstance(stop, bool) or not isinstance(stop, (int, np.integer)) or not 1 <= stop <= B - 1:
+        raise ValueError("path_lines: stop must be an int in [1, %d], got %r" % (B - 1, stop))
+    stop = int(stop)
+    pts = f64(np.asarray(_to_cpu_array(seeds)))
+    if pts.ndim != 2 or pts.shape[1] != dim:
+        raise ValueError("path_lines: seeds must have shape (m, %d), got %r" % (dim, tuple(pts.shape)))
+    m = pts.shape[0]
+    rel = np.asarray(release)
+    if rel.dtype == np.bool_ or not np.issubdtype(rel.dtype, np.integer) or rel.shape not in ((), (m,)):
+        raise ValueError("path_lines: release must be an int or an (m,) = (%d,) int array, got %r" % (m, release))
+    rel = np.ascontiguousarray(np.broadcast_to(rel, (m,)), dtype=np.int64)
+    if m and (rel.min() < 0 or rel.max() >= stop):
+        raise ValueError("path_lines: every release index must lie in [0, stop) = [0, %d)" % stop)
+    rel = np.ascontiguousarray(rel, dtype=np.int32)
+    loc, backend = _locator_of(geometry)
+    vecs = [_nodal_values(geometry, zk, backend, who) for zk in fields]
+    S = vecs[0][1]
+    if any(Sk != S for _, Sk in vecs):
+        raise ValueError("path_lines: the snapshots have different numbers of columns")
+    u = _energy_column(u, S, "u", who)
+    slots = (stop - (int(rel.min()) if m else 0)) * int(substeps) + 2
+    if paths and m * slots * dim > 2 ** 31 - 1:
+        raise ValueError("path_lines: the path buffer of m ((stop - min release) substeps + 2) dim doubles has more than "
+                         "2^31 - 1 entries")
+    table = (C.c_void_p * B)(*[v.handle.value for v, _ in vecs])
+    rows, end = np.empty((m, 5)), np.empty((m, dim))
+    status, count, end_element, rested = (np.empty(m, dtype=np.int32) for _ in range(4))
+    h = C.c_void_p()
+    call("mgb_geo_path_lines", loc, B, table, dptr(ts), S, u, m, dptr(pts), iptr(rel), stop, int(substeps), p, int(direction), speed,
+         gmin, int(workgroup or 0), dptr(rows), dptr(end), iptr(status), iptr(count), iptr(end_element), iptr(rested),
+         C.byref(h) if paths else None)
+    offsets = ppts = pelem = None
+    if paths:
+        try:
+            total = int(count.sum())
+            offsets, ppts, pelem = np.empty(m + 1, dtype=np.int64), np.empty((total, dim)), np.empty(total, dtype=np.int32)
+            call("mgb_flowpath_get", h, offsets.ctypes.data_as(_lib.c_ll_p), dptr(ppts), iptr(pelem))
+        finally:
+            call("mgb_flowpath_destroy", h)
+    return PathLines(rows, end, status, count, end_element, rested, ts, rel, stop, int(substeps), offsets, ppts, pelem)
 
 
 # --------------------------------------------------------------------------- plane sections of solutions

@@ -47,6 +47,8 @@ compile "$HERE/_obj/isosurface.o" "$HERE/isosurface.hip" "$HIPCC" --offload-arch
 compile "$HERE/_obj/flowline.o" "$HERE/flowline.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS -ffp-contract=off
 # section.hip: the same for the plane sections (section.hpp on top of levelset.hpp, isosurface.hpp and flowline.hpp)
 compile "$HERE/_obj/section.o" "$HERE/section.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS -ffp-contract=off
+# pathline.hip: the same for the path lines (pathline.hpp on top of flowline.hpp); its object goes last on the link line
+compile "$HERE/_obj/pathline.o" "$HERE/pathline.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS -ffp-contract=off
 compile "$HERE/_obj/boundary.o" "$HERE/boundary.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/estimate.o" "$HERE/estimate.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/parabolic.o" "$HERE/parabolic.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
@@ -59,5 +61,5 @@ for pid in "${pids[@]}"; do
   wait "$pid" || { echo "build.sh: a compile job failed" >&2; exit 1; }
 done
 rm -f "$OUT/libmgb_hip.so"
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,chol_premap,chol_plan,kernels,kernels_f32,mg,interp,reduce,norms,energy,levelset,isosurface,boundary,estimate,parabolic,gpuchol,amg,amg_mg,comm,capi,flowline,section}.o -lpthread -ldl
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,chol_premap,chol_plan,kernels,kernels_f32,mg,interp,reduce,norms,energy,levelset,isosurface,boundary,estimate,parabolic,gpuchol,amg,amg_mg,comm,capi,flowline,section,pathline}.o -lpthread -ldl
 echo "built $OUT/libmgb_hip.so"

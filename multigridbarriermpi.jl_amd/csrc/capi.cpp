@@ -15,6 +15,7 @@
 #include "energy.hpp"
 #include "estimate.hpp"
 #include "flowline.hpp"
+#include "pathline.hpp"
 #include "levelset.hpp"
 #include "mixed.hpp"
 #include "norms.hpp"
@@ -66,6 +67,8 @@ struct mgb_locator_s {
   DevBuf<int32_t> fl_int, fl_pelem;                // ... status, count, end element; the elements of the path points
   DevBuf<long long> fl_offsets;                    // ... the first point of every row in the compacted paths
   DevBuf<const double*> fl_table;                  // ... and the device table of field pointers, uploaded per call
+  DevBuf<double> pl_ts;                            // mgb_geo_path_lines (which shares the fl_ buffers): the snapshot times ...
+  DevBuf<int32_t> pl_release;                      // ... and the release indices of the call
 };
 struct mgb_flowpath_s {
   mgb_ctx_s* ctx;
@@ -1741,6 +1744,139 @@ int mgb_geo_flow_lines_host(mgb_geo g, int B, const double* const* z, int S, int
     A.seeds = seeds;
     A.rows = rows, A.end = end, A.status = status, A.count = count, A.end_element = end_element;
     flowline::flow_lines_host(L.dim, L.k, A, offsets, pts, elem, capacity);
+  });
+}
+
+// ---- path lines through the snapshots of a parabolic run (pathline.hpp / pathline.hip); buffers and handle are the flow lines'
+int mgb_geo_path_lines(mgb_locator loc, int B, const mgb_vec* z, const double* ts_host, int S, int u, int m,
+                       const double* seeds_host, const int32_t* release_host, int stop, int substeps, double p, int direction,
+                       double speed, double gmin, int workgroup, double* rows_host, double* end_host, int32_t* status_host,
+                       int32_t* count_host, int32_t* end_element_host, int32_t* rested_host, mgb_flowpath* paths) {
+  return guard([&] {
+    const bool outputs = rows_host && end_host && status_host && count_host && end_element_host && rested_host;
+    pathline::Call c{};
+    c.null_argument = !(loc && z && ts_host) || (m > 0 && !(seeds_host && release_host && outputs));
+    std::vector<long long> len;
+    if (!c.null_argument && B >= 2 && B <= 65535) {
+      len.resize((size_t)B);
+      for (int b = 0; b < B; ++b) len[b] = z[b] == nullptr ? -1 : z[b]->ctx != loc->ctx ? -2 : (long long)z[b]->n;
+      c.field_len = len.data();
+    }
+    if (loc) {
+      c.dim = loc->loc.dim;
+      c.world = loc->ctx->ctx.world;
+      c.want_len = (long long)loc->loc.n * S;
+    }
+    c.B = B, c.S = S, c.u = u, c.m = m, c.stop = stop, c.substeps = substeps, c.direction = direction, c.workgroup = workgroup;
+    c.p = p, c.speed = speed, c.gmin = gmin, c.ts = ts_host, c.release = release_host, c.paths = paths != nullptr;
+    pathline::Args A{};
+    pathline::check("geo_path_lines", c, A);
+    const interp::Locator& L = loc->loc;
+    const int dim = L.dim;
+    const size_t rows = (size_t)m;
+    std::unique_ptr<mgb_flowpath_s> out;
+    if (paths) {
+      out.reset(new mgb_flowpath_s{loc->ctx, dim, {}, {}, {}});
+      out->offsets.assign(rows + 1, 0);
+    }
+    if (m == 0) {
+      if (paths) *paths = out.release();
+      return;
+    }
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const size_t nout = rows * (pathline::kRowCols + dim);
+    if (loc->fl_out.n < nout) loc->fl_out.alloc(nout);
+    if (loc->fl_int.n < 4 * rows) loc->fl_int.alloc(4 * rows);
+    if (paths) {
+      const size_t slots = rows * (size_t)A.stride;
+      if (loc->fl_pts.n < slots * dim) loc->fl_pts.alloc(slots * dim);
+      if (loc->fl_pelem.n < slots) loc->fl_pelem.alloc(slots);
+    }
+    std::vector<const double*> table((size_t)B);
+    for (int b = 0; b < B; ++b) table[b] = z[b]->buf.p;
+    loc->fl_table.upload(table.data(), table.size());      // every earlier launch that read these has been waited for
+    loc->fl_seeds.upload(seeds_host, (size_t)m * dim);
+    loc->pl_ts.upload(ts_host, (size_t)B);
+    loc->pl_release.upload(release_host, (size_t)m);
+    A.own = L.view(loc->cellptr.p, loc->cellelem.p, loc->x.p);
+    A.z = loc->fl_table.p;
+    A.ts = loc->pl_ts.p;
+    A.seeds = loc->fl_seeds.p;
+    A.release = loc->pl_release.p;
+    A.rows = loc->fl_out.p;
+    A.end = loc->fl_out.p + rows * pathline::kRowCols;
+    A.status = loc->fl_int.p;
+    A.count = loc->fl_int.p + rows;
+    A.end_element = loc->fl_int.p + 2 * rows;
+    A.rested = loc->fl_int.p + 3 * rows;
+    A.pts = paths ? loc->fl_pts.p : nullptr;
+    A.pelem = paths ? loc->fl_pelem.p : nullptr;
+    pathline::launch_advance(st, dim, L.k, A, workgroup ? workgroup : pathline::kDefaultWorkgroup);
+    hip_check(hipGetLastError(), "geo_path_lines launch");
+    hip_check(hipStreamSynchronize(st), "sync geo_path_lines");
+    std::vector<double> dbl(nout);
+    std::vector<int32_t> ints(4 * rows);
+    hip_check(hipMemcpy(dbl.data(), loc->fl_out.p, nout * sizeof(double), hipMemcpyDeviceToHost), "D2H");
+    hip_check(hipMemcpy(ints.data(), loc->fl_int.p, 4 * rows * sizeof(int32_t), hipMemcpyDeviceToHost), "D2H");
+    std::copy(dbl.begin(), dbl.begin() + rows * pathline::kRowCols, rows_host);
+    std::copy(dbl.begin() + rows * pathline::kRowCols, dbl.end(), end_host);
+    std::copy(ints.begin(), ints.begin() + rows, status_host);
+    std::copy(ints.begin() + rows, ints.begin() + 2 * rows, count_host);
+    std::copy(ints.begin() + 2 * rows, ints.begin() + 3 * rows, end_element_host);
+    std::copy(ints.begin() + 3 * rows, ints.end(), rested_host);
+    if (!paths) return;
+    for (size_t r = 0; r < rows; ++r) {
+      if (count_host[r] < 0 || count_host[r] > A.stride) throw InternalError("geo_path_lines: a count outside its row");
+      out->offsets[r + 1] = out->offsets[r] + count_host[r];
+    }
+    const long long total = out->offsets[rows];
+    if (total > 0) {
+      out->pts.alloc((size_t)total * dim);
+      out->elem.alloc((size_t)total);
+      loc->fl_offsets.upload(out->offsets.data(), rows + 1);
+      flowline::Args F{};      // what compact_kernel reads: the fixed-stride rows, one "field" of m rows
+      F.B = 1, F.m = m, F.stride = A.stride, F.pts = A.pts, F.pelem = A.pelem;
+      flowline::launch_compact(st, dim, F, loc->fl_offsets.p, out->pts.p, out->elem.p);
+      hip_check(hipGetLastError(), "geo_path_lines compact launch");
+      hip_check(hipStreamSynchronize(st), "sync geo_path_lines compact");
+    }
+    *paths = out.release();
+  });
+}
+int mgb_geo_path_lines_host(mgb_geo g, int B, const double* const* z, const double* ts, int S, int u, int m, const double* seeds,
+                            const int32_t* release, int stop, int substeps, double p, int direction, double speed, double gmin,
+                            double* rows, double* end, int32_t* status, int32_t* count, int32_t* end_element, int32_t* rested,
+                            long long* offsets, double* pts, int32_t* elem, long long capacity) {
+  return guard([&] {
+    pathline::Call c{};
+    c.null_argument = !(g && z && ts) || (m > 0 && !(seeds && release && rows && end && status && count && end_element && rested));
+    std::vector<long long> len;
+    if (!c.null_argument && B >= 2 && B <= 65535) {
+      len.resize((size_t)B);
+      for (int b = 0; b < B; ++b) len[b] = z[b] == nullptr ? -1 : (long long)g->g.n * S;
+      c.field_len = len.data();
+    }
+    if (g) {
+      c.dim = g->g.dim;
+      c.want_len = (long long)g->g.n * S;
+    }
+    c.world = 1;
+    c.B = B, c.S = S, c.u = u, c.m = m, c.stop = stop, c.substeps = substeps, c.direction = direction, c.workgroup = 0;
+    c.p = p, c.speed = speed, c.gmin = gmin, c.ts = ts, c.release = release, c.paths = offsets != nullptr;
+    pathline::Args A{};
+    pathline::check("geo_path_lines_host", c, A);
+    need((offsets == nullptr) == (pts == nullptr) && (offsets == nullptr) == (elem == nullptr),
+         "geo_path_lines_host: offsets, points and elements come together");
+    need(!offsets || capacity >= 0, "geo_path_lines_host: negative capacity");
+    const interp::Locator L = interp::build_locator(g->g);
+    A.own = L.view(L.cellptr.data(), L.cellelem.data(), g->g.x.data());
+    A.z = z;
+    A.ts = ts;
+    A.seeds = seeds;
+    A.release = release;
+    A.rows = rows, A.end = end, A.status = status, A.count = count, A.end_element = end_element, A.rested = rested;
+    pathline::path_lines_host(L.dim, L.k, A, offsets, pts, elem, capacity);
   });
 }
 
