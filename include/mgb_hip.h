@@ -823,6 +823,61 @@ int mgb_geo_path_lines_host(mgb_geo g, int B, const double* const* z /* B arrays
                             double* end /* m x dim */, int32_t* status, int32_t* count, int32_t* end_element, int32_t* rested,
                             long long* offsets_or_null, double* pts_or_null, int32_t* elem_or_null, long long capacity);
 
+/* ---- line integrals of nodal fields: chords, gates, projections (2-D and 3-D geometries; single-GPU contexts, fp64) -------- *
+ * Segment i is x(t) = a_i + t (b_i - a_i), t in [0, 1], l = |b - a|, tdir = (b - a) / l and in 2-D the left normal
+ * nu = (-tdir_y, tdir_x).  The field is the broken polynomial field of column u of z (n x S row-major), as for
+ * mgb_geo_interpolate.  What one segment collects (csrc/ray.hpp: integrate, run by the kernels and by the host restatement):
+ *   1. Clip.  For element e the reference coordinates of a and of b (the inverse maps of mgb_geo_interpolate) make every
+ *      constraint function -- lambda_0, lambda_1, lambda_2 in 2-D; xi_d and 1 - xi_d in 3-D -- affine along the segment:
+ *      g_j(t) = alpha_j + t beta_j, alpha_j = g_j(a), beta_j = g_j(b) - g_j(a).  e's interval is {t in [0, 1] : g_j(t) >= -tau
+ *      for all j}, tau = 1e-12: beta_j > 0 raises t0 to -(alpha_j + tau) / beta_j, beta_j < 0 lowers t1 to the same quotient,
+ *      beta_j == 0 with alpha_j + tau < 0 empties it.  Comparisons only, never fmin / fmax.  A piece needs t1 > t0.
+ *   2. Ownership.  With m = x((t0 + t1) / 2) the piece counts iff the element of m by the containment rule of
+ *      mgb_geo_interpolate -- the LOWEST element containing m -- is e.  A segment in a face, an edge or through a vertex is
+ *      integrated once, in the lowest of the elements that share it; elements that only touch the segment drop out.
+ *      Neighbouring pieces overlap by at most tau / |beta_j| in t at each end; this is not corrected.
+ *   3. Walk.  The segment is clipped to the bounding box of the bin grid grown by 1e-9 x its diagonal (the slack).  The major
+ *      axis M maximises |b_d - a_d| x (cells per unit length of axis d).  For each cell layer along M between the layers of
+ *      the entry and the exit point (each moved outwards by the slack), in the direction of travel: the t-range of the layer
+ *      grown by the slack, the segment's coordinates on the other axes at both ends of that range -/+ the slack, converted to
+ *      cell coordinates (monotone), give a rectangle of cells, visited in ascending order.  In cell c the ascending
+ *      candidate list is walked; element e is processed there iff it has a piece and the cell of its midpoint is c.  Every
+ *      cell and every element is visited once.  a == b, a non-finite end point or a segment beside the box give no pieces.
+ *   4. Quadrature.  Gauss-Legendre on [t0, t1] with 4 points in 2-D and 3, 4, 6 points in 3-D for k = 1, 2, 3 (exact for
+ *      int u, of degree 3 k <= 2 N - 1 along a line).  At a point: value and gradient of e's own polynomial, sigma =
+ *      |grad u|^(p - 2) grad u (grad u itself at p = 2, grad u / |grad u| at p = 1, exactly 0 where grad u = 0).  Maximum and
+ *      minimum over the Gauss points and both piece ends.
+ *   5. Per row r = b m + i (field b, segment i) MGB_RAY_COLS doubles and an int32 count of owned pieces:
+ *        [0] length    sum (t1 - t0) l            [4] max   as in 4.
+ *        [1] integral  int u ds                   [5] min   as in 4.
+ *        [2] along     int sigma . tdir ds        [6] enter the smallest t0
+ *        [3] across    int sigma . nu ds; 0 (3-D) [7] leave the largest t1
+ *      Plain (uncompensated) sums in walk order.  No pieces: 0, 0, 0, 0, -inf, +inf, NaN, NaN and count 0.  A non-finite value
+ *      or gradient at any point of an owned piece makes [1] .. [5] of that row NaN; [0], [6], [7] and count are unaffected;
+ *      an element without an owned piece is never read.  A row depends on its segment and field alone: not on m, B, the
+ *      workgroup size or its place in the batch.
+ *   6. Pieces (pieces_or_null non-null): per row, in walk order, the element (int32) and t0, t1, int u of every owned piece,
+ *      in CSR form.  The counts come from the measure launch, the host forms the offsets, a second launch walks again and
+ *      writes at its offsets.  They come back through mgb_levelset_get / mgb_levelset_destroy, unchanged: row_offsets B m + 1,
+ *      seg total x 3, item = the element.
+ * workgroup: 0 (the default, 64), 64, 128 or 256 lanes; one lane per (segment, field) on a grid (ceil(m / workgroup), B).
+ * The rule is compiled with fp contraction off on both sides: device and host restatement agree bit for bit for p = 1 and 2;
+ * for another p, along and across differ by pow.
+ * MGB_E_ARG, before anything is allocated, launched or written: a null argument or field; a 1-D geometry; B < 1 or B > 65535;
+ * p not finite or < 1; S < 1; u outside [0, S); m < 0; B m beyond 2^31 - 1; another workgroup size; vectors of the wrong
+ * length or of another context; a sharded context.  m = 0 returns at once (an empty handle with pieces). */
+#define MGB_RAY_COLS 8
+int mgb_geo_line_integrals(mgb_locator loc, int B, const mgb_vec* z /* B vectors of n x S */, int S, int u, int m,
+                           const double* a_host /* m x dim */, const double* b_host /* m x dim */, double p, int workgroup,
+                           double* rows_host /* B m x MGB_RAY_COLS */, int32_t* count_host /* B m */,
+                           mgb_levelset* pieces_or_null);
+/* host restatement (no context, no GPU): the same routine, row after row.  offsets_or_null (B m + 1), piece_or_null
+ * (capacity x 3) and elem_or_null (capacity) come together; MGB_E_ARG when there are more pieces than they hold. */
+int mgb_geo_line_integrals_host(mgb_geo g, int B, const double* const* z /* B arrays of n x S */, int S, int u, int m,
+                                const double* a /* m x dim */, const double* b /* m x dim */, double p,
+                                double* rows /* B m x MGB_RAY_COLS */, int32_t* count /* B m */, long long* offsets_or_null,
+                                double* piece_or_null, int32_t* elem_or_null, long long capacity);
+
 /* ---- boundary facets of a geometry and boundary integrals of p-Laplace solutions --------------------------------------- *
  * The elements are broken and their quadrature is nodal: every node of a boundary facet is a row of x and z already, so the
  * boundary rule of a geometry is a list of nf facets of q nodes each: q global rows, q weights omega, the outward unit normal n,

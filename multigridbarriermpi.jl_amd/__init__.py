@@ -38,7 +38,7 @@ __all__ = [
     "_raw_array", "_to_cpu_array", "MGBError", "device_count", "AMG", "amg", "hcat", "BarrierFn", "barrier_functions",
     "interpolate", "sample_grid", "norms", "error", "convergence", "FieldNorms", "Convergence",
     "energy", "flux", "Energy", "level_sets", "LevelSets", "isosurfaces", "Isosurfaces", "flow_lines", "FlowLines",
-    "path_lines", "PathLines", "sections", "Sections", "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
+    "path_lines", "PathLines", "sections", "Sections", "line_integrals", "project", "LineIntegrals", "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
     "dirichlet_on", "neumann_load", "NeumannLoad",
     "interior", "InteriorFacets", "estimate", "ErrorIndicators", "mark", "refine_triangles", "adapt",
     "estimate_steps", "StepIndicators", "refine_times", "adapt_time",
@@ -2807,6 +2807,152 @@ def sections(obj, planes, p=2.0, u=0, z=None, pieces=True) -> Sections:
         finally:
             call("mgb_levelset_destroy", h)
     return Sections(pl[0].copy() if single else pl, rows, counts, ts, (ts is None, single), dim, offsets, piece, item)
+
+
+# --------------------------------------------------------------------------- line integrals of solutions
+
+
+class LineIntegrals:
+    """Result of line_integrals(): per segment `length` = the length of the part inside the mesh, `integral` = int u ds over
+    it, `mean` = integral / length (NaN where length == 0), `along` = int sigma . tdir ds, `across` = int sigma . nu ds with nu
+    the left normal of the segment (the flow rate through a gate; None in 3-D), `max` and `min` = the extrema of u over the
+    quadrature points and the ends of the pieces (-inf and +inf without pieces), `enter` and `leave` = the parameters t in
+    [0, 1] at which the segment first enters and last leaves the mesh (NaN without pieces), `count` = the number of pieces.
+    Shapes (m,) for one field; an axis of len(ts) in front for a ParabolicSOL (whose `ts` is carried).  `rows` is the (B, m, 8)
+    table of the C ABI.  `pieces(i, b)` gives (elements, t0, t1, integral) of the pieces of segment i in field b, in walk
+    order."""
+
+    def __init__(self, rows, count, ts, dim, offsets=None, piece=None, elem=None):
+        self.rows, self.ts, self.dim = rows, ts, dim
+        self._count, self._offsets, self._piece, self._elem = count, offsets, piece, elem
+        self._shape = count.shape      # (B, m)
+        self._view = (lambda a: a[0]) if ts is None else (lambda a: a)
+        self._set(self._shape[1:])
+
+    def _set(self, shape):
+        B = self._shape[0]
+        col = lambda j: self._view(self.rows[:, :, j].reshape((B,) + tuple(shape)).copy())
+        self.length, self.integral, self.along, self.across, self.max, self.min, self.enter, self.leave = (col(j) for j in range(8))
+        if self.dim == 3:
+            self.across = None
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.mean = np.where(self.length > 0, self.integral / self.length, np.nan)
+        self.count = self._view(self._count.reshape((B,) + tuple(shape)).copy())
+
+    def _row(self, i, b, who):
+        B, m = self._shape
+        if self._offsets is None:
+            raise ValueError("LineIntegrals.%s: line_integrals was called with pieces=False" % who)
+        for v, n, name in ((i, m, "segment"), (b, B, "field")):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -n <= v < n:
+                raise IndexError("LineIntegrals.%s: %s = %r is not one of %d" % (who, name, v, n))
+        r = (int(b) % B) * m + int(i) % m
+        return int(self._offsets[r]), int(self._offsets[r + 1])
+
+    def pieces(self, i, b=0):
+        a, e = self._row(i, b, "pieces")
+        return self._elem[a:e].copy(), self._piece[a:e, 0].copy(), self._piece[a:e, 1].copy(), self._piece[a:e, 2].copy()
+
+    def __repr__(self):
+        return "LineIntegrals(m=%d, length=%r, integral=%r, count=%r)" % (self._shape[1], self.length, self.integral, self.count)
+
+
+def line_integrals(obj, a, b, p=2.0, u=0, z=None, pieces=False, workgroup=None) -> LineIntegrals:
+    """Integrals of a solution along straight segments a[i] -> b[i], (m, dim) each, on the device (csrc/ray.hip; the rule is in
+    include/mgb_hip.h and DESIGN.md section 4t): the length inside the mesh, int u ds, the mean, the flow int sigma . tdir ds
+    along and -- in 2-D -- int sigma . nu ds across the segment (the flow rate through a gate, nu its left normal), sigma =
+    |grad u|^(p-2) grad u, the extrema of u and where the segment enters and leaves the mesh.  One lane walks one segment
+    through the bin grid; every element polynomial is integrated exactly by a fixed Gauss rule.  `obj`, `u` and `z` as in
+    sections(); all snapshots of a ParabolicSOL are integrated by ONE set of launches.  `p`: ONE finite scalar >= 1.
+    `pieces=True` also returns the pieces per element.  `workgroup`: 64, 128 or 256 lanes (None: the default); the result does
+    not depend on it.  A segment outside the mesh, with a == b or with a non-finite end gives an empty row, not an error.
+    A 1-D geometry raises ValueError."""
+    geometry, fields, ts = _level_fields("line_integrals", obj, z)
+    dim = geometry.discretization["dim"]
+    if dim == 1:
+        raise ValueError("line_integrals: a 2-D or 3-D geometry is needed, got 1-D; interpolate() gives the value at a point")
+    if callable(p) or isinstance(p, (HPCVector, HPCMatrix)) or np.ndim(p) != 0:
+        raise TypeError("line_integrals: p must be one scalar per call (a callable or nodal exponent p(x) is not supported)")
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        raise TypeError("line_integrals: p must be one scalar per call, got %r" % (p,))
+    if not (np.isfinite(p) and p >= 1.0):
+        raise ValueError("line_integrals: p must be finite and >= 1, got %r" % (p,))
+    if workgroup not in (None, 64, 128, 256):
+        raise ValueError("line_integrals: workgroup must be 64, 128 or 256, got %r" % (workgroup,))
+    try:
+        pa, pb = (f64(np.asarray(v.to_numpy() if hasattr(v, "to_numpy") else v, dtype=np.float64)) for v in (a, b))
+    except (TypeError, ValueError):
+        raise TypeError("line_integrals: a and b must be (m, %d) arrays" % dim)
+    if pa.ndim == 1 and pb.ndim == 1 and pa.shape == (dim,):
+        pa, pb = pa.reshape(1, dim), pb.reshape(1, dim)
+    if pa.ndim != 2 or pa.shape[1] != dim or pb.shape != pa.shape:
+        raise ValueError("line_integrals: a and b must both have shape (m, %d), got %r and %r" % (dim, tuple(pa.shape), tuple(pb.shape)))
+    m = pa.shape[0]
+    loc, backend = _locator_of(geometry)
+    vecs = [_nodal_values(geometry, zk, backend, "line_integrals") for zk in fields]
+    B, S = len(vecs), vecs[0][1]
+    if any(Sk != S for _, Sk in vecs):
+        raise ValueError("line_integrals: the snapshots have different numbers of columns")
+    if B > 65535:
+        raise ValueError("line_integrals: at most 65535 fields per call")
+    if B * m > 2 ** 31 - 1:
+        raise ValueError("line_integrals: more than 2^31 - 1 rows (fields x segments) per call")
+    u = _energy_column(u, S, "u", "line_integrals")
+    table = (C.c_void_p * B)(*[v.handle.value for v, _ in vecs])
+    rows, count = np.empty((B, m, 8)), np.empty((B, m), dtype=np.int32)
+    h = C.c_void_p()
+    call("mgb_geo_line_integrals", loc, B, table, S, u, m, dptr(pa), dptr(pb), p, int(workgroup or 0), dptr(rows), iptr(count),
+         C.byref(h) if pieces else None)
+    offsets = piece = elem = None
+    if pieces:
+        try:
+            total = int(count.sum())
+            offsets, piece, elem = np.empty(B * m + 1, dtype=np.int64), np.empty((total, 3)), np.empty(total, dtype=np.int32)
+            call("mgb_levelset_get", h, offsets.ctypes.data_as(_lib.c_ll_p), dptr(piece), iptr(elem))
+        finally:
+            call("mgb_levelset_destroy", h)
+    return LineIntegrals(rows, count, ts, dim, offsets, piece, elem)
+
+
+def project(obj, axis=-1, shape=(256, 256), bounds=None, **kw):
+    """A projection of a solution along a coordinate axis: parallel segments along `axis` across the bounding box (or
+    `bounds` = (lower corner, upper corner)), one from every pixel centre of a grid of `shape` pixels over the other axes,
+    slowest axis first as in sample_grid() -- (ny, nx) for a 3-D solution projected along z, (n,) for the marginal profiles of a
+    2-D one.  Returns X (*shape, dim - 1), the pixel centres in the coordinates of the other axes, and the LineIntegrals of
+    line_integrals(obj, a, b, **kw) with every result array reshaped to `shape` ((len(ts), *shape) for a ParabolicSOL): `mean`
+    and `max` are the two usual projections."""
+    geometry = obj if isinstance(obj, Geometry) else getattr(obj, "geometry", None)
+    if not isinstance(geometry, Geometry):
+        raise TypeError("project: expected an AMGBSOL, a ParabolicSOL or a Geometry")
+    dim = geometry.discretization["dim"]
+    if dim == 1:
+        raise ValueError("project: a 2-D or 3-D geometry is needed, got 1-D")
+    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not -dim <= axis < dim:
+        raise ValueError("project: axis must be one of the %d axes, got %r" % (dim, axis))
+    axis = int(axis) % dim
+    shape = (int(shape),) if np.isscalar(shape) else tuple(int(v) for v in shape)
+    if len(shape) != dim - 1 or min(shape) < 1:
+        raise ValueError("project: shape must give one positive pixel count per remaining axis (%d)" % (dim - 1))
+    if bounds is None:
+        x = np.asarray(_to_cpu_array(geometry.x)).reshape(-1, dim)
+        lo, hi = x.min(axis=0), x.max(axis=0)
+    else:
+        lo, hi = (f64(np.asarray(v)).reshape(dim) for v in bounds)
+    others = [d for d in range(dim) if d != axis]
+    # pixel centres: others[0] is the fastest axis of the image, as x is in sample_grid
+    centres = [lo[d] + (np.arange(shape[len(others) - 1 - j]) + 0.5) * ((hi[d] - lo[d]) / shape[len(others) - 1 - j])
+               for j, d in enumerate(others)]
+    mesh = np.meshgrid(*centres[::-1], indexing="ij")
+    X = np.stack(mesh[::-1], axis=-1)
+    flat = X.reshape(-1, dim - 1)
+    a, b = np.empty((len(flat), dim)), np.empty((len(flat), dim))
+    a[:, others], b[:, others] = flat, flat
+    a[:, axis], b[:, axis] = lo[axis], hi[axis]
+    res = line_integrals(obj, a, b, **kw)
+    res._set(shape)
+    return X, res
 
 
 # --------------------------------------------------------------------------- boundary facets and boundary integrals

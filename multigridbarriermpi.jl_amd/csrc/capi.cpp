@@ -16,6 +16,7 @@
 #include "estimate.hpp"
 #include "flowline.hpp"
 #include "pathline.hpp"
+#include "ray.hpp"
 #include "levelset.hpp"
 #include "mixed.hpp"
 #include "norms.hpp"
@@ -69,6 +70,10 @@ struct mgb_locator_s {
   DevBuf<const double*> fl_table;                  // ... and the device table of field pointers, uploaded per call
   DevBuf<double> pl_ts;                            // mgb_geo_path_lines (which shares the fl_ buffers): the snapshot times ...
   DevBuf<int32_t> pl_release;                      // ... and the release indices of the call
+  DevBuf<double> ry_ab, ry_rows;                   // mgb_geo_line_integrals: start and end points; the rows of the call
+  DevBuf<int32_t> ry_count;                        // ... the owned pieces of every row
+  DevBuf<long long> ry_offsets;                    // ... the first piece of every row
+  DevBuf<const double*> ry_table;                  // ... and the device table of field pointers, uploaded per call
 };
 struct mgb_flowpath_s {
   mgb_ctx_s* ctx;
@@ -80,7 +85,8 @@ struct mgb_flowpath_s {
 struct mgb_levelset_s {
   mgb_ctx_s* ctx;
   int width;                                       // doubles per row: segments 4 in 2-D and 2 in 1-D, triangles (mgb_geo_isosurfaces) 9,
-                                                   // pieces of a cut (mgb_geo_sections) 6 in 2-D and 12 in 3-D
+                                                   // pieces of a cut (mgb_geo_sections) 6 in 2-D and 12 in 3-D, pieces of a
+                                                   // segment (mgb_geo_line_integrals) 3
   std::vector<long long> row_offsets;              // B nl + 1
   DevBuf<double> seg;
   DevBuf<int32_t> item;
@@ -2040,6 +2046,120 @@ int mgb_geo_sections_host(mgb_geo g, int B, const double* const* z, int S, int u
     A.z = z;
     A.planes = planes;
     section::sections_host(L.dim, L.k, A, out, counts, row_offsets, piece, item, capacity);
+  });
+}
+
+// ---- line integrals of nodal fields (ray.hpp / ray.hip); the pieces come back through the level sets' handle
+int mgb_geo_line_integrals(mgb_locator loc, int B, const mgb_vec* z, int S, int u, int m, const double* a_host, const double* b_host,
+                           double p, int workgroup, double* rows_host, int32_t* count_host, mgb_levelset* pieces) {
+  return guard([&] {
+    ray::Call c{};
+    c.null_argument = !(loc && z) || (m > 0 && !(a_host && b_host && rows_host && count_host));
+    std::vector<long long> len;
+    if (!c.null_argument && B >= 1 && B <= 65535) {
+      len.resize((size_t)B);
+      for (int b = 0; b < B; ++b) len[b] = z[b] == nullptr ? -1 : z[b]->ctx != loc->ctx ? -2 : (long long)z[b]->n;
+      c.field_len = len.data();
+    }
+    if (loc) {
+      c.dim = loc->loc.dim;
+      c.world = loc->ctx->ctx.world;
+      c.want_len = (long long)loc->loc.n * S;
+    }
+    c.B = B, c.S = S, c.u = u, c.m = m, c.workgroup = workgroup, c.p = p;
+    ray::check("geo_line_integrals", c);
+    const interp::Locator& L = loc->loc;
+    const int dim = L.dim;
+    const size_t rows = (size_t)B * m;
+    std::unique_ptr<mgb_levelset_s> out;
+    if (pieces) {
+      out.reset(new mgb_levelset_s{loc->ctx, ray::kPieceWidth, {}, {}, {}});
+      out->row_offsets.assign(rows + 1, 0);
+    }
+    if (m == 0) {
+      if (pieces) *pieces = out.release();
+      return;
+    }
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const size_t npts = (size_t)m * dim;
+    if (loc->ry_ab.n < 2 * npts) loc->ry_ab.alloc(2 * npts);
+    if (loc->ry_rows.n < rows * ray::kCols) loc->ry_rows.alloc(rows * ray::kCols);
+    if (loc->ry_count.n < rows) loc->ry_count.alloc(rows);
+    std::vector<const double*> table((size_t)B);
+    for (int b = 0; b < B; ++b) table[b] = z[b]->buf.p;
+    loc->ry_table.upload(table.data(), table.size());      // every earlier launch that read these has been waited for
+    std::vector<double> ab(2 * npts);
+    std::copy(a_host, a_host + npts, ab.begin());
+    std::copy(b_host, b_host + npts, ab.begin() + npts);
+    hip_check(hipMemcpy(loc->ry_ab.p, ab.data(), 2 * npts * sizeof(double), hipMemcpyHostToDevice), "H2D");
+    ray::Args A;
+    A.own = L.view(loc->cellptr.p, loc->cellelem.p, loc->x.p);
+    A.z = loc->ry_table.p;
+    A.a = loc->ry_ab.p;
+    A.b = loc->ry_ab.p + npts;
+    A.p = p;
+    A.m = m, A.S = S, A.u = u, A.B = B;
+    A.rows = loc->ry_rows.p;
+    A.count = loc->ry_count.p;
+    const int wg = workgroup ? workgroup : ray::kDefaultWorkgroup;
+    ray::launch_measure(st, dim, L.k, A, wg);
+    hip_check(hipGetLastError(), "geo_line_integrals launch");
+    hip_check(hipStreamSynchronize(st), "sync geo_line_integrals");
+    hip_check(hipMemcpy(rows_host, loc->ry_rows.p, rows * ray::kCols * sizeof(double), hipMemcpyDeviceToHost), "D2H");
+    hip_check(hipMemcpy(count_host, loc->ry_count.p, rows * sizeof(int32_t), hipMemcpyDeviceToHost), "D2H");
+    if (!pieces) return;
+    for (size_t r = 0; r < rows; ++r) {
+      if (count_host[r] < 0) throw InternalError("geo_line_integrals: a negative count");
+      out->row_offsets[r + 1] = out->row_offsets[r] + count_host[r];
+    }
+    const long long total = out->row_offsets[rows];
+    if (total > 0) {
+      out->seg.alloc((size_t)total * out->width);
+      out->item.alloc((size_t)total);
+      loc->ry_offsets.upload(out->row_offsets.data(), rows + 1);
+      ray::launch_emit(st, dim, L.k, A, wg, loc->ry_offsets.p, out->seg.p, out->item.p);
+      hip_check(hipGetLastError(), "geo_line_integrals emit launch");
+      hip_check(hipStreamSynchronize(st), "sync geo_line_integrals emit");
+    }
+    *pieces = out.release();
+  });
+}
+int mgb_geo_line_integrals_host(mgb_geo g, int B, const double* const* z, int S, int u, int m, const double* a, const double* b,
+                                double p, double* rows, int32_t* count, long long* offsets, double* piece, int32_t* elem,
+                                long long capacity) {
+  return guard([&] {
+    ray::Call c{};
+    c.null_argument = !(g && z) || (m > 0 && !(a && b && rows && count));
+    std::vector<long long> len;
+    if (!c.null_argument && B >= 1 && B <= 65535) {
+      len.resize((size_t)B);
+      for (int k = 0; k < B; ++k) len[k] = z[k] == nullptr ? -1 : (long long)g->g.n * S;
+      c.field_len = len.data();
+    }
+    if (g) {
+      c.dim = g->g.dim;
+      c.want_len = (long long)g->g.n * S;
+    }
+    c.world = 1;
+    c.B = B, c.S = S, c.u = u, c.m = m, c.workgroup = 0, c.p = p;
+    ray::check("geo_line_integrals_host", c);
+    need((offsets == nullptr) == (piece == nullptr) && (offsets == nullptr) == (elem == nullptr),
+         "geo_line_integrals_host: offsets, pieces and elements come together");
+    need(!offsets || capacity >= 0, "geo_line_integrals_host: negative capacity");
+    if (m == 0) {
+      if (offsets) offsets[0] = 0;
+      return;
+    }
+    const interp::Locator L = interp::build_locator(g->g);
+    ray::Args A;
+    A.own = L.view(L.cellptr.data(), L.cellelem.data(), g->g.x.data());
+    A.z = z;
+    A.a = a, A.b = b;
+    A.p = p;
+    A.m = m, A.S = S, A.u = u, A.B = B;
+    A.rows = rows, A.count = count;
+    ray::line_integrals_host(L.dim, L.k, A, offsets, piece, elem, capacity);
   });
 }
 
