@@ -1849,6 +1849,8 @@ double Amg::f0_f32(int l, const float* s_host, float t) {
   double h[2];
   hip_check(hipMemcpyAsync(h, scal_.p, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx_.stream), "D2H f0_f32");
   hip_check(hipStreamSynchronize(ctx_.stream), "sync f0_f32");
+  // a row outside the domain decides the value: +inf, also where a NaN entry of that row made the linear part NaN
+  if (h[0] == (double)INFINITY) return h[0];
   return h[0] + (double)t * h[1];
 }
 

@@ -31,7 +31,18 @@ at exactly 1 the row has q = 0 and its gradient and mixed Hessian entries vanish
 single terms, 1e-30 .. 1e30; in an intersection every term in turn is the near-active one.  `level_reference()` carries rows, bounds and all to a level: f0, f1 = B' (w (F1 + t c)),
 f2 = B' diag(w F2) B for the CSR B = D R (row q K + k) of the library's own host matrices; `diag_reference()` and
 `hessian_apply_reference()` read diag(H) and H v off it, and `hessian_apply_matrix_free()` gives H v with the same bound without
-forming H, for the levels of test_gpu_elop_kinds.py that are too large for a dense long-double matrix."""
+forming H, for the levels of test_gpu_elop_kinds.py that are too large for a dense long-double matrix.
+
+WORKING PRECISION.  reference(), level_reference(), ratio(), generate(), classes() and the row sets take `prec`: F64 (the default,
+everything above) or F32, the float instantiation of the same kernel templates (csrc/kernels_f32.hip, test_gpu_barrier_rows_f32.py).
+The bound model is the same first-order one with u = U32 = 2^-24, once the inputs are the floats those kernels read: rows, w, c,
+B, coef and off rounded to float32, a = float32(fl(2.0 / p)) (the kernels cast T(P.cone[ci].a)), per-node a likewise; a_minus
+carries float's rounding of a - 1 and a - 2 (a - 2 is not exact in float for every a < 1).  Rows are generated in double as
+above, then rounded to float32 and filtered by the reference at the rounded rows.  Float has its own limits: every exact
+intermediate, phi^2, s^2 and every entry of F1 and F2 stays inside RANGE32 = (2^-100, 2^100), the closest distance is MIN_DIST32 =
+1e-5 (kappa 8 u32 < 1 on every kept row: the first-order bound means something) and the regimes are REGIMES32.  Overflow of
+1 / phi^2 in float outside that range is a known limit of the float path and not part of this check.  rows_f32() is the float
+baseline: the kernels' formulas in plain numpy float32, the counterpart of the fp64 oracle in rho_base."""
 import numpy as np
 import scipy.sparse as sp
 
@@ -43,6 +54,33 @@ MARGIN = 16.0                # chol_reference.MARGIN: same arithmetic, other ope
 RANGE = (1e-280, 1e280)      # rows where an exact intermediate leaves this range are not generated
 MIN_DIST = 1e-12             # generated rows keep every term at this relative distance or more
 P_NEAR_ONE = 1.0 + 2.0 ** -20
+U32 = 2.0 ** -24
+RANGE32 = (2.0 ** -100, 2.0 ** 100)      # float: exact intermediates, phi^2, s^2 and the entries of F1 / F2 stay inside
+MIN_DIST32 = 1e-5
+
+
+class Precision:
+    """A working precision of the kernels: the scalar type the inputs are rounded to, its unit roundoff (the unit of the bounds),
+    the range outside of which rows are not generated, the closest relative distance and the regimes of the sweep."""
+
+    def __init__(self, name, dtype, u, range_, min_dist):
+        self.name, self.dtype, self.u, self.range, self.min_dist = name, dtype, u, range_, min_dist
+        self.regimes = None                  # filled in below the case table
+
+    def rnd(self, x):
+        """x as the doubles that equal what a kernel of this precision reads."""
+        x = np.asarray(x, dtype=np.float64)
+        if self.dtype is np.float64:
+            return x
+        with np.errstate(all="ignore"):
+            return x.astype(self.dtype).astype(np.float64)
+
+    def __repr__(self):
+        return self.name
+
+
+F64 = Precision("fp64", np.float64, U, RANGE, MIN_DIST)
+F32 = Precision("fp32", np.float32, U32, RANGE32, MIN_DIST32)
 
 
 def mu_of(p):
@@ -111,10 +149,14 @@ def const(c, n):
     return V(np.full(n, c, dtype=LD))
 
 
-def a_minus(a64, k):
-    """a - k as fp64 computes it from the double a: the exact difference, and fp64's rounding error of it as its bound."""
+def a_minus(a64, k, prec=F64):
+    """a - k as the working precision computes it from its a: the exact difference, and the rounding error of the working
+    precision's difference as its bound (fp64 subtracts 1 and 2 exactly on the menu; float does not for every a < 1)."""
     exact = a64.astype(LD) - LD(k)
-    return V(exact, np.abs(exact - (a64 - np.float64(k)).astype(LD)) / LD(U))
+    if prec is F64:
+        return V(exact, np.abs(exact - (a64 - np.float64(k)).astype(LD)) / LD(U))
+    got = (a64.astype(prec.dtype) - prec.dtype(k)).astype(LD)
+    return V(exact, np.abs(exact - got) / LD(prec.u))
 
 
 # ---------------------------------------------------------------------------------------------------------- terms
@@ -129,7 +171,7 @@ def parse(term):
     return dict(kind=0, q=list(idx[:-1]), s=int(idx[-1]), s2=is2, p=p, cols=cols)
 
 
-def _power_cone(T, Y, a64, mu64):
+def _power_cone(T, Y, a64, mu64, prec=F64):
     n = Y.shape[0]
     q = [V(Y[:, i]) for i in T["q"]]
     s = V(Y[:, T["s"]])
@@ -143,7 +185,7 @@ def _power_cone(T, Y, a64, mu64):
     phi = sub(sa, qq)
     ok = (s.v > 0) & (phi.v > 0)
     F = sub(neg(log(phi)), scale(log(s), mu.v))
-    am1, am2 = a_minus(a64, 1), a_minus(a64, 2)
+    am1, am2 = a_minus(a64, 1, prec), a_minus(a64, 2, prec)
     ds = mul(a, power(s, am1))
     dds = mul(mul(a, am1), power(s, am2))
     ip = div(const(1, n), phi)
@@ -169,8 +211,10 @@ def _power_cone(T, Y, a64, mu64):
                 inter=[sa.v, qq.v, phi.v, phi.v * phi.v, s.v * s.v, ds.v])
 
 
-def _half_space(T, Y):
+def _half_space(T, Y, prec=F64):
     n = Y.shape[0]
+    off, coef = float(prec.rnd(T["off"])), [float(c) for c in prec.rnd(T["coef"])]      # the kernels cast T(coef), T(off)
+    T = dict(T, off=off, coef=coef)
     phi, mag = V(np.full(n, T["off"], dtype=LD)), np.full(n, abs(T["off"]), dtype=LD)
     for i, c in zip(T["q"], T["coef"]):
         t = mul(const(c, n), V(Y[:, i]))
@@ -192,10 +236,13 @@ class Rows:
     (every active term strictly inside) and `in_range` (every exact intermediate inside RANGE)."""
 
 
-def reference(terms, Y, a_node=None, mu_node=None, mask=None):
+def reference(terms, Y, a_node=None, mu_node=None, mask=None, prec=F64):
     """Rows of the barrier of `terms` at the rows of Y (n x K doubles).  a_node / mu_node: n x nterms doubles replacing the
-    power cones' constants; mask: n x nterms, 0 = the term is inactive at that row."""
-    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    power cones' constants; mask: n x nterms, 0 = the term is inactive at that row.  prec: the working precision -- the rows,
+    a, the per-node arrays, coef and off are rounded to it first (what its kernels read), the bounds are in its unit
+    roundoff and in_range refers to its range."""
+    Y = np.ascontiguousarray(prec.rnd(Y), dtype=np.float64)
+    RANGE = prec.range
     n, K = Y.shape
     Yl = Y.astype(LD)
     nt = len(terms)
@@ -212,11 +259,11 @@ def reference(terms, Y, a_node=None, mu_node=None, mask=None):
             assert len(set(T["cols"])) == len(T["cols"]) and all(0 <= c < K for c in T["cols"]), term
             act = np.ones(n, dtype=bool) if mask is None else np.asarray(mask)[:, ti] != 0
             if T["kind"] == 0:
-                a64 = np.full(n, a_of(T["p"])) if a_node is None else np.asarray(a_node, dtype=np.float64)[:, ti]
-                mu64 = np.full(n, mu_of(T["p"])) if mu_node is None else np.asarray(mu_node, dtype=np.float64)[:, ti]
-                t = _power_cone(T, Yl, a64, mu64)
+                a64 = prec.rnd(np.full(n, a_of(T["p"])) if a_node is None else np.asarray(a_node, dtype=np.float64)[:, ti])
+                mu64 = prec.rnd(np.full(n, mu_of(T["p"])) if mu_node is None else np.asarray(mu_node, dtype=np.float64)[:, ti])
+                t = _power_cone(T, Yl, a64, mu64, prec)
             else:
-                t = _half_space(T, Yl)
+                t = _half_space(T, Yl, prec)
             z = lambda x: V(np.where(act, x.v, 0), np.where(act, x.e, 0))
             F = add(F, z(t["F"]))
             for c, g in t["G"].items():
@@ -241,8 +288,9 @@ def reference(terms, Y, a_node=None, mu_node=None, mask=None):
     return R
 
 
-def ratio(x, exact, bound, rows=None):
-    """max over entries of |x - exact| / (u bound); an entry whose bound is zero must be met exactly."""
+def ratio(x, exact, bound, rows=None, prec=F64):
+    """max over entries of |x - exact| / (u bound), u the unit roundoff of prec; an entry whose bound is zero must be met
+    exactly."""
     x, exact, bound = np.asarray(x, dtype=LD), np.asarray(exact, dtype=LD), np.asarray(bound, dtype=LD)
     if rows is not None:
         x, exact, bound = x[rows], exact[rows], bound[rows]
@@ -250,7 +298,7 @@ def ratio(x, exact, bound, rows=None):
         return 0.0
     with np.errstate(all="ignore"):
         err = np.abs(x - exact)
-        r = np.where(err == 0, 0, np.where(bound > 0, err / (LD(U) * bound), np.inf))
+        r = np.where(err == 0, 0, np.where(bound > 0, err / (LD(prec.u) * bound), np.inf))
     r = np.where(np.isnan(r), np.inf, r)
     return float(r.max())
 
@@ -287,6 +335,8 @@ CASES = [
 # regimes: (label, target relative distance of the near-active term (None: uniform in [0.25, 1)), decades of the scale)
 REGIMES = [("1e0", None, 3), ("1e-4", 1e-4, 3), ("1e-8", 1e-8, 3), ("1e-11", 1e-11, 3), ("1e0 wide", None, 30),
            ("1e-8 wide", 1e-8, 30)]
+REGIMES32 = [("1e0", None, 3), ("1e-2", 1e-2, 3), ("1e-4", 1e-4, 3), ("1e0 wide", None, 8), ("1e-3 wide", 1e-3, 8)]
+F64.regimes, F32.regimes = REGIMES, REGIMES32
 
 
 def _magnitudes(rng, n, decades):
@@ -349,11 +399,13 @@ def _fill_half(T, Y, free, d, rng, decades):
     free[cj] = False
 
 
-def generate(terms, K, near, target, decades, n, seed):
+def generate(terms, K, near, target, decades, n, seed, prec=F64):
     """n x K doubles strictly inside every term, term `near` at a relative distance close to `target` (None: order one), the
     others at order-one distances where their columns are still free; plus the reference at those rows.  Rows that miss (a
     term whose columns were all given is infeasible or closer than MIN_DIST, the near term off target by more than 8, an
-    intermediate out of RANGE) are dropped, so fewer than n rows may come back."""
+    intermediate out of RANGE) are dropped, so fewer than n rows may come back.  For another working precision the rows are
+    generated in double all the same, then rounded to it, and the reference AT THE ROUNDED ROWS decides what is kept (its
+    range, its MIN_DIST)."""
     rng = np.random.default_rng(seed)
     m = 8 * n
     Y = np.zeros((m, K), dtype=LD)
@@ -367,25 +419,29 @@ def generate(terms, K, near, target, decades, n, seed):
             Y[:, c] = _magnitudes(rng, m, decades) * rng.choice([-1.0, 1.0], m)
     with np.errstate(all="ignore"):
         Y64 = Y.astype(np.float64)
+    if prec is not F64:
+        Y64 = prec.rnd(Y64)
     Y64 = Y64[np.all(np.isfinite(Y64), axis=1)]
-    R = reference(terms, Y64)
+    R = reference(terms, Y64, prec=prec)
     with np.errstate(all="ignore"):
-        keep = R.feasible & R.in_range & np.all(R.dist >= MIN_DIST, axis=1)
+        keep = R.feasible & R.in_range & np.all(R.dist >= prec.min_dist, axis=1)
         if target is not None:
             keep &= (R.dist[:, near] <= 8 * target) & (R.dist[:, near] >= target / 8)
     rows = np.flatnonzero(keep)[:n]
     return Y64[rows]
 
 
-def classes(rows_per_class=200, seed=20260101):
-    """The sweep: for every case of the table, every regime and every term as the near-active one, a batch of rows.  Yields
-    (label, K, terms, Y)."""
+def classes(rows_per_class=200, seed=20260101, prec=F64, only=None):
+    """The sweep: for every case of the table (only: the cases with these indices, the same rows as in the whole sweep), every
+    regime of the working precision and every term as the near-active one, a batch of rows.  Yields (label, K, terms, Y)."""
     for ci, (name, K, terms) in enumerate(CASES):
-        for ri, (rl, target, decades) in enumerate(REGIMES):
+        if only is not None and ci not in only:
+            continue
+        for ri, (rl, target, decades) in enumerate(prec.regimes):
             if decades > 3 and len(terms) > 1:
                 continue                       # the wide scales run on the single terms
             for near in range(len(terms)):
-                Y = generate(terms, K, near, target, decades, rows_per_class, seed + 1000 * ci + 10 * ri + near)
+                Y = generate(terms, K, near, target, decades, rows_per_class, seed + 1000 * ci + 10 * ri + near, prec)
                 label = "%s | %s" % (name, rl) + (" | near term %d" % near if len(terms) > 1 else "")
                 yield label, K, terms, Y
 
@@ -405,6 +461,35 @@ def hand_made():
         (2, [("linear", [0, 1], [1.0, -1.0], 0.5)], [[1.0, 2.0]], "half space: affine form < 0"),
         (4, [([1, 2, 3], 1.5), ("linear", [0], [1.0], -1.0)], [[0.5, 0.1, 0.1, 1.0], [2.0, 3.0, 0.0, 1.0]],
          "intersection: one term violated, the other satisfied"),
+    ]
+
+
+def float_representable(Y):
+    """Per row of Y: every entry is a float32 (NaN counts as one)."""
+    Y = np.asarray(Y, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        back = Y.astype(np.float32).astype(np.float64)
+    return np.all((back == Y) | np.isnan(Y), axis=1)
+
+
+def rounding_rows():
+    """Rows whose class is decided by the rounding to float: (K, terms, row, outside_in_float, what).  Every row is strictly
+    feasible in double.  outside_in_float = True: the rounded row lies on or outside the boundary, F = +inf exactly in float
+    while the double value stays finite; False: the rounded row is inside by more than the float bound of phi, F is finite."""
+    e30, e18 = 2.0 ** -30, 2.0 ** -18
+    half = [("linear", [0, 1], [1.0, -1.0], 0.5)]
+    return [
+        (3, [([0, 1, 2], 1.0)], [3.0, 4.0, 5.0 * (1 + e30)], True, "p = 1, s = 5 (1 + 2^-30) rounds to 5: phi = 0 in float"),
+        (3, [([0, 1, 2], 2.0)], [3.0, 4.0, 25.0 * (1 + e30)], True, "p = 2, s = 25 (1 + 2^-30) rounds to 25: phi = 0 in float"),
+        (3, [([0, 1, 2], 1.0)], [3.0 + 0.9 * 2.0 ** -22, 4.0, 5.0 + 0.28 * 2.0 ** -21], True,
+         "p = 1, q_1 rounds up and s down: phi < 0 in float"),
+        (4, [([0, 1, 2], 1.0, 3)], [3.0, 4.0, 7.0, -2.0 * (1 - e30)], True, "is2: s + s2 rounds to 5: phi = 0 in float"),
+        (2, half, [1.0, 1.5 * (1 - e30)], True, "half space: y_2 rounds to 1.5, affine form 0 in float"),
+        (2, half, [1.0 - 0.9 * 2.0 ** -24, 1.5 - 0.95 * 2.0 ** -24], True, "half space: y_1 rounds down to 1 - 2^-24, y_2 up to 1.5: form < 0"),
+        (3, [([0, 1, 2], 1.0)], [3.0, 4.0, 5.0 * (1 + e18 + e30)], False, "p = 1, s rounds to 5 (1 + 2^-18): inside in float"),
+        (3, [([0, 1, 2], 2.0)], [3.0, 4.0, 25.0 * (1 + e18 + e30)], False, "p = 2, s rounds to 25 (1 + 2^-18): inside in float"),
+        (4, [([0, 1, 2], 1.0, 3)], [3.0, 4.0, 7.0, -2.0 * (1 - e18 - e30)], False, "is2: s + s2 rounds to 5 + 2^-17: inside in float"),
+        (2, half, [1.0, 1.5 * (1 - e18 - e30)], False, "half space: the affine form rounds to 1.5 2^-18 in float"),
     ]
 
 
@@ -447,9 +532,10 @@ class Level:
     pass
 
 
-def level_reference(B, K, w, c, t, Dz, terms, a_node=None, mu_node=None, mask=None, hessian=True):
-    """Exact objective, gradient and Hessian of a level at the rows Dz (n x K doubles), with fp64 bounds that hold for any
-    order of summation.  B: CSR, n K x N, row q K + k.
+def level_reference(B, K, w, c, t, Dz, terms, a_node=None, mu_node=None, mask=None, hessian=True, prec=F64):
+    """Exact objective, gradient and Hessian of a level at the rows Dz (n x K doubles), with bounds (units of prec.u) that hold
+    for any order of summation in the working precision; B, w, c, t and Dz are rounded to it first.  B: CSR, n K x N, row
+    q K + k.
 
       f0F = sum_q w_q F_q               bound  sum_q w_q (bF_q + |F_q|) + (n - 1) sum_q |w_q F_q|
       f0C = sum_q w_q <c_q, Dz_q>       bound  sum_q w_q ((K + 1) sum_k |c_qk Dz_qk| + |<c_q, Dz_q>|) + (n - 1) sum_q |w_q <c_q, Dz_q>|
@@ -458,9 +544,13 @@ def level_reference(B, K, w, c, t, Dz, terms, a_node=None, mu_node=None, mask=No
       H v                               bound  (bound of H) |v| + (r + 2) (|B|' |w F2| |B|) |v|,           r = longest row of H"""
     B = sp.csr_matrix(B)
     Dz = np.ascontiguousarray(Dz, dtype=np.float64)
+    if prec is not F64:
+        B = B.copy()                          # a matrix of its own: sorting one that shares index arrays would disturb the caller's
+        B.data = prec.rnd(B.data)
+        Dz, w, c, t = np.ascontiguousarray(prec.rnd(Dz)), prec.rnd(w), prec.rnd(c), float(prec.rnd(t))
     n, N = Dz.shape[0], B.shape[1]
     assert B.shape[0] == n * K and Dz.shape[1] == K
-    R = reference(terms, Dz, a_node, mu_node, mask)
+    R = reference(terms, Dz, a_node, mu_node, mask, prec=prec)
     Lv = Level()
     Lv.rows = R
     wl, cl, Dl = np.asarray(w, dtype=LD), np.asarray(c, dtype=LD), Dz.astype(LD)
@@ -588,31 +678,148 @@ def rho_base(terms, Y, R, p_node=None, mask=None):
         return (ratio(Q.F(None, Y), R.F, R.bF), ratio(Q.F1(None, Y), R.F1, R.bF1), ratio(Q.F2(None, Y), R.F2, R.bF2))
 
 
-def node_exponent_rows(rows_per_p=60, seed=7):
+# ---------------------------------------------------------------------------------------------------------- float baseline
+def _pow_a32(s, a):
+    return np.where(a == np.float32(2), s * s, np.where(a == np.float32(1), s, np.power(s, a)))
+
+
+def rows_f32(terms, Y32, a_node=None, mu_node=None, mask=None, mutate=None):
+    """F (n), F1 (n, K), F2 (n, K, K) of the rows Y32 in plain numpy float32: the float baseline, the counterpart of the fp64
+    oracle in rho_base.  Written from the formulas of csrc/kernels_tpl.hpp (load_cone, pow_a, barrier_value and the f1 / f2
+    kernels with unit weight) without calling the library or the oracle; every operation is a float32 numpy operation in the
+    kernels' order.  F is +inf on an infeasible row; F1 and F2 are unspecified there.  `mutate` plants one error for the tests
+    of the check itself: "slot" swaps the output slots of a term's first q column and its last column (the next column of the
+    row if the term has only one), "mu" uses mu + 1, "a-1" uses the exponent a - 1 where a - 2 belongs."""
+    f = np.float32
+    assert mutate in (None, "slot", "mu", "a-1")
+    Y = np.ascontiguousarray(Y32, dtype=f)
+    n, K = Y.shape
+    one, two, four = f(1), f(2), f(4)
+    F, G, H = np.zeros(n, dtype=f), np.zeros((n, K), dtype=f), np.zeros((n, K, K), dtype=f)
+    with np.errstate(all="ignore"):
+        for ti, term in enumerate(terms):
+            T = parse(term)
+            act = np.ones(n, dtype=bool) if mask is None else np.asarray(mask)[:, ti] != 0
+            g, h = np.zeros((n, K), dtype=f), np.zeros((n, K, K), dtype=f)
+            if T["kind"] == 1:
+                coef = [f(c) for c in T["coef"]]
+                phi = np.full(n, f(T["off"]), dtype=f)
+                for i, ci in zip(T["q"], coef):
+                    phi = phi + ci * Y[:, i]
+                ok = phi > 0
+                Ft = -np.log(phi)
+                ip2 = one / (phi * phi)
+                for i, ci in zip(T["q"], coef):
+                    g[:, i] = -(ci / phi)
+                    for j, cj in zip(T["q"], coef):
+                        h[:, i, j] = ci * cj * ip2
+            else:
+                a = np.full(n, f(a_of(T["p"])), dtype=f) if a_node is None else np.asarray(a_node)[:, ti].astype(f)
+                mu = np.full(n, f(mu_of(T["p"])), dtype=f) if mu_node is None else np.asarray(mu_node)[:, ti].astype(f)
+                q = [Y[:, i] for i in T["q"]]
+                qq = np.zeros(n, dtype=f)
+                for qi in q:
+                    qq = qq + qi * qi
+                s = Y[:, T["s"]] + Y[:, T["s2"]] if T["s2"] >= 0 else Y[:, T["s"]]
+                ok = s > 0
+                sa = np.where(ok, _pow_a32(s, a), f(-1))
+                phi = sa - qq
+                ok = ok & (phi > 0)
+                if mutate == "mu":
+                    mu = mu + one
+                Ft = -np.log(phi) - mu * np.log(s)
+                ds = a * _pow_a32(s, a - one)
+                dds = np.where(a == one, f(0), a * (a - one) * _pow_a32(s, a - (one if mutate == "a-1" else two)))
+                ip = one / phi
+                ip2 = ip * ip
+                gs = -ds / phi - mu / s
+                hss = -dds * ip + ds * ds * ip2 + mu / (s * s)
+                scols = [T["s"]] + ([T["s2"]] if T["s2"] >= 0 else [])
+                for i, ci in enumerate(T["q"]):
+                    g[:, ci] = two * q[i] / phi
+                    for j, cj in enumerate(T["q"]):
+                        h[:, ci, cj] = four * q[i] * q[j] * ip2 + (two * ip if i == j else f(0))
+                    for cs in scols:
+                        h[:, ci, cs] = h[:, cs, ci] = -two * q[i] * ds * ip2
+                for cs in scols:
+                    g[:, cs] = gs
+                    for cs_ in scols:
+                        h[:, cs, cs_] = hss
+            if mutate == "slot":
+                c0 = T["cols"][0]
+                c1 = T["cols"][-1] if len(T["cols"]) > 1 else (c0 + 1) % K
+                g[:, [c0, c1]] = g[:, [c1, c0]]
+                h[:, [c0, c1], :] = h[:, [c1, c0], :]
+                h[:, :, [c0, c1]] = h[:, :, [c1, c0]]
+            F = F + np.where(act, np.where(ok, Ft, f(np.inf)), f(0))
+            G = G + np.where(act[:, None], g, f(0))
+            H = H + np.where(act[:, None, None], h, f(0))
+    assert F.dtype == f and G.dtype == f and H.dtype == f
+    return F, G, H
+
+
+def rho_base32(terms, Y, R, a_node=None, mu_node=None, mask=None, mutate=None):
+    """(ratio of F, of F1, of F2) of rows_f32 against the float reference R = reference(..., prec=F32) at the rows Y."""
+    F, G, H = rows_f32(terms, Y, a_node, mu_node, mask, mutate)
+    return (ratio(F, R.F, R.bF, prec=F32), ratio(G, R.F1, R.bF1, prec=F32), ratio(H, R.F2, R.bF2, prec=F32))
+
+
+def level_f32(B, K, w, c, t, Dz, terms, a_node=None, mu_node=None, mask=None, hessian=True):
+    """The level formulas in numpy float32 at the state Dz, the level baseline of the float kernels: (f0F, f0C, g, H) with the
+    row values w F and w <c, Dz> formed in float and summed in double (as the kernels hand them to the double reduction),
+    g = B' (w (F1 + t c)) and H = B' diag(w F2) B as float32 sparse products."""
+    f = np.float32
+    B32 = sp.csr_matrix(B).astype(f)          # a copy with index arrays of its own
+    Y, w32, c32, t32 = np.asarray(Dz).astype(f), np.asarray(w).astype(f), np.asarray(c).astype(f), f(t)
+    n = Y.shape[0]
+    F, G, H = rows_f32(terms, Y, a_node, mu_node, mask)
+    with np.errstate(all="ignore"):
+        cd = np.zeros(n, dtype=f)
+        for j in range(K):
+            cd = cd + c32[:, j] * Y[:, j]
+        f0F, f0C = float((w32 * F).astype(np.float64).sum()), float((w32 * cd).astype(np.float64).sum())
+        g = B32.T @ (w32[:, None] * (G + t32 * c32)).reshape(-1)
+        assert g.dtype == f
+        if not hessian:
+            return f0F, f0C, g, None
+        q = np.repeat(np.arange(n), K * K)
+        kk = np.tile(np.repeat(np.arange(K), K), n)
+        ll = np.tile(np.arange(K), n * K)
+        blk = sp.csr_matrix(((w32[:, None, None] * H).reshape(-1), (q * K + kk, q * K + ll)), shape=(n * K, n * K))
+        Hd = (B32.T @ blk @ B32).toarray()
+        assert Hd.dtype == f
+    return f0F, f0C, g, Hd
+
+
+def node_exponent_rows(rows_per_p=60, seed=7, prec=F64):
     """Rows for a power cone whose exponent varies from row to row and crosses p = 2 (mu takes all three values):
-    (K, terms, Y, p_node); the term's own p is a placeholder, as in AMG(cones=[(idx, p(x))])."""
+    (K, terms, Y, p_node); the term's own p is a placeholder, as in AMG(cones=[(idx, p(x))]).  The distances are those of the
+    working precision's narrow regimes."""
     ps = [1.0, 1.1, 1.7, 2.0, 2.1, 2.6, 8.0]
     Ys, pn = [], []
+    regimes = [(None, 3), (1e-4, 3), (1e-8, 3), (1e-11, 3)] if prec is F64 else [r[1:] for r in prec.regimes if r[2] <= 3]
     for i, p in enumerate(ps):
-        for j, (target, decades) in enumerate([(None, 3), (1e-4, 3), (1e-8, 3), (1e-11, 3)]):
-            Y = generate([([1, 2, 3], p)], 4, 0, target, decades, rows_per_p // 4, seed + 10 * i + j)
+        for j, (target, decades) in enumerate(regimes):
+            Y = generate([([1, 2, 3], p)], 4, 0, target, decades, rows_per_p // len(regimes), seed + 10 * i + j, prec)
             Ys.append(Y)
             pn.append(np.full(len(Y), p))
     return 4, [([1, 2, 3], 1.0)], np.vstack(Ys), np.concatenate(pn)[:, None]
 
 
-def piecewise_rows(n=240, seed=11):
+def piecewise_rows(n=240, seed=11, prec=F64):
     """Rows for a piecewise set -- the cone everywhere, the half space on some rows only; where the half space is masked out
-    half of the rows violate it (an inactive term constrains nothing): (K, terms, Y, mask)."""
+    half of the rows violate it (an inactive term constrains nothing): (K, terms, Y, mask).  The distances are those of the
+    working precision's narrow regimes."""
     terms = [([1, 2, 3], 1.5), ("linear", [0], [1.0], -0.25)]
     rng = np.random.default_rng(seed)
-    Y = np.vstack([generate(terms, 4, near, target, 3, n // 6, seed + 10 * near + j)
-                   for near in (0, 1) for j, target in enumerate((None, 1e-4, 1e-9))])
+    targets = (None, 1e-4, 1e-9) if prec is F64 else tuple(r[1] for r in prec.regimes if r[2] <= 3)
+    Y = np.vstack([generate(terms, 4, near, target, 3, n // 6, seed + 10 * near + j, prec)
+                   for near in (0, 1) for j, target in enumerate(targets)])
     mask = np.ones((len(Y), 2), dtype=bool)
     mask[:, 1] = rng.random(len(Y)) < 0.5
     out = ~mask[:, 1] & (rng.random(len(Y)) < 0.5)
     Y[out, 0] = -np.abs(Y[out, 0]) - 1.0
-    return 4, terms, Y, mask
+    return 4, terms, (Y if prec is F64 else prec.rnd(Y)), mask
 
 
 # ---------------------------------------------------------------------------------------------------------- golden states

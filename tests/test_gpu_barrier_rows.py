@@ -27,7 +27,8 @@ barrier_reference.CASES x REGIMES x near-active term; positions (grid-stride loo
 Python types accept an empty matrix); argument errors for repeated columns inside a power cone; states of the Newton path
 through AMG.apply_D / f0 / f0_trial / f1 / f2 / f2_template_f64 / hessian_apply at the golden end points (t = 1e8, kappa up to
 2.4e9), at states with a term mask, per-node exponents, an obstacle in contact and the feasibility slack column, and at scale
-(fem2d L = 7 and 8).  Float32 is out of scope: at kappa ~ 1e8 a float row has no correct digit."""
+(fem2d L = 7 and 8).  The Float32 instantiation of the same templates is held to exact rows at float precision, in the range
+the float solve works in (t up to 1e4, kappa 8 u32 < 1), by test_gpu_barrier_rows_f32.py."""
 import os
 
 import numpy as np
