@@ -878,6 +878,62 @@ int mgb_geo_line_integrals_host(mgb_geo g, int B, const double* const* z /* B ar
                                 double* rows /* B m x MGB_RAY_COLS */, int32_t* count /* B m */, long long* offsets_or_null,
                                 double* piece_or_null, int32_t* elem_or_null, long long capacity);
 
+/* ---- time statistics of a run of snapshots ------------------------------------------------------------------------------ *
+ * The one reduction along the TIME axis, per node: for B >= 2 snapshots z[0..B-1] (n x S row-major, column u) at the strictly
+ * increasing times ts[0..B-1] of one geometry, what each node saw -- dose, peak, trough, variation -- and, per level c, when
+ * the value first rose above c, when it last fell back, for how long and by how much it was above.  (csrc/timestat.hpp is the
+ * rule, run by the gfx950 kernel and by the host restatement.)
+ * Notation: v_m = z[m][i S + u]; h_m = ts[m+1] - ts[m], ONE subtraction, done once per call on the host and handed to both
+ * sides.  A value is ABOVE when v > c (the rule of mgb_geo_level_sets: a value on the level is not above).  Every sum is a
+ * plain running sum in ascending m.
+ * Node table, n x MGB_TIMESTAT_NODE_COLS:
+ *   [0] integral   acc += (0.5 h_m) (v_m + v_{m+1})                  [5] variation  sum |v_{m+1} - v_m|
+ *   [1] max_m v_m  [2] ts of the FIRST m that attains it             [6] rate       max_m |v_{m+1} - v_m| / h_m
+ *   [3] min_m v_m  [4] its time, likewise                            [7] change     v_{B-1} - v_0
+ * Level table, nl x n x MGB_TIMESTAT_LEVEL_COLS (level-major, so that a wave's stores are contiguous):
+ *   [0] arrival  [1] left  [2] exposure  [3] excess  [4] entries (a whole number, stored as a double)
+ *   start: v_0 > c gives entries = 1, arrival = ts[0].
+ *   interval with both ends above:   exposure += h_m;   excess += h_m ((v_m + v_{m+1}) 0.5 - c).
+ *   interval with exactly one end above, always parametrised from the not-above end lo to the above end hi:
+ *     t = (c - v_lo) / (v_hi - v_lo),  f = 1.0 - t,  e = f h_m;   exposure += e;   excess += e ((v_hi - c) 0.5);
+ *     rising (hi = m+1):  where there is no entry yet arrival = ts[m] + t h_m;  entries += 1.
+ *     falling:            left = ts[m+1] - t h_m  (the last one stays).
+ *   interval with neither end above: nothing.   arrival / left without an event hold `never` (any double, NaN included).
+ * A node with a non-finite v_m has NaN in all 8 node columns and all 5 columns of every level (`never` does not apply), and its
+ * terms reach the totals as NaN: a NaN is never dropped.
+ * Totals, (1 + nl) rows of 5 doubles (three sums, two NaN-sticky maxima), w the nodal weights of the geometry:
+ *   row 0      [0] sum w integral       [1] sum w variation   [2] sum w change   [3] max_i max_i        [4] max_i (-min_i)
+ *   row 1 + l  [0] sum w [entries > 0]  [1] sum w exposure    [2] sum w excess   [3] max arrival over the nodes with
+ *                                                                                    entries > 0        [4] max_i exposure_i
+ *   Both maxima of every row start from -inf (the identity of the level sets): row 1 + l holds -inf in [3] where no node was reached.
+ * Launches: the statistics on a grid (ceil(n / 256), 1 + ceil(nl / chunk)) of 256 threads, one node per thread, which walks
+ * m = 0..B-1 once with several loads in flight and its state in registers -- y = 0 the node columns and row 0, y >= 1 a chunk
+ * of levels -- and writes one partial row per workgroup and result row; then one workgroup per row, which folds the partials in
+ * the order of the other field reductions.  Two launches, one wait and one copy of the totals whatever B and nl are; the
+ * snapshot pointers, h, ts and the levels go up in one copy.  The tables stay on the device.  No atomics.
+ *   Cost: every slab of workgroups reads all B snapshots, so a call reads the run 1 + ceil(nl / chunk) times (chunk = 4:
+ *   3 passes for 8 levels, 1025 for the 4096 allowed) and writes 40 n bytes per level.  The launches stay two, the traffic
+ *   grows with nl: pass the levels that are wanted, not a fine ladder of them.
+ *   A repeated call returns the same bits.  Row 1 + l and the level table of level l do not depend on nl, on the other levels or
+ *   on the chunk.  The bits depend on the B snapshots and times handed over alone: a window of a longer run is a call of its own.
+ *   The rule is compiled with fp contraction off on both sides: device and host restatement agree bit for bit in both tables
+ *   and in the maxima; the three sums differ by their order (host: serial, compensated).
+ * MGB_E_ARG, before anything is launched or written: a null argument or field (levels and level may be null where nl = 0);
+ * B < 2; ts not finite or not strictly increasing; nl < 0 or nl > 4096; a non-finite level; S < 1; u outside [0, S); a vector
+ * of the wrong length or of another context; an output that is also an input or the other output; a sharded context. */
+#define MGB_TIMESTAT_NODE_COLS 8
+#define MGB_TIMESTAT_LEVEL_COLS 5
+int mgb_geo_time_stats(mgb_locator loc, int B, const mgb_vec* z /* B vectors of n x S */, const double* ts_host /* B */, int S,
+                       int u, int nl, const double* levels_host_or_null, double never,
+                       mgb_vec node /* n x MGB_TIMESTAT_NODE_COLS */, mgb_vec level_or_null /* nl x n x MGB_TIMESTAT_LEVEL_COLS */,
+                       double* out_host /* (1 + nl) x 5 */);
+/* host restatement (no context, no GPU): the same per-node routines, serially in ascending node order; the three sums are
+ * compensated (Neumaier) as in the other _host functions. */
+int mgb_geo_time_stats_host(mgb_geo g, int B, const double* const* z /* B arrays of n x S */, const double* ts /* B */, int S,
+                            int u, int nl, const double* levels_or_null, double never,
+                            double* node /* n x MGB_TIMESTAT_NODE_COLS */, double* level_or_null /* nl x n x MGB_TIMESTAT_LEVEL_COLS */,
+                            double* out /* (1 + nl) x 5 */);
+
 /* ---- boundary facets of a geometry and boundary integrals of p-Laplace solutions --------------------------------------- *
  * The elements are broken and their quadrature is nodal: every node of a boundary facet is a row of x and z already, so the
  * boundary rule of a geometry is a list of nf facets of q nodes each: q global rows, q weights omega, the outward unit normal n,

@@ -41,7 +41,7 @@ __all__ = [
     "path_lines", "PathLines", "sections", "Sections", "line_integrals", "project", "LineIntegrals", "boundary", "boundary_flux", "Boundary", "BoundaryFlux",
     "dirichlet_on", "neumann_load", "NeumannLoad",
     "interior", "InteriorFacets", "estimate", "ErrorIndicators", "mark", "refine_triangles", "adapt",
-    "estimate_steps", "StepIndicators", "refine_times", "adapt_time",
+    "estimate_steps", "StepIndicators", "refine_times", "adapt_time", "time_stats", "TimeStats",
 ]
 
 
@@ -2317,6 +2317,138 @@ def level_sets(obj, levels, u=0, z=None, refine=0, segments=True) -> LevelSets:
         finally:
             call("mgb_levelset_destroy", h)
     return LevelSets(lv[0].item() if scalar else lv, rows, counts, ts, (ts is None, scalar), dim, int(refine), offsets, seg, item)
+
+
+# --------------------------------------------------------------------------- time statistics of parabolic runs
+
+
+class TimeStats:
+    """Result of time_stats(): what every node saw over the window `ts` of a run.  `node` (n, 8) and `level` (nl * n, 5;
+    None without levels) are the HPCMatrix tables of the C ABI and stay on the device; the array attributes copy a table on
+    first use and cache it.  Per node, shape (n,): `integral`, `mean` (= integral / (ts[-1] - ts[0])), `max`, `tmax`, `min`,
+    `tmin`, `variation`, `rate`, `change`.  Per node and level, (n,) for a scalar level and (n, nl) for an array: `arrival`,
+    `left` (the value `never` where there is none), `exposure`, `excess`, `entries` (int64), `reached` (= entries > 0).
+    Totals, floats: `total`, `total_variation`, `total_change`, `peak`, `trough`; per level (a float for a scalar level):
+    `reached_measure`, `exposure_total`, `excess_total`, `last_arrival` (-inf where nothing was reached), `longest_exposure`.
+    `rows` is the raw (1 + nl, 5) table.  A node with a non-finite value in the window holds NaN everywhere (`entries` then
+    reads as the smallest int64 and `reached` as False)."""
+
+    _NODE = {"integral": 0, "max": 1, "tmax": 2, "min": 3, "tmin": 4, "variation": 5, "rate": 6, "change": 7}
+    _LEVEL = {"arrival": 0, "left": 1, "exposure": 2, "excess": 3}
+    _ROW0 = {"total": 0, "total_variation": 1, "total_change": 2, "peak": 3}
+    _ROWL = {"reached_measure": 0, "exposure_total": 1, "excess_total": 2, "last_arrival": 3, "longest_exposure": 4}
+
+    def __init__(self, node, level, rows, ts, levels, scalar):
+        self.node, self.level, self.rows, self.ts, self.levels = node, level, rows, ts, levels
+        self._scalar, self._node_host, self._level_host = scalar, None, None
+
+    def _node_table(self):
+        if self._node_host is None:
+            self._node_host = self.node.to_numpy()
+        return self._node_host
+
+    def _level_table(self, name):
+        if self.level is None:
+            raise ValueError("TimeStats.%s: time_stats was called without levels" % name)
+        if self._level_host is None:
+            n = self.node.shape[0]
+            self._level_host = self.level.to_numpy().reshape(-1, n, 5)
+        return self._level_host
+
+    def _per_level(self, a):
+        return a[0].copy() if self._scalar else a.T.copy()
+
+    def __getattr__(self, name):
+        if name in TimeStats._NODE:
+            return self._node_table()[:, TimeStats._NODE[name]].copy()
+        if name in TimeStats._LEVEL:
+            return self._per_level(self._level_table(name)[:, :, TimeStats._LEVEL[name]])
+        if name in TimeStats._ROW0:
+            return float(self.rows[0, TimeStats._ROW0[name]])
+        if name in TimeStats._ROWL:
+            if self.level is None:
+                raise ValueError("TimeStats.%s: time_stats was called without levels" % name)
+            col = self.rows[1:, TimeStats._ROWL[name]]
+            return float(col[0]) if self._scalar else col.copy()
+        raise AttributeError(name)
+
+    @property
+    def mean(self) -> np.ndarray:
+        return self.integral / (self.ts[-1] - self.ts[0])
+
+    @property
+    def trough(self) -> float:
+        return -float(self.rows[0, 4])
+
+    @property
+    def entries(self) -> np.ndarray:
+        with np.errstate(invalid="ignore"):
+            return self._per_level(self._level_table("entries")[:, :, 4]).astype(np.int64)
+
+    @property
+    def reached(self) -> np.ndarray:
+        return self._per_level(self._level_table("reached")[:, :, 4]) > 0.0
+
+    def __repr__(self):
+        return "TimeStats(ts=[%g .. %g], levels=%r, total=%r, peak=%r, trough=%r)" % (
+            self.ts[0], self.ts[-1], self.levels, self.total, self.peak, self.trough)
+
+
+def _snapshot_index(v, T, name, who):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise TypeError("%s: %s must be a snapshot index (an int), got %r" % (who, name, v))
+    if not -T <= v < T:
+        raise ValueError("%s: %s = %d is not one of the %d snapshots" % (who, name, v, T))
+    return int(v) % T
+
+
+def time_stats(par, levels=None, u=0, start=0, stop=None, never=float("nan")) -> TimeStats:
+    """What every node of a ParabolicSOL saw over time, reduced along the time axis on the device (csrc/timestat.hip; the rule
+    is in include/mgb_hip.h and DESIGN.md section 4u): the trapezoid integral (the dose), peak and trough with their times,
+    total variation, the largest rate of change, and per level c the arrival time (first rise above c, interpolated linearly
+    between snapshots), the last time the value fell back, the time spent above c and the integral of the excess over c.
+    `u`: the column (negative: from the end); `start`, `stop`: the first and the last snapshot of the window (negative: from
+    the end; stop=None: the last), at least 2 snapshots; `levels`: None, a finite scalar or a 1-D array; `never`: the value of
+    `arrival` / `left` where there is none -- NaN, or any float, e.g. ts[-1] + 1 to draw isochrones with
+    level_sets(geometry, c, z=st.arrival).  One statistics launch and one finish launch whatever len(ts) and len(levels) are
+    (every 4 levels read the run once more: 1 + ceil(len(levels) / 4) passes); the per-node tables stay on the device (TimeStats.node, TimeStats.level)."""
+    who = "time_stats"
+    if not isinstance(par, ParabolicSOL):
+        raise TypeError("time_stats: expected a ParabolicSOL")
+    geometry, fields, ts = _level_fields(who, par, None)
+    T = len(fields)
+    a = _snapshot_index(start, T, "start", who)
+    b = T - 1 if stop is None else _snapshot_index(stop, T, "stop", who)
+    if b - a + 1 < 2:
+        raise ValueError("time_stats: the window start..stop = %d..%d holds fewer than 2 snapshots" % (a, b))
+    if isinstance(never, bool) or not isinstance(never, (int, float, np.integer, np.floating)):
+        raise TypeError("time_stats: never must be a float, got %r" % (never,))
+    tw = f64(np.asarray(ts, dtype=np.float64)[a:b + 1])
+    if tw.ndim != 1 or not np.all(np.isfinite(tw)) or not np.all(np.diff(tw) > 0):
+        raise ValueError("time_stats: the times of the window must be finite and strictly increasing")
+    lv, scalar = (None, False) if levels is None else _level_values(who, levels)
+    nl = 0 if lv is None else lv.size
+    if nl > 4096:
+        raise ValueError("time_stats: at most 4096 levels per call, got %d" % nl)
+    loc, backend = _locator_of(geometry)
+    vecs = [_nodal_values(geometry, zk, backend, who) for zk in fields[a:b + 1]]
+    B, S, n = len(vecs), vecs[0][1], len(geometry.w)
+    if any(Sk != S for _, Sk in vecs):
+        raise ValueError("time_stats: the snapshots have different numbers of columns")
+    u = _energy_column(u, S, "u", who)
+
+    def table_of(rows, cols):
+        out = HPCMatrix.__new__(HPCMatrix)
+        out.shape, out.backend = (rows, cols), backend
+        out._v = HPCVector(rows * cols, backend)
+        return out
+
+    node, level = table_of(n, 8), (table_of(nl * n, 5) if nl else None)
+    table = (C.c_void_p * B)(*[v.handle.value for v, _ in vecs])
+    rows = np.empty((1 + nl, 5))
+    call("mgb_geo_time_stats", loc, B, table, dptr(tw), S, u, nl, dptr(lv) if nl else None, float(never), node._v.handle,
+         level._v.handle if nl else None, dptr(rows))
+    return TimeStats(node, level, rows, tw, None if lv is None else (lv[0].item() if scalar else lv), scalar)
 
 
 # --------------------------------------------------------------------------- isosurfaces of 3-D solutions

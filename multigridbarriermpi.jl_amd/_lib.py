@@ -168,6 +168,9 @@ PROTOTYPES = {
                                c_i32_p, C.POINTER(H)],
     "mgb_geo_line_integrals_host": [H, C.c_int, C.POINTER(c_dbl_p), C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, C.c_double, c_dbl_p,
                                     c_i32_p, c_ll_p, c_dbl_p, c_i32_p, C.c_longlong],
+    "mgb_geo_time_stats": [H, C.c_int, C.POINTER(H), c_dbl_p, C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_double, H, H, c_dbl_p],
+    "mgb_geo_time_stats_host": [H, C.c_int, C.POINTER(c_dbl_p), c_dbl_p, C.c_int, C.c_int, C.c_int, c_dbl_p, C.c_double, c_dbl_p,
+                                c_dbl_p, c_dbl_p],
     "mgb_geo_path_lines": [H, C.c_int, C.POINTER(H), c_dbl_p, C.c_int, C.c_int, C.c_int, c_dbl_p, c_i32_p, C.c_int, C.c_int,
                            C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, c_dbl_p, c_dbl_p, c_i32_p, c_i32_p, c_i32_p,
                            c_i32_p, C.POINTER(H)],

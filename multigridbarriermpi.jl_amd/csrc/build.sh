@@ -51,6 +51,8 @@ compile "$HERE/_obj/section.o" "$HERE/section.hip" "$HIPCC" --offload-arch=gfx95
 compile "$HERE/_obj/pathline.o" "$HERE/pathline.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS -ffp-contract=off
 # ray.hip: the same for the line integrals (ray.hpp on top of section.hpp and flowline.hpp); its object goes last on the link line
 compile "$HERE/_obj/ray.o" "$HERE/ray.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS -ffp-contract=off
+# timestat.hip: the same for the time statistics (timestat.hpp); its object goes last on the link line
+compile "$HERE/_obj/timestat.o" "$HERE/timestat.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS -ffp-contract=off
 compile "$HERE/_obj/boundary.o" "$HERE/boundary.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/estimate.o" "$HERE/estimate.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
 compile "$HERE/_obj/parabolic.o" "$HERE/parabolic.hip" "$HIPCC" --offload-arch=gfx950 $CXXFLAGS
@@ -63,5 +65,5 @@ for pid in "${pids[@]}"; do
   wait "$pid" || { echo "build.sh: a compile job failed" >&2; exit 1; }
 done
 rm -f "$OUT/libmgb_hip.so"
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,chol_premap,chol_plan,kernels,kernels_f32,mg,interp,reduce,norms,energy,levelset,isosurface,boundary,estimate,parabolic,gpuchol,amg,amg_mg,comm,capi,flowline,section,pathline,ray}.o -lpthread -ldl
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libmgb_hip.so" "$HERE"/_obj/{geometry,mfchol,bwd_fused,chol_premap,chol_plan,kernels,kernels_f32,mg,interp,reduce,norms,energy,levelset,isosurface,boundary,estimate,parabolic,gpuchol,amg,amg_mg,comm,capi,flowline,section,pathline,ray,timestat}.o -lpthread -ldl
 echo "built $OUT/libmgb_hip.so"

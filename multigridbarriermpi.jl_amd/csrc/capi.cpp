@@ -21,6 +21,7 @@
 #include "mixed.hpp"
 #include "norms.hpp"
 #include "section.hpp"
+#include "timestat.hpp"
 
 using namespace mgb;
 
@@ -74,6 +75,8 @@ struct mgb_locator_s {
   DevBuf<int32_t> ry_count;                        // ... the owned pieces of every row
   DevBuf<long long> ry_offsets;                    // ... the first piece of every row
   DevBuf<const double*> ry_table;                  // ... and the device table of field pointers, uploaded per call
+  DevBuf<double> tst_scratch;                      // mgb_geo_time_stats: partials and results, grown on demand
+  DevBuf<uint64_t> tst_uniform;                    // ... snapshot pointers, steps, times and levels of the call, uploaded in one copy
 };
 struct mgb_flowpath_s {
   mgb_ctx_s* ctx;
@@ -1619,6 +1622,82 @@ int mgb_geo_level_sets_host(mgb_geo g, int B, const double* const* z, int S, int
     A.levels = levels;
     A.nel = L.nel, A.S = S, A.u = u, A.B = B, A.nl = nl, A.refine = refine;
     levelset::level_sets_host(L.dim, A, out, counts, row_offsets, seg, item, capacity);
+  });
+}
+
+// ---- time statistics of a run of snapshots (timestat.hpp / timestat.hip)
+namespace {
+// what both entry points check alike (timestat::check), and the steps h_m = ts[m+1] - ts[m] both sides are handed
+std::vector<double> time_steps(const char* who, bool null_argument, int B, const double* ts, int S, int u, int nl, const double* levels) {
+  timestat::Call c;
+  c.null_argument = null_argument;
+  c.B = B, c.S = S, c.u = u, c.nl = nl, c.ts = ts, c.levels = levels;
+  timestat::check(who, c);
+  std::vector<double> h((size_t)B - 1);
+  for (int m = 0; m + 1 < B; ++m) h[m] = ts[m + 1] - ts[m];
+  return h;
+}
+}  // namespace
+int mgb_geo_time_stats(mgb_locator loc, int B, const mgb_vec* z, const double* ts_host, int S, int u, int nl,
+                       const double* levels_host, double never, mgb_vec node, mgb_vec level, double* out_host) {
+  return guard([&] {
+    const bool null_argument = !(loc && z && ts_host && node && out_host) || (nl > 0 && !(levels_host && level));
+    const std::vector<double> h = time_steps("geo_time_stats", null_argument, B, ts_host, S, u, nl, levels_host);
+    need(loc->ctx->ctx.world == 1, "geo_time_stats: sharded contexts are not supported");
+    const interp::Locator& L = loc->loc;
+    std::vector<const double*> table;
+    field_table("geo_time_stats", loc, B, z, S, table);
+    need(node->n == (long long)L.n * timestat::kNodeCols, "geo_time_stats: node must hold n x 8 values");
+    need(nl == 0 || level->n == (long long)nl * L.n * timestat::kLevelCols, "geo_time_stats: level must hold nl x n x 5 values");
+    need(node->ctx == loc->ctx && (nl == 0 || level->ctx == loc->ctx), "geo_time_stats: vectors of another context");
+    need(nl == 0 || node != level, "geo_time_stats: node and level are the same vector");
+    for (int b = 0; b < B; ++b) need(z[b] != node && (nl == 0 || z[b] != level), "geo_time_stats: an output is also an input");
+    hipStream_t st = loc->ctx->ctx.stream;
+    hip_check(hipSetDevice(loc->ctx->ctx.device), "hipSetDevice");
+    const size_t nwg = (size_t)reduce::workgroups(L.n), rows = 1 + (size_t)nl;
+    const size_t nd = timestat::scratch_doubles((size_t)nl, nwg);
+    if (loc->tst_scratch.n < nd) loc->tst_scratch.alloc(nd);
+    // the uniform data of the call in ONE copy: B pointers | B - 1 steps | B times | nl levels, 8 bytes each
+    std::vector<uint64_t> uni((size_t)B + h.size() + (size_t)B + (size_t)nl);
+    static_assert(sizeof(const double*) == 8 && sizeof(double) == 8, "8-byte words");
+    std::memcpy(uni.data(), table.data(), (size_t)B * 8);
+    std::memcpy(uni.data() + B, h.data(), h.size() * 8);
+    std::memcpy(uni.data() + B + h.size(), ts_host, (size_t)B * 8);
+    if (nl) std::memcpy(uni.data() + B + h.size() + B, levels_host, (size_t)nl * 8);
+    loc->tst_uniform.upload(uni.data(), uni.size());      // every earlier launch that read it has been waited for
+    timestat::Args A;
+    A.z = reinterpret_cast<const double* const*>(loc->tst_uniform.p);
+    A.h = reinterpret_cast<const double*>(loc->tst_uniform.p + B);
+    A.ts = A.h + h.size();
+    A.levels = A.ts + B;
+    A.w = loc->w.p;
+    A.node = node->buf.p;
+    A.level = nl ? level->buf.p : nullptr;
+    A.never = never;
+    A.n = L.n, A.S = S, A.u = u, A.B = B, A.nl = nl;
+    timestat::launch_time_stats(st, A, loc->tst_scratch.p);
+    hip_check(hipGetLastError(), "geo_time_stats launch");
+    hip_check(hipStreamSynchronize(st), "sync geo_time_stats");
+    hip_check(hipMemcpy(out_host, loc->tst_scratch.p + timestat::results_offset((size_t)nl, nwg), rows * reduce::kCols * sizeof(double),
+                        hipMemcpyDeviceToHost), "D2H");
+  });
+}
+int mgb_geo_time_stats_host(mgb_geo g, int B, const double* const* z, const double* ts, int S, int u, int nl, const double* levels,
+                            double never, double* node, double* level, double* out) {
+  return guard([&] {
+    const bool null_argument = !(g && z && ts && node && out) || (nl > 0 && !(levels && level));
+    const std::vector<double> h = time_steps("geo_time_stats_host", null_argument, B, ts, S, u, nl, levels);
+    for (int b = 0; b < B; ++b) need(z[b] != nullptr, "geo_time_stats_host: null field");
+    need(g->g.w.size() == (size_t)g->g.n, "geo_time_stats_host: the geometry must carry one weight per node");
+    need(nl == 0 || node != level, "geo_time_stats_host: node and level are the same array");
+    need(node != out && (nl == 0 || level != out), "geo_time_stats_host: out is also a table");
+    for (int b = 0; b < B; ++b)
+      need(z[b] != node && z[b] != out && (nl == 0 || z[b] != level), "geo_time_stats_host: an output is also an input");
+    timestat::Args A;
+    A.z = z, A.h = h.data(), A.ts = ts, A.levels = levels, A.w = g->g.w.data();
+    A.node = node, A.level = nl ? level : nullptr, A.never = never;
+    A.n = g->g.n, A.S = S, A.u = u, A.B = B, A.nl = nl;
+    timestat::time_stats_host(A, out);
   });
 }
 
